@@ -12,12 +12,15 @@ split_by_bytes); each rank generates and processes
 its own range (no string data crosses xGMI), and one all-gather of a u64
 places every rank's encoded output in the global layout (output_offsets).
 value = plaintext bytes of all ranks x steps / max-over-ranks wall time of
-the timed region (barrier + synchronize on both sides), GiB/s.  The decoded
-output is checked against the input after the timed region (bit-exact), and
+the timed region (barrier + synchronize on both sides), GiB/s.
+
+A plain run does only that: set up, warm up, time the steps, write the last
+step's outputs if --dump-outputs DIR is given, print the result line.  With
+--full the decoded output is then checked against the input (bit-exact), and
 per-kernel HIP-event times from a second pass give the roofline of the
 dominant kernel.
 
-`extra` also carries (never the value): config 5 (16M Zipf-length strings
+With --full, `extra` also carries (never the value): config 5 (16M Zipf-length strings
 1..4096 B, split by bytes over the ranks), config 4 (65,536 header blocks at
 dynamic table 0 through qh_decode_sections_batch, split by block), alphabet
 U, the PCIe-inclusive host path, and the CPU baseline of BASELINE.md (the
@@ -48,7 +51,7 @@ METRIC = "GiB/s device-resident QPACK Huffman encode+decode, 1M strings; bit-exa
 SEED5, SEED4 = 0x5EED0005, 0x5EED0004
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (200 steps: the timed region's fixed cost -- the first launch after the
@@ -78,7 +81,17 @@ def parse():
                     help="skip the config 4 / config 5 / alphabet-U legs in extra")
     ap.add_argument("--profile-only", action="store_true",
                     help="just run warmup+steps (for rocprofv3), minimal reporting")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is reported beside the value: "
+                         "the bit-exact check, per-kernel times and roofline, counter passes, configs "
+                         "1 / 4 / 5, alphabet U, the host path and the CPU baseline (the --no-* options "
+                         "trim these legs); without it the run sets up, warms up, times the steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left in the caller's output "
+                         "buffers as DIR/<name>.npy (float32 / float64, see dump_outputs; with N > 1 "
+                         "ranks, rank 0's shard)")
+    return ap.parse_args(argv)
 
 
 def spawn(args) -> int:
@@ -240,6 +253,69 @@ def leg_counters(args, kernel="qh_k_dec_peek", coalesced=None):
     return out, chain
 
 
+DUMP_ROWS = 1 << 20    # strings whose spans are written (all of config 3's 2^20 per GPU)
+DUMP_SAMPLE = 1 << 20  # bytes sampled from each stream
+DUMP_CHUNK = 4096      # bytes per checksum row (more when a stream would need over 2^16 rows)
+DUMP_SEED = 0x5EED0D
+
+
+def dump_outputs(path, torch, enc, eout, dec, dout):
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    so that two builds can be compared output for output (the batch is the
+    same from run to run: synth is seeded).  For each of the two streams
+    (`enc`: qh_encode_batch's dst / out, `dec`: qh_decode_batch's), with the
+    valid bytes of the strings -- [off, off + len) where status is 0, the
+    slot layout's gaps left out -- taken back to back in string order:
+
+      <s>_spans.npy   float64 [n, 2]  off, len of every string as returned
+      <s>_status.npy  float32 [n]     status of every string
+      <s>_sums.npy    float64 [k, 2]  per run of c bytes of the valid bytes
+                                      (c = 4096, or more to keep k <= 2^16):
+                                      their sum, and their sum weighted by
+                                      1 + (index in the run) % 251 -- exact
+      <s>_sample.npy  float32 [m]     the valid bytes at m <= 2^20 positions
+                                      drawn with a fixed seed, ascending
+
+    Beyond 2^20 strings the spans and status rows are a fixed seeded sample
+    (ascending).  About 52 MB at most in all."""
+    os.makedirs(path, exist_ok=True)
+    dev = enc.device
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+    def stream(name, buf, out, rows=1 << 18):
+        n = out.shape[0]
+        rng = np.random.default_rng(DUMP_SEED)
+        off, ln, st = out[:, 0], out[:, 1] & 0xFFFFFFFF, out[:, 1] >> 32
+        sel = slice(None)
+        if n > DUMP_ROWS:
+            sel = torch.from_numpy(np.sort(rng.integers(0, n, size=DUMP_ROWS))).to(dev)
+        save(name + "_spans", torch.stack([off[sel], ln[sel]], 1).to(torch.float64))
+        save(name + "_status", st[sel].to(torch.float32))
+        ln = torch.where(st == 0, ln, torch.zeros_like(ln))
+        parts = []
+        for i0 in range(0, n, rows):
+            l = ln[i0:i0 + rows]
+            tot = int(l.sum().item())
+            if tot == 0:
+                continue
+            pos = torch.arange(tot, device=dev, dtype=torch.int64) - torch.repeat_interleave(torch.cumsum(l, 0) - l, l)
+            at = torch.repeat_interleave(off[i0:i0 + rows], l) + pos
+            parts.append(buf[at.clamp_(0, buf.numel() - 1)])
+        valid = torch.cat(parts) if parts else buf[:0]
+        m = valid.numel()
+        c = DUMP_CHUNK * max(1, -(-m // (DUMP_CHUNK << 16)))
+        v = torch.cat([valid, valid.new_zeros((-m) % c)]).view(-1, c).to(torch.int64)
+        w = 1 + torch.arange(c, device=dev, dtype=torch.int64) % 251
+        save(name + "_sums", torch.stack([v.sum(1), (v * w).sum(1)], 1).to(torch.float64))
+        at = np.sort(rng.integers(0, m, size=min(m, DUMP_SAMPLE))) if m else np.zeros(0, dtype=np.int64)
+        save(name + "_sample", valid[torch.from_numpy(at).to(dev)].to(torch.float32))
+
+    stream("enc", enc, eout)
+    stream("dec", dec, dout)
+
+
 def _cpu_model():
     try:
         for ln in open("/proc/cpuinfo"):
@@ -338,9 +414,45 @@ def main():
     D.barrier()
     elapsed_max = D.max(time.perf_counter() - t0)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, enc, eout, dec, dout)
+
     if args.profile_only:
         if rank == 0:
             print(json.dumps({"profile_only": True, "ms_per_step": 1e3 * elapsed_max / args.steps}))
+        D.close()
+        return
+
+    total_all = D.sum(float(total))
+    value = total_all * args.steps / elapsed_max / GIB
+    line = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed_max / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (splitmix64, nghttp3_amd/synth.py)",
+        "config": {"workload": "config 3: Huffman encode+decode round trip, 2^20 strings "
+                               f"{args.min_len}-{args.max_len} B per GPU, alphabet {args.alphabet}; one "
+                               "batch of N x 2^20 strings split by bytes over the N GPUs",
+                   "strings_per_gpu": args.strings, "strings_rank0": n, "plain_bytes_rank0": total,
+                   "enc_bytes_rank0": enc_bytes, "plain_bytes_all": int(total_all),
+                   "seed": hex(args.seed), "parallelism": f"shard{world}",
+                   "dist_backend": args.dist_backend if world > 1 else None},
+        "full": args.full,
+    }
+    if not args.full:
+        # the plain run ends here: the bit-exact check and every other leg
+        # are --full's (bit_exact: null = not checked in this run)
+        line.update({"bit_exact": None, "roofline": None, "cpu_baseline": None, "extra": None})
+        if rank == 0:
+            print(json.dumps(line), flush=True)
         D.close()
         return
 
@@ -360,7 +472,6 @@ def main():
     # packing pass), reported beside the slot layout
     t_dense = timed(lambda: codec.decode_dev(enc, eout, dec, dout, dense=True), args.steps)
     dense_ok = D.sum(0.0 if roundtrip_ok(src, spans, dec, dout) else 1.0) == 0
-    total_all = D.sum(float(total))
 
     # ---- two batches in flight (reported beside the value, never as it): a
     # second context on its own HIP stream with its own output buffers, the
@@ -390,7 +501,6 @@ def main():
                    "bit_exact": D.sum(0.0 if ok2 else 1.0) == 0,
                    "how": "two contexts (own stream and buffers each), round trips alternating"}
         del codec2, enc2, eout2, dec2, dout2, pair
-    value = total_all * args.steps / elapsed_max / GIB
 
     def kernel_table(ktimes, n, plain, encb):
         algo = {  # algorithmic HBM bytes per launch
@@ -568,26 +678,7 @@ def main():
         cpu = leg_cpu(args, src, spans, total, n)
 
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed_max / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (splitmix64, nghttp3_amd/synth.py)",
-            "config": {"workload": "config 3: Huffman encode+decode round trip, 2^20 strings "
-                                   f"{args.min_len}-{args.max_len} B per GPU, alphabet {args.alphabet}; one "
-                                   "batch of N x 2^20 strings split by bytes over the N GPUs",
-                       "strings_per_gpu": args.strings, "strings_rank0": n, "plain_bytes_rank0": total,
-                       "enc_bytes_rank0": enc_bytes, "plain_bytes_all": int(total_all),
-                       "seed": hex(args.seed), "parallelism": f"shard{world}",
-                       "dist_backend": args.dist_backend if world > 1 else None},
+        line.update({
             "bit_exact": bad == 0,
             "roofline": roofline,
             "cpu_baseline": cpu,
@@ -604,7 +695,7 @@ def main():
                       "config5_zipf": config5, "config4_qpack_blocks": config4,
                       "config1_qif": config1,
                       "config3_alphabet_U": configU},
-        }
+        })
         print(json.dumps(line), flush=True)
     D.close()
 

@@ -8,7 +8,7 @@ i=0
 for L in "$@"; do
   i=$((i+1))
   EV=""; [ "$L" != base ] && EV="QHUFF_LIB=$(realpath $L)"
-  env $EV timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-host-path --c5-strings 0 --c4-blocks 0 > $O/b$i.json 2> $O/b$i.err || { tail -5 $O/b$i.err; exit 1; }
+  env $EV timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --no-host-path --c5-strings 0 --c4-blocks 0 > $O/b$i.json 2> $O/b$i.err || { tail -5 $O/b$i.err; exit 1; }
   python -c "
 import json;d=json.loads(open('$O/b$i.json').read().strip().splitlines()[-1])
 k=d['extra']['kernels']; r=d['roofline']; e=d['extra']

@@ -7,7 +7,7 @@ i=0
 for L in "$@"; do
   i=$((i+1))
   EV=""; [ "$L" != base ] && EV="QHUFF_LIB=$(realpath $L)"
-  env $EV timeout -k 10 600 python -u bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $O/b$i.log 2>&1 || { tail -5 $O/b$i.log; exit 1; }
+  env $EV timeout -k 10 600 python -u bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/b$i.log 2>&1 || { tail -5 $O/b$i.log; exit 1; }
   grep '"metric"' $O/b$i.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); h=d['extra']['host_path']
 print('$L', d['value'], h['probe']['both_ms'], 'pinned', h['pinned']['ms'], h['pinned']['ms_each'], 'pageable', h['pageable']['ms'], h['pageable']['ms_each'])"

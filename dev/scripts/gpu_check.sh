@@ -14,7 +14,7 @@ if [ "$sel" != "NONE" ]; then
   if [ $rc -ne 0 ]; then echo "pytest rc=$rc"; exit $rc; fi
 fi
 if [ $# -gt 0 ]; then
-  timeout -k 10 400 python -u bench.py "$@" > "$out/bench.log" 2>&1
+  timeout -k 10 400 python -u bench.py --full "$@" > "$out/bench.log" 2>&1
   rc=$?
   echo "bench rc=$rc"
   tail -c 600 "$out/bench.log"

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -v --timeout 240 --timeout-me
 rc=$?; tail -1 $O/pytest_gpu.log; [ $rc -ne 0 ] && { grep -E "FAILED|Error" $O/pytest_gpu.log | head; exit $rc; }
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
 rc=$?; tail -1 $O/smoke.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1
+timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1
 rc=$?; [ $rc -ne 0 ] && { tail -5 $O/bench.log; exit $rc; }
 grep '"metric"' $O/bench.log > $O/bench.json; head -c 600 $O/bench.json; echo
 R=$(pwd)

@@ -21,7 +21,8 @@ Fixtures (all data, no reference source text):
   oracle (pinned by the two fixtures above).
 * corpus.npz   -- ~4k mixed strings (edge lengths, alphabets A / U / digits,
   all 256 byte values) with oracle encodings, plus corrupted encodings with
-  their statuses.  np.savez, no pickled objects.
+  their statuses.  An .npz whose members are LZMA-compressed (np.load reads
+  it like any other; deflate leaves it above 1 MiB), no pickled objects.
 * digests.json -- SHA-256 of the plaintext and of the dense oracle encodings
   of the full-size synthetic configs, for size-independent
   parity on the GPU box.
@@ -29,10 +30,12 @@ Fixtures (all data, no reference source text):
 from __future__ import annotations
 
 import hashlib
+import io
 import json
 import os
 import re
 import sys
+import zipfile
 
 import numpy as np
 
@@ -177,6 +180,15 @@ def corrupt(enc: bytes, kind: int, rng) -> bytes:
     return bytes(b)
 
 
+def savez_lzma(path, **arrays):
+    """np.savez with LZMA-compressed members."""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, a, allow_pickle=False)
+            z.writestr(name + ".npy", buf.getvalue())
+
+
 def gen_corpus(path):
     rng = np.random.default_rng(0x5EED00C0)
     strs = corpus_strings(rng)
@@ -197,10 +209,10 @@ def gen_corpus(path):
     bad_status = np.array([oracle.decode_one(x)[0] for x in bad], dtype=np.int32)
     bad_out = [oracle.decode_one(x)[1] for x in bad]
     bad_out_len = np.array([len(x) for x in bad_out], dtype=np.uint32)
-    np.savez_compressed(path, plain=plain, off=off, len=ln, enc=enc, enc_off=eoff, enc_len=elen,
-                        bad=bad_cat, bad_off=bad_off, bad_len=bad_len, bad_status=bad_status,
-                        bad_out=np.frombuffer(b"".join(bad_out) or b"\0", dtype=np.uint8),
-                        bad_out_len=bad_out_len)
+    savez_lzma(path, plain=plain, off=off, len=ln, enc=enc, enc_off=eoff, enc_len=elen,
+               bad=bad_cat, bad_off=bad_off, bad_len=bad_len, bad_status=bad_status,
+               bad_out=np.frombuffer(b"".join(bad_out) or b"\0", dtype=np.uint8),
+               bad_out_len=bad_out_len)
     print("corpus:", len(strs), "strings,", int((bad_status != 0).sum()), "of 1024 corrupted fail")
 
 
