@@ -221,9 +221,13 @@ QH_EXPORT int qh_ctx_set_encoder(qh_ctx *ctx, int kind);
  * QH_OPT_LENS_LANE_PASS: 1 counts every string's encoded length a lane per
  *   string (the path the length kernel takes for scattered spans) instead
  *   of streaming the strings' region; 0 (default) chooses per window.
+ * QH_OPT_SECTIONS_SLICE_BLOCKS: header blocks per slice of the pipelined
+ *   host-memory qh_decode_sections_batch (QH_SECTIONS_PACKED); 0 (default)
+ *   lets the library choose.  Any value gives the same results.
  * No reference counterpart (the reference codec has no batch kernels). */
 #define QH_OPT_LONG_MIN 1
 #define QH_OPT_LENS_LANE_PASS 2
+#define QH_OPT_SECTIONS_SLICE_BLOCKS 3
 QH_EXPORT int qh_ctx_set_option(qh_ctx *ctx, int option, int64_t value);
 QH_EXPORT void *qh_ctx_stream(qh_ctx *ctx);
 /* Wait for all work queued on the context's stream. */
@@ -442,8 +446,35 @@ QH_EXPORT int qh_scan_blocks_batch(qh_ctx *ctx, const uint8_t *src,
  * QH_ERR_NOMEM (caps or dst_cap too small: nothing was decoded; resize and
  * call again).  opts: QH_SECTIONS_DTABLE0 decodes as a decoder whose
  * dynamic table capacity is 0 (qpack_decode -s 0): any Required Insert
- * Count but 0 fails the block (reconstruct_ricnt, :3915-3950). */
+ * Count but 0 fails the block (reconstruct_ricnt, :3915-3950).
+ *
+ * QH_SECTIONS_PACKED (both `where` values) changes dst's layout and nothing
+ * else: the decoded Huffman strings lie back to back in dst, in
+ * Huffman-string order, strs[k].off of a successful Huffman string being
+ * the sum of the decoded lengths of the successful Huffman strings before
+ * it; a failed Huffman string takes no bytes (status QH_ERR_QPACK_FATAL,
+ * len 0); raw strings still point into src.  lines, spans, line_start,
+ * span_start, status, verdict, token, prefixes, nlines, nspans and nhuff
+ * are byte for byte those of the call without the bit.
+ * dst_cap >= (total block bytes) * 8 / 5 always suffices (every Huffman
+ * string lies inside its block and decodes to at most len * 8 / 5 bytes).
+ * On success dst_need is the exact number of packed bytes written.  If the
+ * packed bytes would pass dst_cap the call returns QH_ERR_NOMEM with
+ * dst_need set to the exact need and nothing written at or past dst_cap;
+ * in that case (QH_SECTIONS_PACKED only) the other outputs are unspecified.
+ * (When lines_cap or spans_cap is too small, QH_ERR_NOMEM comes from the
+ * count as without the bit, nothing else written; dst_need then holds an
+ * upper bound of the packed bytes, the slot layout's total.)
+ * With QH_WHERE_HOST, QH_SECTIONS_PACKED and the caps that always suffice
+ * (lines_cap, spans_cap >= total block bytes + 1, dst_cap >= total block
+ * bytes * 8 / 5, lines / spans / strs given) the call is pipelined over
+ * slices of consecutive blocks (QH_OPT_SECTIONS_SLICE_BLOCKS): a slice's
+ * results go back to host memory while the next slices come in and are
+ * decoded.  Any other host call counts everything first and keeps the
+ * contract above (QH_ERR_NOMEM with the full totals, nothing else written).
+ * Any other bit of opts gives QH_ERR_INVALID_ARGUMENT. */
 #define QH_SECTIONS_DTABLE0 0x1u
+#define QH_SECTIONS_PACKED 0x2u
 
 typedef struct qh_sections {
   qh_field_line *lines;

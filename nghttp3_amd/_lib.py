@@ -34,6 +34,9 @@ QH_ENCODER_AUTO = 3
 QH_ENCODER_REGION = 4
 QH_OPT_LONG_MIN = 1
 QH_OPT_LENS_LANE_PASS = 2
+QH_OPT_SECTIONS_SLICE_BLOCKS = 3
+QH_SECTIONS_DTABLE0 = 0x1
+QH_SECTIONS_PACKED = 0x2
 
 NGHTTP3_QPACK_HUFFMAN_FLAG_ACCEPTED = 0x01
 NGHTTP3_QPACK_HUFFMAN_FLAG_SYM = 0x02

@@ -112,6 +112,17 @@ struct qh_ctx {
   unsigned long long *d_ends = nullptr;  // its device address (mapped), or null
   void *hp_buf = nullptr;
   size_t hp_cap = 0;
+  // host-memory field sections, sliced (qh_sections.inc sections_host_sliced):
+  // blocks per slice (QH_OPT_SECTIONS_SLICE_BLOCKS; 0: chosen by the
+  // library), one event per slice, the slices' output staging (a bump
+  // arena, sized by the most bytes a call has staged) and the packed strings
+  uint64_t sec_slice_blocks = 0;
+  std::vector<hipEvent_t> sp_ev;
+  void *sp_buf = nullptr;
+  size_t sp_cap = 0;
+  uint64_t sp_hint = 0;
+  void *sp_dense = nullptr;
+  size_t sp_dense_cap = 0;
   void *dn_buf = nullptr;  // QH_WHERE_DEVICE_DENSE: scan scratch, carries, the slots
   size_t dn_cap = 0;
   void *pw_buf = nullptr;   // wave-chunk decoder: per-wave string tables
@@ -944,6 +955,11 @@ int decode_dense(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
 // Eight slices of >= 2^17 strings (sixteen measured no faster: the H2D and
 // D2H of consecutive slices take turns rather than overlap,
 // dev/scripts/host_path_trace.py)
+// (The field sections' host pipeline, qh_sections.inc sections_host_sliced,
+// chooses up to QH_SEC_SLICES = 4 slices of at least 4 MiB of header blocks:
+// its slices cost more, a host wait for framing's totals and six copies
+// back each, and 4 measured best on config 4, 2.88 ms against 3.08 for one
+// slice and 2.94 for eight; dev/scripts/sections_host_times.py.)
 #ifndef QH_HP_SLICES
 #define QH_HP_SLICES 8
 #endif
@@ -962,6 +978,55 @@ int decode_dense(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
 constexpr int kHostSlices = QH_HP_SLICES;
 constexpr uint64_t kHostSliceMin = (1u << 20) / QH_HP_SLICES;  // strings
 constexpr int kHostScanThreads = 8;           // host threads over the spans' pre-pass
+
+// The host pipelines' streams, events and pinned words (created once).
+int host_pipe_init(qh_ctx *c) {
+  if (c->s_h2d) return 0;
+  QH_HIP(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
+  QH_HIP(hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
+  QH_HIP(hipStreamCreateWithFlags(&c->s_end, hipStreamNonBlocking));
+  QH_HIP(hipEventCreateWithFlags(&c->hp_end_ev, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
+  QH_HIP(hipEventCreateWithFlags(&c->hp_user_ev, hipEventDisableTiming));
+  QH_HIP(hipHostMalloc((void **)&c->h_ends, 64 * sizeof(unsigned long long)));
+  // (QHUFF_HOST_MAPPED_ENDS, development: the packing kernel stores each
+  // slice's end through the device address of this mapped buffer instead
+  // of a copy command; measured slower, 6.7 against 4.9 ms per 2^20
+  // strings: a kernel that writes host memory ends with a system-scope
+  // release, which writes back L2)
+  if (QH_DEV_KNOBS && getenv("QHUFF_HOST_MAPPED_ENDS") &&
+      hipHostGetDevicePointer((void **)&c->d_ends, c->h_ends, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_ends = nullptr;
+  }
+  c->hp_ev.resize(2 * kHostSlices, nullptr);
+  // (blocking-sync events: the returner thread sleeps in its waits instead
+  // of spinning a CPU of the process's quota)
+  for (auto &e : c->hp_ev)
+    QH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
+  return 0;
+}
+
+// The pipeline's H2D, decodes and packing run on the context's own s_h2d
+// (after the work queued on the caller's stream), not on the caller's
+// stream: its three streams, created together, then sit on three
+// different hardware queues, whereas the caller's stream may share one
+// with s_d2h.  Measured: with one more stream created in the process
+// before the context's, the caller's (null) stream and s_d2h shared a
+// queue and the pinned decode took 6.5-7.0 ms instead of 4.4
+// (DESIGN.md section 7).  A caller's stream restricted to some CUs
+// keeps the work (the pipeline then stays on it).
+struct OnOwnStream {
+  qh_ctx *c;
+  hipStream_t user;
+  bool on;
+  ~OnOwnStream() {
+    if (!on) return;
+    c->stream = user;  // (and the caller's stream waits for the pipeline)
+    if (hipEventRecord(c->hp_user_ev, c->s_h2d) != hipSuccess ||
+        hipStreamWaitEvent(user, c->hp_user_ev, 0) != hipSuccess)
+      (void)hipGetLastError();
+  }
+};
 
 int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64_t n, uint8_t *dst,
                      uint64_t dst_cap, qh_span_out *out);
@@ -982,50 +1047,8 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
                      uint64_t dst_cap, qh_span_out *out) {
   int rv = reset_stats(c, n);
   if (rv || n == 0) return rv;
-  if (!c->s_h2d) {
-    QH_HIP(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
-    QH_HIP(hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
-    QH_HIP(hipStreamCreateWithFlags(&c->s_end, hipStreamNonBlocking));
-    QH_HIP(hipEventCreateWithFlags(&c->hp_end_ev, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
-    QH_HIP(hipEventCreateWithFlags(&c->hp_user_ev, hipEventDisableTiming));
-    QH_HIP(hipHostMalloc((void **)&c->h_ends, 64 * sizeof(unsigned long long)));
-    // (QHUFF_HOST_MAPPED_ENDS, development: the packing kernel stores each
-    // slice's end through the device address of this mapped buffer instead
-    // of a copy command; measured slower, 6.7 against 4.9 ms per 2^20
-    // strings: a kernel that writes host memory ends with a system-scope
-    // release, which writes back L2)
-    if (QH_DEV_KNOBS && getenv("QHUFF_HOST_MAPPED_ENDS") &&
-        hipHostGetDevicePointer((void **)&c->d_ends, c->h_ends, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      c->d_ends = nullptr;
-    }
-    c->hp_ev.resize(2 * kHostSlices, nullptr);
-    // (blocking-sync events: the returner thread sleeps in its waits instead
-    // of spinning a CPU of the process's quota)
-    for (auto &e : c->hp_ev)
-      QH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
-  }
-  // The pipeline's H2D, decodes and packing run on the context's own s_h2d
-  // (after the work queued on the caller's stream), not on the caller's
-  // stream: its three streams, created together, then sit on three
-  // different hardware queues, whereas the caller's stream may share one
-  // with s_d2h.  Measured: with one more stream created in the process
-  // before the context's, the caller's (null) stream and s_d2h shared a
-  // queue and the pinned decode took 6.5-7.0 ms instead of 4.4
-  // (DESIGN.md section 7).  A caller's stream restricted to some CUs
-  // keeps the work (the pipeline then stays on it).
-  struct OnOwnStream {
-    qh_ctx *c;
-    hipStream_t user;
-    bool on;
-    ~OnOwnStream() {
-      if (!on) return;
-      c->stream = user;  // (and the caller's stream waits for the pipeline)
-      if (hipEventRecord(c->hp_user_ev, c->s_h2d) != hipSuccess ||
-          hipStreamWaitEvent(user, c->hp_user_ev, 0) != hipSuccess)
-        (void)hipGetLastError();
-    }
-  } own{c, c->stream, QH_HP_OWN_STREAM && c->all_cus};
+  if ((rv = host_pipe_init(c))) return rv;
+  OnOwnStream own{c, c->stream, QH_HP_OWN_STREAM && c->all_cus};
   if (own.on) {
     QH_HIP(hipEventRecord(c->hp_user_ev, own.user));
     QH_HIP(hipStreamWaitEvent(c->s_h2d, c->hp_user_ev, 0));
@@ -1463,6 +1486,9 @@ QH_EXPORT void qh_ctx_del(qh_ctx *c) {
   if (c->pw_buf) hipFree(c->pw_buf);
   if (c->hp_buf) hipFree(c->hp_buf);
   for (auto e : c->hp_ev) hipEventDestroy(e);
+  for (auto e : c->sp_ev) hipEventDestroy(e);
+  if (c->sp_buf) hipFree(c->sp_buf);
+  if (c->sp_dense) hipFree(c->sp_dense);
   if (c->h_ends) hipHostFree(c->h_ends);
   if (c->s_h2d) hipStreamDestroy(c->s_h2d);
   if (c->s_d2h) hipStreamDestroy(c->s_d2h);
@@ -1528,6 +1554,10 @@ QH_EXPORT int qh_ctx_set_option(qh_ctx *c, int option, int64_t value) {
     case QH_OPT_LENS_LANE_PASS:
       if (value != 0 && value != 1) return QH_ERR_INVALID_ARGUMENT;
       c->lens_lane = value != 0;
+      return 0;
+    case QH_OPT_SECTIONS_SLICE_BLOCKS:
+      if (value < 0) return QH_ERR_INVALID_ARGUMENT;
+      c->sec_slice_blocks = (uint64_t)value;
       return 0;
     default:
       return QH_ERR_INVALID_ARGUMENT;

@@ -223,6 +223,9 @@ __global__ void __launch_bounds__(64) qh_k_frame_count(const uint8_t *__restrict
       } else {  // (a block the fast parse does not answer for, or one not staged)
         scan_out o;
         frame_init(o, opts);
+        // (the fast parse fills the prefix in before it gives up: a block
+        // whose prefix is not valid reports zero, staged or not)
+        pf = qh_section_prefix{0, 0, 0, 0};
         o.lstarts = ls;
         o.lstarts_cap = ls ? kFrLines : 0;
         // (two call sites: in the first the parser's byte reads provably come

@@ -49,15 +49,17 @@ __global__ void __launch_bounds__(256) qh_k_dense_sums(const SpanOut *__restrict
   if (threadIdx.x == 0) btot[blockIdx.x] = red4[0] + red4[1] + red4[2] + red4[3];
 }
 
-// One tile (64 strings from i0) of a wave, its packed bytes starting at base.
-__device__ __forceinline__ void dense_tile(
-    uint64_t i0, uint64_t base, SpanOut o, uint32_t lane, uint32_t wid,
-    const uint8_t *__restrict__ slots, SpanOut *__restrict__ out, uint64_t n,
+// The copy of one tile (64 strings from i0) of a wave, its packed bytes
+// starting at base: lane t's string (ok: it has bytes to pack, o.len of them
+// at slots + o.off) goes to dense + d when it fits under dense_cap.
+__device__ __forceinline__ void dense_tile_copy(
+    uint64_t i0, uint64_t base, SpanOut o, bool ok, uint32_t lane, uint32_t wid,
+    const uint8_t *__restrict__ slots, uint64_t n,
     uint8_t *__restrict__ dense, uint64_t dense_cap, unsigned long long *__restrict__ carry_out,
     unsigned long long *__restrict__ host_end, uint32_t (&pre)[kDnWaves][64],
-    uint64_t (&soff)[kDnWaves][64], uint64_t (&doff)[kDnWaves][64], uint32_t (&slen)[kDnWaves][64]) {
+    uint64_t (&soff)[kDnWaves][64], uint64_t (&doff)[kDnWaves][64], uint32_t (&slen)[kDnWaves][64],
+    uint64_t &d_out, bool &fits_out) {
   const uint64_t i = i0 + lane;
-  const bool ok = i < n && o.status == 0;
   const unsigned long long L = ok ? o.len : 0u;
   const unsigned long long incl = wave_scan_add_u64(L);  // (DPP: the wave is whole)
   const uint64_t d = base + incl - L;
@@ -123,6 +125,23 @@ __device__ __forceinline__ void dense_tile(
     }
     __builtin_amdgcn_wave_barrier();  // (the next tile rewrites this wave's LDS rows)
   }
+  d_out = d;
+  fits_out = fits;
+}
+
+// One tile (64 strings from i0) of a wave, its packed bytes starting at base.
+__device__ __forceinline__ void dense_tile(
+    uint64_t i0, uint64_t base, SpanOut o, uint32_t lane, uint32_t wid,
+    const uint8_t *__restrict__ slots, SpanOut *__restrict__ out, uint64_t n,
+    uint8_t *__restrict__ dense, uint64_t dense_cap, unsigned long long *__restrict__ carry_out,
+    unsigned long long *__restrict__ host_end, uint32_t (&pre)[kDnWaves][64],
+    uint64_t (&soff)[kDnWaves][64], uint64_t (&doff)[kDnWaves][64], uint32_t (&slen)[kDnWaves][64]) {
+  const uint64_t i = i0 + lane;
+  const bool ok = i < n && o.status == 0;
+  uint64_t d;
+  bool fits;
+  dense_tile_copy(i0, base, o, ok, lane, wid, slots, n, dense, dense_cap, carry_out, host_end, pre,
+                  soff, doff, slen, d, fits);
   if (i < n) {
     if (ok && !fits) {
       o.status = QH_ERR_NOMEM;

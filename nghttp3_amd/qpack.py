@@ -356,6 +356,15 @@ def lookup_tokens_dev(codec: HuffmanBatchCodec, src, spans, token):
                "qh_lookup_tokens_batch")
 
 
+def _huffman_flags(spans):
+    """bool per span: its QH_SPAN_HUFFMAN flag (one pass over the flags' low
+    bytes; the two-pass `(flags & 1) != 0` is a visible part of a
+    host-memory decode of millions of spans)."""
+    assert SPAN_HUFFMAN == 1 and spans.dtype == SPAN_IN_DTYPE and spans.flags.c_contiguous
+    low = spans.view(np.uint8).reshape(-1, SPAN_IN_DTYPE.itemsize)[:, SPAN_IN_DTYPE.fields["flags"][1]]
+    return (low & np.uint8(1)).view(np.bool_)
+
+
 class FieldSectionDecoder:
     """Whole header blocks -> every string of every block, decoded, checked
     and (names) tokenised, through one qh_decode_sections_batch call: GPU
@@ -371,13 +380,17 @@ class FieldSectionDecoder:
                  dtable0: bool = False):
         self.codec = codec or HuffmanBatchCodec(device)
         self.opts = SECTIONS_DTABLE0 if dtable0 else 0
+        self._spare = None  # the last decode_blocks result's arrays (_host_bufs)
 
-    def decode_blocks_dev(self, src, blocks, bufs=None):
+    def decode_blocks_dev(self, src, blocks, bufs=None, packed=False):
         """src uint8 and blocks int64 [n,2] (SPAN_IN layout) torch tensors in
         HBM.  Returns a dict of torch tensors (lines, spans, strs, verdict,
         tokens, line_start, span_start, status, dst) plus the totals
         (nlines, nspans, nhuff, dst_need); `bufs` (a previous result)
-        reuses its allocations.  Asynchronous after the framing sync."""
+        reuses its allocations.  Asynchronous after the framing sync.
+        ``packed`` (QH_SECTIONS_PACKED): the decoded Huffman strings back to
+        back in dst (dst_need: their bytes) instead of the slot layout; the
+        call then also waits for the decode."""
         import torch
         dev = src.device
         n = blocks.shape[0]
@@ -394,6 +407,9 @@ class FieldSectionDecoder:
                  "span_start": torch.empty(n + 1, dtype=torch.int32, device=dev),
                  "status": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
                  "dst": torch.empty(64, dtype=torch.uint8, device=dev)}
+        opts = self.opts | (_lib.QH_SECTIONS_PACKED if packed else 0)
+        if packed and b["dst"].numel() < cap * 8 // 5:  # (the bound that always suffices)
+            b["dst"] = torch.empty(cap * 8 // 5, dtype=torch.uint8, device=dev)
         lib = _load()
         p = lambda t: t.data_ptr()
         for _ in range(2):  # a second try only when dst was too small
@@ -401,7 +417,7 @@ class FieldSectionDecoder:
                              p(b["tokens"]), p(b["line_start"]), p(b["span_start"]), p(b["status"]),
                              None, p(b["dst"]), b["dst"].numel(), 0, 0, 0, 0)
             rv = lib.qh_decode_sections_batch(self.codec._ctx, ctypes.c_void_p(src.data_ptr()),
-                                              ctypes.c_void_p(blocks.data_ptr()), n, self.opts,
+                                              ctypes.c_void_p(blocks.data_ptr()), n, opts,
                                               ctypes.byref(st), _lib.QH_WHERE_DEVICE)
             if rv == _lib.QH_ERR_NOMEM and st.dst_need > b["dst"].numel():
                 b["dst"] = torch.empty(int(st.dst_need), dtype=torch.uint8, device=dev)
@@ -412,46 +428,112 @@ class FieldSectionDecoder:
                   "dst_need": st.dst_need})
         return b
 
-    def decode_blocks(self, src, blocks):
+    _HOST_ARRAYS = (("lines", FIELD_LINE_DTYPE), ("spans", SPAN_IN_DTYPE), ("strs", SPAN_OUT_DTYPE),
+                    ("verdict", np.int8), ("tokens", np.int32))
+
+    @staticmethod
+    def _host_empty(raw, key, count, dtype, pinned):
+        """raw["arrays"][key] = an uninitialised array; raw["roots"][key] the
+        object that owns its memory (every view handed out refers to it)."""
+        dtype = np.dtype(dtype)
+        if pinned:
+            import torch
+            t = torch.empty(max(count * dtype.itemsize, 1), dtype=torch.uint8, pin_memory=True)
+            root = t.numpy()
+            arr = root[:count * dtype.itemsize].view(dtype)
+        else:
+            root = arr = np.empty(count, dtype=dtype)
+        raw["arrays"][key] = arr
+        raw["roots"][key] = root
+        del root, arr
+        raw["refs0"] = FieldSectionDecoder._refs(raw)
+
+    @staticmethod
+    def _refs(raw):
+        import sys
+        return [sys.getrefcount(raw["roots"][k]) for k in sorted(raw["roots"])]
+
+    @staticmethod
+    def _released(raw):
+        """Whether nothing but `raw` itself refers to its arrays any more (a
+        result hands out views of them, and each view holds its root)."""
+        return FieldSectionDecoder._refs(raw) == raw["refs0"]
+
+    def _host_bufs(self, bufs, cap, n, dst_size, pinned):
+        """The output arrays of decode_blocks: those of `bufs` (a previous
+        result) when large enough, else the last call's when its result has
+        been dropped, else new ones (uninitialised: a result only ever shows
+        what the call wrote)."""
+        raw = bufs.get("_raw") if bufs else None
+        if raw is None and self._spare is not None and self._released(self._spare):
+            raw = self._spare
+        if raw is None or raw["pinned"] != pinned or raw["cap"] < cap or raw["n"] < n:
+            raw = {"arrays": {}, "roots": {}, "cap": cap, "n": n, "pinned": pinned}
+            for k, dt in self._HOST_ARRAYS:
+                self._host_empty(raw, k, cap, dt, pinned)
+            self._host_empty(raw, "line_start", n + 1, np.uint32, pinned)
+            self._host_empty(raw, "span_start", n + 1, np.uint32, pinned)
+            self._host_empty(raw, "status", max(n, 1), np.int32, pinned)
+            self._host_empty(raw, "prefixes", max(n, 1), PREFIX_DTYPE, pinned)
+            self._host_empty(raw, "dst", dst_size, np.uint8, pinned)
+        if raw["arrays"]["dst"].size < dst_size:
+            self._host_empty(raw, "dst", dst_size, np.uint8, pinned)
+        return raw
+
+    def decode_blocks(self, src, blocks, packed=False, bufs=None, pinned=False):
         """Host arrays in and out: -> dict with lines, spans, strs
         (SPAN_OUT_DTYPE: Huffman strings in dst, raw strings in src),
         huffman (bool per span), verdict, tokens, line_start, span_start,
-        status, dst."""
+        status, dst (its first dst_need bytes).
+        ``packed`` (QH_SECTIONS_PACKED): the decoded Huffman strings back to
+        back in dst; dst is sized by the bound that always suffices, so the
+        library pipelines the call over slices of blocks.  ``bufs`` (a
+        previous result) has its arrays written again when they are large
+        enough; ``pinned`` allocates the arrays in page-locked memory.  The
+        arrays are allocated uninitialised, and those of the last result
+        are taken again once that result has been dropped."""
         lib = _load()
         src = _u8(src)
         if src.size == 0:
             src = np.zeros(1, dtype=np.uint8)
         blocks = np.ascontiguousarray(blocks, dtype=SPAN_IN_DTYPE)
         n = blocks.size
-        cap = int(blocks["len"].sum(dtype=np.uint64)) + 1
-        lines = np.zeros(cap, dtype=FIELD_LINE_DTYPE)
-        spans = np.zeros(cap, dtype=SPAN_IN_DTYPE)
-        strs = np.zeros(cap, dtype=SPAN_OUT_DTYPE)
-        verdict = np.zeros(cap, dtype=np.int8)
-        tokens = np.zeros(cap, dtype=np.int32)
-        ls = np.zeros(n + 1, dtype=np.uint32)
-        ss = np.zeros(n + 1, dtype=np.uint32)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        prefixes = np.zeros(max(n, 1), dtype=PREFIX_DTYPE)
-        dst = np.zeros(64, dtype=np.uint8)
+        nbytes = int(blocks["len"].sum(dtype=np.uint64))
+        cap = nbytes + 1
+        # slots: a first guess (about twice the decoded bytes for header
+        # text), grown to dst_need when short
+        dst_size = max(nbytes * 8 // 5, 64) if packed else 3 * nbytes + 64
+        raw = self._host_bufs(bufs, cap, n, dst_size, pinned)
+        self._spare = None
+        a = raw["arrays"]
+        opts = self.opts | (_lib.QH_SECTIONS_PACKED if packed else 0)
         for _ in range(2):
-            st = qh_sections(lines.ctypes.data, cap, spans.ctypes.data, cap, strs.ctypes.data,
-                             verdict.ctypes.data, tokens.ctypes.data, ls.ctypes.data, ss.ctypes.data,
-                             status.ctypes.data, prefixes.ctypes.data, dst.ctypes.data, dst.size,
-                             0, 0, 0, 0)
-            rv = lib.qh_decode_sections_batch(self.codec._ctx, _vp(src), _vp(blocks), n, self.opts,
+            dst = a["dst"]
+            st = qh_sections(a["lines"].ctypes.data, raw["cap"], a["spans"].ctypes.data, raw["cap"],
+                             a["strs"].ctypes.data, a["verdict"].ctypes.data, a["tokens"].ctypes.data,
+                             a["line_start"].ctypes.data, a["span_start"].ctypes.data,
+                             a["status"].ctypes.data, a["prefixes"].ctypes.data, dst.ctypes.data,
+                             dst.size, 0, 0, 0, 0)
+            rv = lib.qh_decode_sections_batch(self.codec._ctx, _vp(src), _vp(blocks), n, opts,
                                               ctypes.byref(st), _lib.QH_WHERE_HOST)
             if rv == _lib.QH_ERR_NOMEM and st.dst_need > dst.size:
-                dst = np.zeros(int(st.dst_need), dtype=np.uint8)
+                del dst
+                self._host_empty(raw, "dst", int(st.dst_need), np.uint8, pinned)
                 continue
             _lib.check(rv, "qh_decode_sections_batch")
             break
         ns = int(st.nspans)
-        spans = spans[:ns]
-        return {"lines": lines[:st.nlines], "spans": spans, "strs": strs[:ns],
-                "huffman": (spans["flags"] & SPAN_HUFFMAN) != 0, "verdict": verdict[:ns],
-                "tokens": tokens[:ns], "line_start": ls, "span_start": ss, "status": status[:n],
-                "prefixes": prefixes[:n], "dst": dst}
+        spans = a["spans"][:ns]
+        res = {"lines": a["lines"][:st.nlines], "spans": spans, "strs": a["strs"][:ns],
+               "huffman": _huffman_flags(spans), "verdict": a["verdict"][:ns],
+               "tokens": a["tokens"][:ns], "line_start": a["line_start"][:n + 1],
+               "span_start": a["span_start"][:n + 1], "status": a["status"][:n],
+               "prefixes": a["prefixes"][:n], "dst": dst[:int(st.dst_need)],
+               "nlines": int(st.nlines), "nspans": ns, "nhuff": int(st.nhuff),
+               "dst_need": int(st.dst_need), "_raw": raw}
+        del dst, spans
+        self._spare = raw
+        return res
 
 
 def static_entry(idx: int):

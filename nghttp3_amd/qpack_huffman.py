@@ -188,8 +188,11 @@ class HuffmanBatchCodec:
         """Tuning options (include/qhuff.h QH_OPT_*; results are identical):
         'long_min' (the sorted decoder's workgroup-per-string threshold, in
         encoded bytes; 0 = off) and 'lens_lane_pass' (1: every string's
-        encoded length counted a lane per string)."""
-        k = {"long_min": _lib.QH_OPT_LONG_MIN, "lens_lane_pass": _lib.QH_OPT_LENS_LANE_PASS}[option]
+        encoded length counted a lane per string) and 'sections_slice_blocks'
+        (header blocks per slice of the pipelined host-memory field-section
+        decode; 0 = chosen by the library)."""
+        k = {"long_min": _lib.QH_OPT_LONG_MIN, "lens_lane_pass": _lib.QH_OPT_LENS_LANE_PASS,
+             "sections_slice_blocks": _lib.QH_OPT_SECTIONS_SLICE_BLOCKS}[option]
         _lib.check(self._lib.qh_ctx_set_option(self._ctx, k, int(value)), "qh_ctx_set_option")
 
     def sync(self):
