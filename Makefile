@@ -24,7 +24,7 @@ $(LIBDIR)/qh_scalar.o: $(CSRC)/qh_scalar.c $(CSRC)/qh_tables.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
+$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_scratch.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -63,13 +63,14 @@ $(STAMPS): $(CSRC)/qh_device.hip $(CSRC)/*.inc dev/csrc/*.inc $(CSRC)/qh_common.
 	$(HIPCC) $(HIPFLAGS) -DQH_STAMPS -DQH_STEP_COUNTS=1 -c $< -o $(LIBDIR)/qh_device_stamps.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/qh_device_stamps.o $(LIBDIR)/qh_scalar.o $(LIBDIR)/qh_qpack.o $(LIBDIR)/qh_http.o $(LIBDIR)/qh_static.o
 
-# Development build with every kernel variant, after
-#   git apply dev/patches/dev_variants_api.patch
-# (the variants' host side, kept out of the product API; -DQH_DEV_VARIANTS: decoders
-# fsm / fsm2 / lut / run / other peek widths and queue shapes, the
-# chunk-engine and streaming encoders), selected by QHUFF_DECODER /
-# QHUFF_ENCODER / QHUFF_CODES; loaded only when QHUFF_LIB points at it
-# (dev/scripts/dec_variants.py).
+# Development build (-DQH_DEV_VARIANTS): the product plus the pair decoder
+# (dev/csrc/qh_pair_dec.inc: QHUFF_DECODER=pair13...), the segment encoder
+# (dev/csrc/qh_enc_seg.inc: QHUFF_SEG=1) and any kPeekVariants entry by name
+# (QHUFF_DECODER); loaded only when QHUFF_LIB points at it
+# (dev/scripts/dec_variants.py).  The older variants (fsm / fsm2 / lut / run
+# / queue decoders, the chunk-engine and streaming encoders, the zero-copy
+# host path) and their host side are in the history at 30ebdce; two of their
+# kernels (qh_k_enc_lens, qh_k_copy16) still compile here, launched by nothing.
 DEV := $(LIBDIR)/libqhuff_dev.so
 dev: $(DEV)
 $(DEV): $(CSRC)/qh_device.hip $(CSRC)/*.inc dev/csrc/*.inc $(CSRC)/qh_common.h $(LIBDIR)/qh_scalar.o $(LIBDIR)/qh_qpack.o $(LIBDIR)/qh_http.o $(LIBDIR)/qh_static.o

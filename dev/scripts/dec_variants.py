@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Time every decoder variant (QHUFF_DECODER) on a BASELINE-shaped batch and
+"""Time decoder variants (QHUFF_DECODER) on a BASELINE-shaped batch and
 check each against the plaintext (development tool, one GPU).  Loads the
-development build (make dev -> nghttp3_amd/lib/libqhuff_dev.so), which holds
-every variant; the product library ships peek11s and wring11x16r2 only.
+development build (make dev -> nghttp3_amd/lib/libqhuff_dev.so): every
+kPeekVariants entry by name, the shipped three (peek11s, wring11x16r2,
+sorted11), the measurement entries and the pair decoder (pair13...).  The
+older variants (fsm, fsm2, lut, run, queue) are in the history at 30ebdce.
 
 Usage: python scripts/dec_variants.py [--n N] [--alphabet A|U] [--reps R]
-         [--kinds fsm,peek11,...]
+         [--kinds peek11s,pair13w16s2,...]
 Prints one JSON line per variant: kernel avg us (HIP events), plaintext
 GiB/s of the kernel alone, bit_exact.
 """

@@ -7,16 +7,49 @@ using namespace qhk;
 // host side: context, scratch, timing
 // ---------------------------------------------------------------------------
 
+// The context's buffers (qh_scratch.h), by name: qh_ctx_del walks the array.
+enum BufId {
+  kBufSym,     // encode table, 257*2 words
+  kBufDtab,    // DecTables: symbol-level decode tables
+  kBufStats,   // two DevStats (qh_ctx::d_stats)
+  kBufPeek0,   // peek tables, W = 8 .. 12
+  kBufPtab0 = kBufPeek0 + 5,  // (development) pair tables (dev/csrc/qh_pair_dec.inc), W = 12 .. 14
+  kBufEhint = kBufPtab0 + 3,  // QH_ENCODER_AUTO's hint, two halves
+  kBufBtot,       // the encoder's block totals, two halves of btot_cap(c) words
+  kBufTileState,  // scan tile states (+1 word for the tile counter)
+  kBufBlk,        // one total per block (and per window of the length pass)
+  kBufSched,      // sorted decoder (qh_sched.inc): block histograms + class pairs
+  kBufSrec,       // ... its records
+  kBufFrame,      // framing counts and line starts
+  kBufFrameLb,    // framing look-back regions, two halves used by alternate calls
+  kBufSec,        // sections pipeline (SecLayout)
+  kBufLongList,   // the window decoder's plan and the fused check's long strings
+  kBufHostPipe,   // host-memory decode pipeline (decode_host)
+  kBufSlice,      // host-memory field sections, sliced: the slices' output staging
+  kBufSliceDense,  // ... the packed strings
+  kBufDense,      // QH_WHERE_DEVICE_DENSE: scan scratch, carries, the slots
+  kBufWaves,      // wave-chunk decoder: per-wave string tables
+  kBufEncSec,       // qh_encode_sections_batch: per-string scratch
+  kBufEncSecCodes,  // ... the picked Huffman strings
+  kBufEncSecLoff,   // ... per-line offsets
+  kBufEw,         // fused encoder: window records and ticket counters, two halves
+  kBufStage0,     // host-mode staging: src, spans in, dst, spans out
+  kBufPinned0 = kBufStage0 + 4,  // from here on: pinned host memory
+  kBufEhintHost = kBufPinned0,  // the hint's host copy
+  kBufFrameHost,   // framing's totals read back (8 words)
+  kBufEnds,        // host pipelines: a slice's dense end (64 words)
+  kBufEncSecHost,  // the sections encoder's totals read back (8 words)
+  kNumBuf
+};
+
 struct qh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  uint32_t *d_fsm = nullptr;  // 257*16 words
-  uint32_t *d_sym = nullptr;  // 257*2 words
-  uint8_t *d_pair = nullptr;  // code bits of byte pairs, then of bytes (kPairBytes)
-  int lens_pair = -1;         // length pass: pair table (1) or byte table (0); -1 unset
-  int lens_grid_p = 0;        // resident blocks of the pair-table length pass
-  DecTables *d_dtab = nullptr;  // symbol-level decode tables (qh_lut_dec.inc)
+  qhs::Scratch buf[kNumBuf];
+  // events and streams the context created (destroyed by qh_ctx_del)
+  std::vector<hipEvent_t> owned_ev;
+  std::vector<hipStream_t> owned_streams;
   // Kernel option bits.  The product build sets only bit 4 (every window's
   // lengths to the lane pass, QH_OPT_LENS_LANE_PASS; the same results).
   // Development builds (QH_DEV_KNOBS, qh_common.h) also read QHUFF_DEBUG,
@@ -27,61 +60,31 @@ struct qh_ctx {
   uint32_t dbg = 0;
   bool lens_lane = false;  // QH_OPT_LENS_LANE_PASS
   int bpc = 0;          // QHUFF_BPC (development): blocks per CU override
-  int enc_kind = 0;  // QHUFF_ENCODER=chunks: the chunk-engine length kernel
   int codes_kind = 4;  // 0: qh_k_enc_lanes (QH_ENCODER_WINDOWS); 2: qh_k_enc_waves
-                       // (QH_ENCODER_WAVES); 3: qh_k_encf (QH_ENCODER_FUSED);
-                       // 4: QH_ENCODER_AUTO; 5: qh_k_enc_region (QH_ENCODER_REGION);
-                       // 1: qh_k_enc_stream (development)
+                       // (QH_ENCODER_WAVES); 3: qh_k_encw (QH_ENCODER_FUSED);
+                       // 4: QH_ENCODER_AUTO; 5: qh_k_enc_region (QH_ENCODER_REGION)
   int rg_grid = 0;     // qh_k_enc_region: resident workgroups
-  int dec_kind = 0;  // kDecPeek0 windows (default), kDecWaves; dev: 0 fsm, 1 lut, 2 fsm2, kDecQ
-  uint32_t *d_peek[5] = {};  // peek tables, W = 8 .. 12
-  uint32_t *d_peekq = nullptr;  // zero-escape peek table, W = 11 (qh_dec_q.inc)
-  uint32_t *d_ptab[3] = {};  // (development) pair tables (dev/csrc/qh_pair_dec.inc), W = 12 .. 14
-  uint8_t *d_junk = nullptr;    // (development decoders' idle store target)
-  void *q_wbase = nullptr;      // qh_k_dec_q: per-wave slot totals / bases
-  size_t q_wbase_cap = 0;
-  int q_grid = 0;               // qh_k_dec_q: resident blocks
-  int q_kind = 0;               // qh_k_dec_q variant (kQVariants)
-  uint32_t *d_perm = nullptr;  // qh_k_dec_plan: task order
+  int dec_kind = 0;  // index into kPeekVariants: kDecWindows (default), kDecWaves, kDecSorted
   // QH_ENCODER_AUTO's hint: per workgroup of the last encode, its strings'
   // sums (two device buffers, one pinned copy, its stream and events)
-  unsigned long long *d_ehint = nullptr, *h_ehint = nullptr;
   hipStream_t s_ehint = nullptr;
   hipEvent_t ehint_src = nullptr, ehint_done = nullptr;
   int ehint_par = 0, ehint_grid = 0;
   bool ehint_pending = false, ehint_fused = false;
-  size_t perm_cap = 0;
-  int run_grid = 0;  // qh_k_dec_run: resident blocks (occupancy x CUs)
-  DevStats *d_stats = nullptr;  // the current op's: one of d_stats2[0..1]
+  DevStats *d_stats = nullptr;  // the current op's: one of kBufStats's two
   // Stats and the encoder's block totals are double-buffered: an op's first
   // kernel zeroes the buffer the next op will use (the previous op's, done),
   // so no memset command precedes the op's kernels (*_clean: that buffer is
   // zero).
-  DevStats *d_stats2 = nullptr;
   int stats_par = 0;
   bool stats_clean = false;
-  uint64_t *d_btot2 = nullptr;  // 2 x btot_cap
-  size_t btot_cap = 0;
   int btot_par = 0;
   bool btot_clean = false;
-  uint64_t *d_tile_state = nullptr;
-  size_t tile_state_cap = 0;  // entries (+1 word for the tile counter)
-  uint64_t *d_blk = nullptr;  // chunk engine: one total per block
-  size_t blk_cap = 0;
-  // sorted decoder (qh_sched.inc): block histograms + class pairs, records
-  void *d_sched = nullptr;
-  void *d_srec = nullptr;
-  size_t srec_cap = 0;
   int sorted_grid = 0;
   // sorted decoder: strings of at least long_min encoded bytes (their length
   // class and longer) are decoded a wave per string; QHUFF_LONG_MIN
   // (development) moves the threshold, 0 turns the path off
   uint32_t long_min = 4096;
-  uint32_t *d_wcount = nullptr;  // pairs used alternately: lens list, lens queue, codes list
-  EncWin *d_cwl = nullptr;       // windows left to qh_k_enc_lanes
-  size_t cwl_cap = 0;
-  int cpar = 0;
-  int wpar = 0;
   int lens_grid = 0;  // qh_k_enc_lens_stream: resident blocks
   int enc_bpc = 0, enc_bpc_w = 0;    // qh_k_enc_lanes: resident blocks per CU
   int enc_nt = 0;  // qh_k_enc_lanes: threads per workgroup (QH_ENC_THREADS; QHUFF_ENC_THREADS)
@@ -90,56 +93,26 @@ struct qh_ctx {
   // the stream reaches every CU (no CU mask): the fused encoder's per-XCD
   // ticket heads need a wave on every XCD (qh_enc_fused.inc)
   bool all_cus = true;
-  // framing counts / sections scratch (grown on demand, kept between calls)
-  void *fr_buf = nullptr;
-  size_t fr_cap = 0;
-  uint64_t *fr_lb = nullptr;  // framing look-back regions (two, used by alternate calls)
-  uint64_t fr_lb_words = 0;
-  int fr_par = 0;
-  void *sec_buf = nullptr;
-  size_t sec_cap = 0;
+  int fr_par = 0;  // framing look-back regions: the half this call uses
   uint64_t sec_hint = 0;  // the most spans a sections call has framed (its scratch layout)
-  uint64_t *fr_h = nullptr;  // pinned: the framing totals read back
-  hipEvent_t fr_ev = nullptr;  // recorded after that copy
-  void *ll_buf = nullptr;  // the fused-check decoder's list of long strings (qh_k_dec_long_list)
-  size_t ll_cap = 0;
+  hipEvent_t fr_ev = nullptr;  // recorded after the copy into kBufFrameHost
   // host-memory decode pipeline (decode_host)
   hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_end = nullptr;  // (s_end: the slices' ends read back)
   hipEvent_t hp_end_ev = nullptr;
   hipEvent_t hp_user_ev = nullptr;  // (the host path's hand-offs with the caller's stream)
   std::vector<hipEvent_t> hp_ev;
-  unsigned long long *h_ends = nullptr;  // pinned: each slice's dense end
-  unsigned long long *d_ends = nullptr;  // its device address (mapped), or null
-  void *hp_buf = nullptr;
-  size_t hp_cap = 0;
+  unsigned long long *d_ends = nullptr;  // kBufEnds's device address (mapped), or null
   // host-memory field sections, sliced (qh_sections.inc sections_host_sliced):
   // blocks per slice (QH_OPT_SECTIONS_SLICE_BLOCKS; 0: chosen by the
-  // library), one event per slice, the slices' output staging (a bump
-  // arena, sized by the most bytes a call has staged) and the packed strings
+  // library), one event per slice, and the most bytes a call has staged
+  // (kBufSlice is a bump arena of that size)
   uint64_t sec_slice_blocks = 0;
   std::vector<hipEvent_t> sp_ev;
-  void *sp_buf = nullptr;
-  size_t sp_cap = 0;
   uint64_t sp_hint = 0;
-  void *sp_dense = nullptr;
-  size_t sp_dense_cap = 0;
-  void *dn_buf = nullptr;  // QH_WHERE_DEVICE_DENSE: scan scratch, carries, the slots
-  size_t dn_cap = 0;
-  void *pw_buf = nullptr;   // wave-chunk decoder: per-wave string tables
-  size_t pw_cap = 0;
-  void *es_buf = nullptr;   // qh_encode_sections_batch: per-string / per-line scratch
-  size_t es_cap = 0;
-  void *es_ebuf = nullptr;  // qh_encode_sections_batch: the picked Huffman strings
-  size_t es_ecap = 0;
-  void *es_loff = nullptr;  // qh_encode_sections_batch: per-line offsets
-  size_t es_loff_cap = 0;   // (bytes)
-  uint64_t es_nl_hint = 0;  // the most lines a call has seen (the offsets' capacity)
-  uint64_t *es_h = nullptr;  // pinned: the sections encoder's totals read back
-  hipEvent_t es_ev = nullptr;  // recorded after that copy
-  // fused encoder (qh_enc_fused.inc): two halves of window records and of
-  // ticket counters, used by alternate calls
-  void *d_ew = nullptr;
-  size_t ew_cap = 0;  // windows per half
+  uint64_t es_nl_hint = 0;  // the most lines a call has seen (kBufEncSecLoff's capacity)
+  hipEvent_t es_ev = nullptr;  // recorded after the copy into kBufEncSecHost
+  // fused encoder (qh_enc_fused.inc): the halves of kBufEw are used by
+  // alternate calls
   int ew_par = 0;
   int ew_grid = 0;
   int es_grid = 0;       // qh_k_encs: resident workgroups
@@ -147,9 +120,6 @@ struct qh_ctx {
   // qh_k_dec_plan's bounds (kPlanSkew, kPlanSkewLong; development:
   // QHUFF_PLAN_SKEW, QHUFF_PLAN_SKEW_LONG)
   float plan_skew = kPlanSkew, plan_skew_long = kPlanSkewLong;
-  // host-mode staging
-  void *h_buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t h_cap[4] = {0, 0, 0, 0};
   // timing
   bool timing = false;
   struct Ev {
@@ -158,6 +128,9 @@ struct qh_ctx {
   };
   std::vector<Ev> events;
   std::vector<hipEvent_t> pool;
+  qh_ctx() {
+    for (int k = kBufPinned0; k < kNumBuf; ++k) buf[k].kind = qhs::kPinned;
+  }
 };
 
 namespace {
@@ -172,6 +145,46 @@ namespace {
     }                                                                          \
   } while (0)
 
+// HIP's memory behind qh_scratch.h: the context's stream is synchronised
+// before a buffer that may be in use is freed.
+struct HipAlloc {
+  hipStream_t stream;
+  bool alloc(void **p, size_t bytes, qhs::Kind k) {
+    return (k == qhs::kPinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes)) == hipSuccess;
+  }
+  void free(void *p, qhs::Kind k) { k == qhs::kPinned ? (void)hipHostFree(p) : (void)hipFree(p); }
+  bool quiesce() { return hipStreamSynchronize(stream) == hipSuccess; }
+};
+
+// At least `bytes` in buffer `id`, grown (never shrunk, contents not kept)
+// on demand.  *fresh: the buffer is a new allocation (its owner's zeroes or
+// flags have to be set up again).
+int reserve(qh_ctx *c, int id, size_t bytes, qhs::Policy pol = qhs::kPow2MiB, bool *fresh = nullptr) {
+  HipAlloc a{c->stream};
+  const int r = qhs::reserve(a, c->buf[id], bytes, pol);
+  if (fresh) *fresh = r == qhs::kGrown;
+  if (r != qhs::kFailed) return 0;
+  fprintf(stderr, "qhuff: buffer %d: %zu bytes not reserved: %s\n", id, bytes,
+          hipGetErrorString(hipGetLastError()));
+  return QH_ERR_FATAL;
+}
+template <class T = void>
+T *mem(const qh_ctx *c, int id) {
+  return static_cast<T *>(c->buf[id].p);
+}
+
+// Events and streams owned by the context.
+int make_event(qh_ctx *c, hipEvent_t *e, unsigned flags = hipEventDisableTiming) {
+  QH_HIP(hipEventCreateWithFlags(e, flags));
+  c->owned_ev.push_back(*e);
+  return 0;
+}
+int make_stream(qh_ctx *c, hipStream_t *s) {
+  QH_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  c->owned_streams.push_back(*s);
+  return 0;
+}
+
 hipEvent_t take_event(qh_ctx *c) {
   if (!c->pool.empty()) {
     hipEvent_t e = c->pool.back();
@@ -179,8 +192,7 @@ hipEvent_t take_event(qh_ctx *c) {
     return e;
   }
   hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
+  return make_event(c, &e, hipEventDefault) ? nullptr : e;
 }
 
 struct Timed {
@@ -204,15 +216,7 @@ struct Timed {
 
 int ensure_tile_state(qh_ctx *c, uint64_t n) {
   const size_t tiles = (size_t)((n + kScanTile - 1) / kScanTile) + 1;
-  if (tiles + 2 > c->tile_state_cap) {
-    if (c->d_tile_state) hipFree(c->d_tile_state);
-    c->d_tile_state = nullptr;
-    size_t cap = 1024;
-    while (cap < tiles + 2) cap *= 2;
-    QH_HIP(hipMalloc(&c->d_tile_state, cap * sizeof(uint64_t)));
-    c->tile_state_cap = cap;
-  }
-  return 0;
+  return reserve(c, kBufTileState, (tiles + 2) * sizeof(uint64_t), qhs::Policy{1024 * sizeof(uint64_t)});
 }
 
 // out[i].off = exclusive prefix of out[i].len (qh_scan.inc).
@@ -222,10 +226,10 @@ int launch_scan(qh_ctx *c, const SpanIn *in, SpanOut *out, uint64_t n) {
   if (rv) return rv;
   const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
   // word 0 = tile counter (as u32), words 1.. = tile states
-  QH_HIP(hipMemsetAsync(c->d_tile_state, 0, (tiles + 1) * sizeof(uint64_t),
-                        c->stream));
-  uint32_t *ctr = reinterpret_cast<uint32_t *>(c->d_tile_state);
-  uint64_t *states = c->d_tile_state + 1;
+  uint64_t *const ts = mem<uint64_t>(c, kBufTileState);
+  QH_HIP(hipMemsetAsync(ts, 0, (tiles + 1) * sizeof(uint64_t), c->stream));
+  uint32_t *ctr = reinterpret_cast<uint32_t *>(ts);
+  uint64_t *states = ts + 1;
   Timed t(c, "qh_k_scan");
   hipLaunchKernelGGL(qh_k_scan, dim3((unsigned)tiles), dim3(kBlock), 0,
                      c->stream, in, out, n, states, ctr, c->d_stats);
@@ -233,26 +237,9 @@ int launch_scan(qh_ctx *c, const SpanIn *in, SpanOut *out, uint64_t n) {
   return 0;
 }
 
-// A device scratch buffer of at least `bytes`, grown (never shrunk) on
-// demand; the stream is synchronised before a buffer in use is freed.
-int grow(qh_ctx *c, void **buf, size_t *cap, size_t bytes) {
-  if (*cap >= bytes) return 0;
-  if (*buf) {
-    QH_HIP(hipStreamSynchronize(c->stream));
-    hipFree(*buf);
-  }
-  *buf = nullptr;
-  *cap = 0;
-  size_t nc = 1u << 20;
-  while (nc < bytes) nc *= 2;
-  QH_HIP(hipMalloc(buf, nc));
-  *cap = nc;
-  return 0;
-}
-
 int reset_stats(qh_ctx *c, uint64_t n) {
   c->stats_par ^= 1;
-  c->d_stats = c->d_stats2 + c->stats_par;
+  c->d_stats = mem<DevStats>(c, kBufStats) + c->stats_par;
   if (!c->stats_clean) QH_HIP(hipMemsetAsync(c->d_stats, 0, sizeof(DevStats), c->stream));
   c->stats_clean = false;
   c->last_n = n;
@@ -260,7 +247,7 @@ int reset_stats(qh_ctx *c, uint64_t n) {
 }
 // The stats buffer the next op will use (zeroed by this op's first kernel,
 // which then sets c->stats_clean).
-DevStats *stats_other(qh_ctx *c) { return c->d_stats2 + (c->stats_par ^ 1); }
+DevStats *stats_other(qh_ctx *c) { return mem<DevStats>(c, kBufStats) + (c->stats_par ^ 1); }
 
 int check_ctx(qh_ctx *c) {
   if (!c) return QH_ERR_INVALID_ARGUMENT;
@@ -279,13 +266,7 @@ int chunk_grid(qh_ctx *c, uint64_t n, int blocks_per_cu) {
 }
 
 int ensure_blk(qh_ctx *c, int grid) {
-  if ((size_t)grid <= c->blk_cap) return 0;
-  if (c->d_blk) hipFree(c->d_blk);
-  c->d_blk = nullptr;
-  c->blk_cap = 0;
-  QH_HIP(hipMalloc(&c->d_blk, (size_t)grid * sizeof(uint64_t)));
-  c->blk_cap = (size_t)grid;
-  return 0;
+  return reserve(c, kBufBlk, (size_t)grid * sizeof(uint64_t), qhs::kExact);
 }
 
 // Blocks of `kernel` resident per CU (hipOccupancy* assumes 64 KiB of LDS;
@@ -330,15 +311,15 @@ void launch_enc_lanes(qh_ctx *c, int grid, const uint8_t *src, const SpanIn *in,
                       uint32_t per) {
   if (enc_lanes_nt(c) == 128)
     hipLaunchKernelGGL(qh_k_enc_lanes<128>, dim3(grid), dim3(128), 0, c->stream, src, in, out, n,
-                       dst, dst_cap, (const uint32_t *)c->d_sym, totals, c->d_stats, per,
+                       dst, dst_cap, mem<const uint32_t>(c, kBufSym), totals, c->d_stats, per,
                        (const EncWin *)nullptr, (const uint32_t *)nullptr);
   else if (enc_lanes_nt(c) == 512)
     hipLaunchKernelGGL(qh_k_enc_lanes<512>, dim3(grid), dim3(512), 0, c->stream, src, in, out, n,
-                       dst, dst_cap, (const uint32_t *)c->d_sym, totals, c->d_stats, per,
+                       dst, dst_cap, mem<const uint32_t>(c, kBufSym), totals, c->d_stats, per,
                        (const EncWin *)nullptr, (const uint32_t *)nullptr);
   else
     hipLaunchKernelGGL(qh_k_enc_lanes<256>, dim3(grid), dim3(256), 0, c->stream, src, in, out, n,
-                       dst, dst_cap, (const uint32_t *)c->d_sym, totals, c->d_stats, per,
+                       dst, dst_cap, mem<const uint32_t>(c, kBufSym), totals, c->d_stats, per,
                        (const EncWin *)nullptr, (const uint32_t *)nullptr);
 }
 
@@ -375,8 +356,16 @@ uint32_t lens_kpb(qh_ctx *c, uint64_t n, int grid, uint32_t *ws_out = nullptr) {
   return (uint32_t)kpb;
 }
 
+// The encoder's block totals: two halves of btot_cap words, used by
+// alternate ops.
+size_t btot_cap(const qh_ctx *c) { return c->buf[kBufBtot].cap / (2 * sizeof(uint64_t)); }
+uint64_t *btot_half(const qh_ctx *c, int par) {
+  uint64_t *const b = mem<uint64_t>(c, kBufBtot);
+  return b ? b + par * btot_cap(c) : nullptr;
+}
+
 // Encoded lengths (qh_k_enc_lens): out[i].len and/or hlen[i]; per-block
-// totals into c->d_blk when `totals`.
+// totals into kBufBlk when `totals`.
 int launch_enc_lens(qh_ctx *c, const uint8_t *src, const SpanIn *in,
                     uint64_t n, uint32_t *hlen, SpanOut *out, int grid,
                     bool totals, uint64_t *btot = nullptr,
@@ -388,8 +377,8 @@ int launch_enc_lens(qh_ctx *c, const uint8_t *src, const SpanIn *in,
   const int sgrid = (int)std::min<size_t>(nwin, (size_t)lens_grid_of(c));
   // the next op's stats and block totals, zeroed by this kernel
   DevStats *const zs = stats_other(c);
-  uint64_t *const zb = c->d_btot2 ? c->d_btot2 + (c->btot_par ^ 1) * c->btot_cap : nullptr;
-  const uint32_t zbn = zb ? (uint32_t)c->btot_cap : 0u;
+  uint64_t *const zb = btot_half(c, c->btot_par ^ 1);
+  const uint32_t zbn = zb ? (uint32_t)btot_cap(c) : 0u;
   {
     // (one launch: windows whose strings are scattered are counted by a lane
     // per string inside it -- a separate kernel for them cost ~6 us a call
@@ -398,7 +387,7 @@ int launch_enc_lens(qh_ctx *c, const uint8_t *src, const SpanIn *in,
     hipLaunchKernelGGL(qh_k_enc_lens_stream<QH_LENS_WAVES>, dim3(sgrid), dim3(QH_LENS_WAVES * 64),
                        0, c->stream, src, in, out, hlen, n / (uint64_t)grid,
                        (uint32_t)(n % (uint64_t)grid), (uint32_t)grid, kpb, ws,
-                       (const uint32_t *)c->d_sym, totals ? c->d_blk : nullptr, btot, c->d_stats,
+                       mem<const uint32_t>(c, kBufSym), totals ? mem<uint64_t>(c, kBufBlk) : nullptr, btot, c->d_stats,
                        c->dbg | opts | (c->lens_lane ? 4u : 0u), (const uint8_t *)nullptr, zs, zb, zbn,
                        hint);
   }
@@ -415,30 +404,37 @@ int count_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
                          false);
 }
 
-// The fused encoder (qh_enc_fused.inc): one launch of qh_k_encw.  Its
-// window records and ticket counters are double-buffered: a launch zeroes
-// the pair the next call will use (both zeroed when allocated).
+// The fused and segment encoders' window records and ticket counters, two
+// halves used by alternate calls: a launch zeroes the pair the next call will
+// use (both zeroed when allocated).  Room for nwin windows; p: this call's half.
+struct EncWindows {
+  uint64_t *recs;
+  uint32_t *ctrs;
+  uint64_t cap;  // windows per half
+  int p;
+};
+int enc_windows(qh_ctx *c, uint64_t nwin, EncWindows &w) {
+  constexpr size_t ctr_b = 2 * 32 * kEwHeads * sizeof(uint32_t);
+  bool fresh = false;
+  int rv = reserve(c, kBufEw, 2 * qhs::pow2_at_least(nwin, 4096) * sizeof(uint64_t) + ctr_b,
+                   qhs::kExact, &fresh);
+  if (rv) return rv;
+  if (fresh) QH_HIP(hipMemsetAsync(c->buf[kBufEw].p, 0, c->buf[kBufEw].cap, c->stream));
+  w.cap = (c->buf[kBufEw].cap - ctr_b) / (2 * sizeof(uint64_t));
+  w.recs = mem<uint64_t>(c, kBufEw);
+  w.ctrs = reinterpret_cast<uint32_t *>(w.recs + 2 * w.cap);
+  w.p = c->ew_par;
+  c->ew_par ^= 1;
+  return 0;
+}
+
+// The fused encoder (qh_enc_fused.inc): one launch of qh_k_encw.
 int encode_fused(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, uint8_t *dst,
                  uint64_t dst_cap, SpanOut *out, unsigned long long *hint = nullptr) {
-  const uint64_t nwin = (n + kEwStrings - 1) / kEwStrings;
-  if (nwin > c->ew_cap) {
-    if (c->d_ew) {
-      QH_HIP(hipStreamSynchronize(c->stream));
-      hipFree(c->d_ew);
-    }
-    c->d_ew = nullptr;
-    c->ew_cap = 0;
-    size_t cap = 4096;
-    while (cap < nwin) cap *= 2;
-    const size_t bytes = 2 * cap * sizeof(uint64_t) + 2 * 32 * kEwHeads * sizeof(uint32_t);
-    QH_HIP(hipMalloc(&c->d_ew, bytes));
-    QH_HIP(hipMemsetAsync(c->d_ew, 0, bytes, c->stream));
-    c->ew_cap = cap;
-  }
-  uint64_t *const recs = reinterpret_cast<uint64_t *>(c->d_ew);
-  uint32_t *const ctrs = reinterpret_cast<uint32_t *>(recs + 2 * c->ew_cap);
-  const int p = c->ew_par;
-  c->ew_par ^= 1;
+  EncWindows w;
+  int rv = enc_windows(c, (n + kEwStrings - 1) / kEwStrings, w);
+  if (rv) return rv;
+  const int p = w.p;
   if (!c->ew_grid) c->ew_grid = c->num_cus * resident_blocks((const void *)qh_k_encw, 64 * kEwWaves);
   // per-XCD ticket counters on the whole chip (8 XCDs of 32 CUs) when the
   // stream reaches every CU; else one counter (a partition's XCD ids need
@@ -447,9 +443,9 @@ int encode_fused(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
   const uint32_t heads = c->num_cus == 256 && c->all_cus ? kEwHeads : 1u;
   Timed t(c, "qh_k_encw");
   hipLaunchKernelGGL(qh_k_encw, dim3(c->ew_grid), dim3(64 * kEwWaves), 0, c->stream, src, in, out,
-                     n, dst, dst_cap, (const uint32_t *)c->d_sym, ctrs + p * 32 * kEwHeads,
-                     ctrs + (p ^ 1) * 32 * kEwHeads, recs + p * c->ew_cap,
-                     recs + (p ^ 1) * c->ew_cap, (uint64_t)c->ew_cap, heads, c->d_stats,
+                     n, dst, dst_cap, mem<const uint32_t>(c, kBufSym), w.ctrs + p * 32 * kEwHeads,
+                     w.ctrs + (p ^ 1) * 32 * kEwHeads, w.recs + p * w.cap,
+                     w.recs + (p ^ 1) * w.cap, w.cap, heads, c->d_stats,
                      stats_other(c), hint);
   QH_HIP(hipGetLastError());
   c->stats_clean = true;
@@ -461,32 +457,17 @@ int encode_fused(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
 // records and ticket counters as the fused encoder's (128-string windows).
 int encode_segments(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, uint8_t *dst,
                     uint64_t dst_cap, SpanOut *out, unsigned long long *hint = nullptr) {
-  const uint64_t nwin = (n + kSgStr - 1) / kSgStr;
-  if (nwin > c->ew_cap) {
-    if (c->d_ew) {
-      QH_HIP(hipStreamSynchronize(c->stream));
-      hipFree(c->d_ew);
-    }
-    c->d_ew = nullptr;
-    c->ew_cap = 0;
-    size_t cap = 4096;
-    while (cap < nwin) cap *= 2;
-    const size_t bytes = 2 * cap * sizeof(uint64_t) + 2 * 32 * kEwHeads * sizeof(uint32_t);
-    QH_HIP(hipMalloc(&c->d_ew, bytes));
-    QH_HIP(hipMemsetAsync(c->d_ew, 0, bytes, c->stream));
-    c->ew_cap = cap;
-  }
-  uint64_t *const recs = reinterpret_cast<uint64_t *>(c->d_ew);
-  uint32_t *const ctrs = reinterpret_cast<uint32_t *>(recs + 2 * c->ew_cap);
-  const int p = c->ew_par;
-  c->ew_par ^= 1;
+  EncWindows w;
+  int rv = enc_windows(c, (n + kSgStr - 1) / kSgStr, w);
+  if (rv) return rv;
+  const int p = w.p;
   if (!c->es_grid) c->es_grid = c->num_cus * resident_blocks((const void *)qh_k_encs, 64 * kSgWaves);
   const uint32_t heads = c->num_cus == 256 && c->all_cus ? kEwHeads : 1u;
   Timed t(c, "qh_k_encs");
   hipLaunchKernelGGL(qh_k_encs, dim3(c->es_grid), dim3(64 * kSgWaves), 0, c->stream, src, in, out,
-                     n, dst, dst_cap, (const uint32_t *)c->d_sym, ctrs + p * 32 * kEwHeads,
-                     ctrs + (p ^ 1) * 32 * kEwHeads, recs + p * c->ew_cap,
-                     recs + (p ^ 1) * c->ew_cap, (uint64_t)c->ew_cap, heads, c->d_stats,
+                     n, dst, dst_cap, mem<const uint32_t>(c, kBufSym), w.ctrs + p * 32 * kEwHeads,
+                     w.ctrs + (p ^ 1) * 32 * kEwHeads, w.recs + p * w.cap,
+                     w.recs + (p ^ 1) * w.cap, w.cap, heads, c->d_stats,
                      stats_other(c), hint, c->dbg >> 8);
   QH_HIP(hipGetLastError());
   c->stats_clean = true;
@@ -515,7 +496,7 @@ void enc_auto_choose(qh_ctx *c) {
   c->ehint_pending = false;
   unsigned long long t[4] = {0, 0, 0, 0};
   for (int b = 0; b < c->ehint_grid; ++b)
-    for (int k = 0; k < 4; ++k) t[k] += c->h_ehint[4 * b + k];
+    for (int k = 0; k < 4; ++k) t[k] += mem<unsigned long long>(c, kBufEhintHost)[4 * b + k];
   if (t[0] == 0) return;
   const double m1 = (double)t[1] / (double)t[0], m2 = (double)t[2] / (double)t[0];
   c->ehint_fused = m2 > 2.5 * m1 * m1 || m1 > 512.0 || t[3] > t[1];
@@ -523,17 +504,15 @@ void enc_auto_choose(qh_ctx *c) {
 // The hint buffer this call's encoder writes (grid workgroups), or null.
 unsigned long long *enc_hint_buffer(qh_ctx *c, int grid) {
   if (grid > kEncHintBlocks) return nullptr;
-  if (!c->d_ehint) {
-    if (hipMalloc(&c->d_ehint, 2 * 4 * kEncHintBlocks * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_ehint, 4 * kEncHintBlocks * sizeof(unsigned long long)) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->s_ehint, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ehint_src, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ehint_done, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
+  constexpr size_t half_b = 4 * kEncHintBlocks * sizeof(unsigned long long);
+  if (!c->ehint_done &&
+      (reserve(c, kBufEhint, 2 * half_b, qhs::kExact) || reserve(c, kBufEhintHost, half_b, qhs::kExact) ||
+       (!c->s_ehint && make_stream(c, &c->s_ehint)) || (!c->ehint_src && make_event(c, &c->ehint_src)) ||
+       make_event(c, &c->ehint_done))) {
+    (void)hipGetLastError();
+    return nullptr;
   }
-  return c->d_ehint + 4 * kEncHintBlocks * c->ehint_par;
+  return mem<unsigned long long>(c, kBufEhint) + 4 * kEncHintBlocks * c->ehint_par;
 }
 // After the encoder's launch: copy its hint back (one copy in flight at a
 // time; the next call's kernels write the other buffer).
@@ -541,7 +520,7 @@ int enc_hint_copy(qh_ctx *c, const unsigned long long *hint, int grid) {
   if (!hint || c->ehint_pending) return 0;
   QH_HIP(hipEventRecord(c->ehint_src, c->stream));
   QH_HIP(hipStreamWaitEvent(c->s_ehint, c->ehint_src, 0));
-  QH_HIP(hipMemcpyAsync(c->h_ehint, hint, 4 * (size_t)grid * sizeof(unsigned long long),
+  QH_HIP(hipMemcpyAsync(mem(c, kBufEhintHost), hint, 4 * (size_t)grid * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, c->s_ehint));
   QH_HIP(hipEventRecord(c->ehint_done, c->s_ehint));
   c->ehint_pending = true;
@@ -571,39 +550,30 @@ int encode_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
     if ((rv = encode_fused(c, src, in, n, dst, dst_cap, out, hint))) return rv;
     return enc_hint_copy(c, hint, c->ew_grid);
   }
-  const bool stream = c->codes_kind == 1;
   if (QH_DEV_KNOBS && !c->enc_bpc && getenv("QHUFF_ENC_BPC"))  // development: blocks per CU
     c->enc_bpc = atoi(getenv("QHUFF_ENC_BPC"));
   if (!c->enc_bpc) c->enc_bpc = enc_lanes_bpc(c);
   if (!c->enc_bpc_w) c->enc_bpc_w = resident_blocks((const void *)qh_k_enc_waves, kBlock);
   // resident: no trailing second wave
   const int grid = chunk_grid(c, n, c->codes_kind == 2 ? c->enc_bpc_w : c->enc_bpc);
-  const uint32_t per = c->enc_kind ? 1u : lens_kpb(c, n, grid);  // totals per block
+  const uint32_t per = lens_kpb(c, n, grid);  // totals per block
   // window totals (grid * per), then one total per block of the codes grid
   // (the length kernels add each window's total into its block's)
   if ((rv = ensure_blk(c, grid * (int)per))) return rv;
-  uint64_t *btot = nullptr;
-  if (!c->enc_kind && !stream) {  // block totals: double-buffered (qh_ctx)
-    if ((size_t)grid > c->btot_cap) {
-      if (c->d_btot2) hipFree(c->d_btot2);
-      c->d_btot2 = nullptr;
-      c->btot_cap = 0;
-      QH_HIP(hipMalloc(&c->d_btot2, 2 * (size_t)grid * sizeof(uint64_t)));
-      c->btot_cap = (size_t)grid;
-      c->btot_clean = false;
-    }
-    c->btot_par ^= 1;
-    btot = c->d_btot2 + c->btot_par * c->btot_cap;
-    if (!c->btot_clean) QH_HIP(hipMemsetAsync(btot, 0, (size_t)grid * sizeof(uint64_t), c->stream));
-    c->btot_clean = false;
-  }
+  // block totals: double-buffered (qh_ctx)
+  bool fresh = false;
+  if ((rv = reserve(c, kBufBtot, 2 * (size_t)grid * sizeof(uint64_t), qhs::kExact, &fresh))) return rv;
+  if (fresh) c->btot_clean = false;
+  c->btot_par ^= 1;
+  uint64_t *const btot = btot_half(c, c->btot_par);
+  if (!c->btot_clean) QH_HIP(hipMemsetAsync(btot, 0, (size_t)grid * sizeof(uint64_t), c->stream));
+  c->btot_clean = false;
   // (the length pass's grid: launch_enc_lens's sgrid)
   const int sgrid = (int)std::min<size_t>((size_t)grid * lens_kpb(c, n, grid), (size_t)lens_grid_of(c));
   unsigned long long *const hint = autoc ? enc_hint_buffer(c, sgrid) : nullptr;
-  // the region codes pass (QH_ENCODER_REGION, and AUTO's choice for text):
-  // the length pass leaves each string's pad in out[i].status for it
-  const bool region = !c->enc_kind && !stream && btot && !c->lens_lane && n < (1ull << 32) &&
-                      c->codes_kind == 5;
+  // the region codes pass (QH_ENCODER_REGION only: AUTO never picks it): the
+  // length pass leaves each string's pad in out[i].status for it
+  const bool region = !c->lens_lane && n < (1ull << 32) && c->codes_kind == 5;
   if ((rv = launch_enc_lens(c, src, in, n, nullptr, out, grid, true, btot, hint,
                             region ? kLensPad : 0u)))
     return rv;
@@ -615,7 +585,7 @@ int encode_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
     const int rgrid = (int)std::min<uint64_t>((uint64_t)c->rg_grid, (uint64_t)grid * kpb);
     Timed t(c, "qh_k_enc_region");
     hipLaunchKernelGGL(qh_k_enc_region<kRgWaves>, dim3(rgrid), dim3(64 * kRgWaves), 0, c->stream, src,
-                       in, out, dst, dst_cap, (const uint32_t *)c->d_sym, (const uint64_t *)c->d_blk,
+                       in, out, dst, dst_cap, mem<const uint32_t>(c, kBufSym), mem<const uint64_t>(c, kBufBlk),
                        (const uint64_t *)btot, n / (uint64_t)grid, (uint32_t)(n % (uint64_t)grid),
                        (uint32_t)grid, kpb, ws, c->d_stats);
     QH_HIP(hipGetLastError());
@@ -624,19 +594,16 @@ int encode_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
   if (c->codes_kind == 2) {  // per-wave chunks (QH_ENCODER_WAVES)
     Timed t(c, "qh_k_enc_waves");
     hipLaunchKernelGGL(qh_k_enc_waves, dim3(grid), dim3(kBlock), 0, c->stream, src, in, out, n,
-                       dst, dst_cap, (const uint32_t *)c->d_sym, (const uint64_t *)btot,
+                       dst, dst_cap, mem<const uint32_t>(c, kBufSym), (const uint64_t *)btot,
                        c->d_stats);
     QH_HIP(hipGetLastError());
     return 0;
   }
-  if (!stream) {  // one string per lane, workgroup windows (default)
-    Timed t(c, "qh_k_enc_lanes");
-    launch_enc_lanes(c, grid, src, in, out, n, dst, dst_cap,
-                     (const uint64_t *)(btot ? btot : c->d_blk), btot ? 1u : per);
-    QH_HIP(hipGetLastError());
-    return enc_hint_copy(c, hint, sgrid);
-  }
-  return 0;
+  // one string per lane, workgroup windows (default)
+  Timed t(c, "qh_k_enc_lanes");
+  launch_enc_lanes(c, grid, src, in, out, n, dst, dst_cap, (const uint64_t *)btot, 1u);
+  QH_HIP(hipGetLastError());
+  return enc_hint_copy(c, hint, sgrid);
 }
 
 // Peek decoder variants (QHUFF_DECODER=peekW[_R][wN]: table width W, R
@@ -717,50 +684,42 @@ static_assert(kPeekVariants[1].waves && !kPeekVariants[1].adaptive && !kPeekVari
 static_assert(kPeekVariants[2].sorted && !kPeekVariants[2].local && !kPeekVariants[2].adaptive &&
                   !kPeekVariants[2].pair,
               "sorted11: the sorted decoder");
-constexpr int kDecPeek0 = 3, kDecWaves = kDecPeek0 + 1, kDecSorted = kDecPeek0 + 2, kDecRun = 100,
-              kDecQ = 200;
+// qh_ctx::dec_kind: an index into kPeekVariants (qh_ctx_set_decoder sets one
+// of these three; development builds any entry, by name)
+constexpr int kDecWindows = 0, kDecWaves = 1, kDecSorted = 2;
+const PeekVariant &variant(const qh_ctx *c) { return kPeekVariants[c->dec_kind]; }
 
-int dec_blocks_per_cu(int kind) {
-  if (kind >= kDecPeek0 && kind < kDecPeek0 + kNumPeek)
-    return resident_blocks((const void *)kPeekVariants[kind - kDecPeek0].fn,
-                           kPeekVariants[kind - kDecPeek0].threads);
-  return 1;
+int dec_blocks_per_cu(const qh_ctx *c) {
+  return resident_blocks((const void *)variant(c).fn, variant(c).threads);
 }
 
 int launch_peek(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
                 uint8_t *dst, uint64_t dst_cap, SpanOut *out, int grid, int8_t *verdict,
                 void *list = nullptr) {
-  if (c->dec_kind < kDecPeek0 || c->dec_kind >= kDecPeek0 + kNumPeek)
-    return QH_ERR_INVALID_ARGUMENT;
-  const PeekVariant &v = kPeekVariants[c->dec_kind - kDecPeek0];
+  const PeekVariant &v = variant(c);
   void *scratch = nullptr;
   if (v.threads != kBlock || v.waves) {  // wave-chunk kernels: a 256-entry region per wave
     const size_t need = (size_t)grid * (v.threads / 64) * kWChunk * sizeof(WInfo);
-    int rv = grow(c, &c->pw_buf, &c->pw_cap, need);
+    int rv = reserve(c, kBufWaves, need);
     if (rv) return rv;
-    scratch = c->pw_buf;
+    scratch = mem(c, kBufWaves);
   }
   if (verdict && !v.fn_check) return QH_ERR_INVALID_ARGUMENT;
-  const uint64_t *blk = (const uint64_t *)c->d_blk;
-  if (v.sorted) scratch = c->d_srec;  // (decode_sorted wrote the records)
+  const uint64_t *blk = mem<const uint64_t>(c, kBufBlk);
+  if (v.sorted) scratch = mem(c, kBufSrec);  // (decode_sorted wrote the records)
   if (v.sorted && !v.local)  // (the count of wave-per-string records, behind the schedule's bases)
-    blk = reinterpret_cast<const uint64_t *>(reinterpret_cast<const uint8_t *>(c->d_sched) +
+    blk = reinterpret_cast<const uint64_t *>(mem<const uint8_t>(c, kBufSched) +
                                              2 * (size_t)kSchedGrid * kSchedClasses * sizeof(uint32_t) +
                                              kSchedClasses * 4 + kSchedGrid * 8);
   if (list) scratch = list;  // (the fused-check window decoder's long strings)
   hipLaunchKernelGGL(verdict ? v.fn_check : v.fn, dim3(grid), dim3(v.threads), 0, c->stream,
                      src, in, out, n, dst,
-                     dst_cap, v.pair ? c->d_ptab[v.W - 12] : c->d_peek[v.W - 8], (const DecTables *)c->d_dtab,
+                     dst_cap, mem<const uint32_t>(c, v.pair ? kBufPtab0 + v.W - 12 : kBufPeek0 + v.W - 8),
+                     mem<const DecTables>(c, kBufDtab),
                      blk, c->d_stats, c->dbg, scratch, verdict);
   QH_HIP(hipGetLastError());
   return 0;
 }
-
-// Resident blocks per CU of a kernel from its LDS and VGPR use (gfx950:
-// 160 KiB LDS per CU, 512 VGPRs per SIMD lane in granules of 8, 8 waves per
-// SIMD).  hipOccupancyMaxActiveBlocksPerMultiprocessor assumes 64 KiB of LDS.
-
-
 
 // Decode: per-block reserved bytes -> lane decode.
 // verdict (optional): per string the field check of its decoded bytes
@@ -770,15 +729,15 @@ int launch_peek(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
 // records in class order, then the window decoder over them round-robin.
 int decode_sorted(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, uint8_t *dst,
                   uint64_t dst_cap, SpanOut *out, int8_t *verdict) {
-  if (kPeekVariants[c->dec_kind - kDecPeek0].local) {  // one pass, the window decoder's grid
-    const int grid = chunk_grid(c, n, c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c->dec_kind));
+  if (variant(c).local) {  // one pass, the window decoder's grid
+    const int grid = chunk_grid(c, n, c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c));
     int rv = ensure_blk(c, grid);
     if (rv) return rv;
-    if ((rv = grow(c, &c->d_srec, &c->srec_cap, (size_t)n * sizeof(SchedRec)))) return rv;
+    if ((rv = reserve(c, kBufSrec, (size_t)n * sizeof(SchedRec)))) return rv;
     {
       Timed t(c, "qh_k_sched_local");
-      hipLaunchKernelGGL(qh_k_sched_local, dim3(grid), dim3(kBlock), 0, c->stream, in, n, c->d_blk,
-                         (SchedRec *)c->d_srec, stats_other(c));
+      hipLaunchKernelGGL(qh_k_sched_local, dim3(grid), dim3(kBlock), 0, c->stream, in, n,
+                         mem<uint64_t>(c, kBufBlk), mem<SchedRec>(c, kBufSrec), stats_other(c));
       QH_HIP(hipGetLastError());
       c->stats_clean = true;
     }
@@ -790,9 +749,10 @@ int decode_sorted(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, u
   if (rv) return rv;
   // block histograms, block starts per class, class totals, slot bases
   const size_t hbytes = (size_t)kSchedGrid * kSchedClasses * sizeof(uint32_t);
-  if (!c->d_sched) QH_HIP(hipMalloc(&c->d_sched, 2 * hbytes + kSchedClasses * 4 + kSchedGrid * 8 + 64));
-  if ((rv = grow(c, &c->d_srec, &c->srec_cap, (size_t)n * sizeof(SchedRec)))) return rv;
-  uint32_t *const bh = (uint32_t *)c->d_sched;
+  if ((rv = reserve(c, kBufSched, 2 * hbytes + kSchedClasses * 4 + kSchedGrid * 8 + 64, qhs::kExact)) ||
+      (rv = reserve(c, kBufSrec, (size_t)n * sizeof(SchedRec))))
+    return rv;
+  uint32_t *const bh = mem<uint32_t>(c, kBufSched);
   uint32_t *const boff = bh + (size_t)kSchedGrid * kSchedClasses;
   uint32_t *const ctot = boff + (size_t)kSchedGrid * kSchedClasses;
   uint64_t *const sbase = (uint64_t *)(ctot + kSchedClasses);
@@ -800,14 +760,14 @@ int decode_sorted(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, u
   {
     Timed t(c, "qh_k_sched_count");
     hipLaunchKernelGGL(qh_k_sched_count, dim3(grid), dim3(kBlock), 0, c->stream, in, n, bh,
-                       c->d_blk, stats_other(c));
+                       mem<uint64_t>(c, kBufBlk), stats_other(c));
     QH_HIP(hipGetLastError());
     c->stats_clean = true;
   }
   {
     Timed t(c, "qh_k_sched_scan");
     hipLaunchKernelGGL(qh_k_sched_scan, dim3(kSchedClasses + 1), dim3(kBlock), 0, c->stream,
-                       (const uint32_t *)bh, boff, ctot, (const uint64_t *)c->d_blk, sbase,
+                       (const uint32_t *)bh, boff, ctot, mem<const uint64_t>(c, kBufBlk), sbase,
                        (uint32_t)grid);
     QH_HIP(hipGetLastError());
   }
@@ -815,10 +775,10 @@ int decode_sorted(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, u
     Timed t(c, "qh_k_sched_scatter");
     hipLaunchKernelGGL(qh_k_sched_scatter, dim3(grid), dim3(kBlock), 0, c->stream, in, n,
                        (const uint32_t *)boff, (const uint32_t *)ctot, (const uint64_t *)sbase,
-                       (SchedRec *)c->d_srec, c->long_min ? sched_class(c->long_min) : kSchedClasses, nlong);
+                       mem<SchedRec>(c, kBufSrec), c->long_min ? sched_class(c->long_min) : kSchedClasses, nlong);
     QH_HIP(hipGetLastError());
   }
-  const PeekVariant &v = kPeekVariants[c->dec_kind - kDecPeek0];
+  const PeekVariant &v = variant(c);
   if (!c->sorted_grid) c->sorted_grid = c->num_cus * resident_blocks((const void *)v.fn, kBlock);
   // (enough workgroups for every string to be a long one: one each)
   const int dgrid = (int)std::min<uint64_t>(n, (uint64_t)c->sorted_grid);
@@ -834,61 +794,54 @@ int decode_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n,
                   int8_t *verdict = nullptr, uint64_t nlong = 0) {
   int rv = reset ? reset_stats(c, n) : 0;
   if (rv || n == 0) return rv;
-  if (c->dec_kind >= kDecPeek0 && c->dec_kind < kDecPeek0 + kNumPeek &&
-      kPeekVariants[c->dec_kind - kDecPeek0].sorted) {
+  if (variant(c).sorted) {
     if (n < (1ull << 32)) return decode_sorted(c, src, in, n, dst, dst_cap, out, verdict);
     // (records index strings with 32 bits: larger batches take the window
     // decoder over the spans as given)
     const int keep = c->dec_kind;
-    c->dec_kind = kDecPeek0;
+    c->dec_kind = kDecWindows;
     rv = decode_device(c, src, in, n, dst, dst_cap, out, false, verdict);
     c->dec_kind = keep;
     return rv;
   }
-  int grid = chunk_grid(c, n, c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c->dec_kind));
-  if (c->dec_kind >= kDecPeek0 && c->dec_kind < kDecPeek0 + kNumPeek &&
-      !kPeekVariants[c->dec_kind - kDecPeek0].waves) {
+  int grid = chunk_grid(c, n, c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c));
+  if (!variant(c).waves) {
     // the window decoder: up to one block per string (a block's long strings
     // are decoded a wave each after its windows, so a small batch of long
     // strings spreads over the chip)
-    const uint64_t cap = (uint64_t)c->num_cus * (c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c->dec_kind));
+    const uint64_t cap = (uint64_t)c->num_cus * (c->bpc > 0 ? c->bpc : dec_blocks_per_cu(c));
     grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(n, cap));
   }
   if ((rv = ensure_blk(c, grid))) return rv;
   // the window decoder's plan (per-block schedule; the fused-check
   // decoder's list of long strings after the records)
-  const bool adaptive = c->dec_kind >= kDecPeek0 && c->dec_kind < kDecPeek0 + kNumPeek &&
-                        kPeekVariants[c->dec_kind - kDecPeek0].adaptive;
+  const bool adaptive = variant(c).adaptive;
   const uint64_t lcap = adaptive && verdict ? nlong : 0;
   if (adaptive) {
     if (nlong > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;
-    if ((rv = grow(c, &c->ll_buf, &c->ll_cap, win_aux_list(grid, n) + lcap * sizeof(SchedRec)))) return rv;
+    if ((rv = reserve(c, kBufLongList, win_aux_list(grid, n) + lcap * sizeof(SchedRec)))) return rv;
     Timed t(c, "qh_k_dec_plan");
-    hipLaunchKernelGGL(qh_k_dec_plan, dim3(grid), dim3(kBlock), 0, c->stream, src, in, n, c->d_blk,
-                       stats_other(c), (uint8_t *)c->ll_buf, (uint32_t)lcap, c->plan_skew, c->plan_skew_long);
+    hipLaunchKernelGGL(qh_k_dec_plan, dim3(grid), dim3(kBlock), 0, c->stream, src, in, n,
+                       mem<uint64_t>(c, kBufBlk), stats_other(c), mem<uint8_t>(c, kBufLongList), (uint32_t)lcap, c->plan_skew, c->plan_skew_long);
   } else {
     Timed t(c, "qh_k_dec_reserve");
     hipLaunchKernelGGL(qh_k_dec_reserve, dim3(grid), dim3(kBlock), 0, c->stream,
-                       in, n, c->d_blk, stats_other(c), nullptr, 0u);
+                       in, n, mem<uint64_t>(c, kBufBlk), stats_other(c), nullptr, 0u);
   }
   QH_HIP(hipGetLastError());
   c->stats_clean = true;
-  if (c->dec_kind >= kDecPeek0) {
-    Timed t(c, "qh_k_dec_peek");
-    rv = launch_peek(c, src, in, n, dst, dst_cap, out, grid, verdict, adaptive ? c->ll_buf : nullptr);
-    if (rv) return rv;
-    if (lcap) {
-      Timed t2(c, "qh_k_dec_long_list");
-      const uint8_t *aux = (const uint8_t *)c->ll_buf;
-      hipLaunchKernelGGL(qh_k_dec_long_list, dim3((unsigned)std::min<uint64_t>(nlong, c->num_cus)),
-                         dim3(64 * kLongNW), 0, c->stream, src, in, out, dst, dst_cap,
-                         (const DecTables *)c->d_dtab, (const uint32_t *)aux,
-                         (const SchedRec *)(aux + win_aux_list(grid, n)), (uint32_t)nlong, c->d_stats,
-                         verdict);
-      QH_HIP(hipGetLastError());
-    }
-  } else {
-    return QH_ERR_INVALID_ARGUMENT;
+  Timed t(c, "qh_k_dec_peek");
+  rv = launch_peek(c, src, in, n, dst, dst_cap, out, grid, verdict, adaptive ? mem(c, kBufLongList) : nullptr);
+  if (rv) return rv;
+  if (lcap) {
+    Timed t2(c, "qh_k_dec_long_list");
+    const uint8_t *aux = mem<const uint8_t>(c, kBufLongList);
+    hipLaunchKernelGGL(qh_k_dec_long_list, dim3((unsigned)std::min<uint64_t>(nlong, c->num_cus)),
+                       dim3(64 * kLongNW), 0, c->stream, src, in, out, dst, dst_cap,
+                       mem<const DecTables>(c, kBufDtab), (const uint32_t *)aux,
+                       (const SchedRec *)(aux + win_aux_list(grid, n)), (uint32_t)nlong, c->d_stats,
+                       verdict);
+    QH_HIP(hipGetLastError());
   }
   QH_HIP(hipGetLastError());
   return 0;
@@ -925,9 +878,9 @@ int decode_dense(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
   const uint64_t words = 2 + (n + qhk::kDnGroup - 1) / qhk::kDnGroup;
   const size_t st_b = (words * sizeof(uint64_t) + 255) & ~(size_t)255;
   // (+16: qh_k_dense_pack loads 16 bytes at a short string's start)
-  if ((rv = grow(c, &c->dn_buf, &c->dn_cap, st_b + dst_cap + 16))) return rv;
-  uint64_t *state = (uint64_t *)c->dn_buf;
-  uint8_t *slots = (uint8_t *)c->dn_buf + st_b;
+  if ((rv = reserve(c, kBufDense, st_b + dst_cap + 16))) return rv;
+  uint64_t *state = mem<uint64_t>(c, kBufDense);
+  uint8_t *slots = mem<uint8_t>(c, kBufDense) + st_b;
   QH_HIP(hipMemsetAsync(state, 0, sizeof(uint64_t), c->stream));  // (the carry in)
   if ((rv = decode_device(c, src, in, n, slots, dst_cap, out, false))) return rv;
   return launch_dense_pack(c, slots, out, n, dst, dst_cap, (const unsigned long long *)state,
@@ -982,27 +935,28 @@ constexpr int kHostScanThreads = 8;           // host threads over the spans' pr
 // The host pipelines' streams, events and pinned words (created once).
 int host_pipe_init(qh_ctx *c) {
   if (c->s_h2d) return 0;
-  QH_HIP(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
-  QH_HIP(hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
-  QH_HIP(hipStreamCreateWithFlags(&c->s_end, hipStreamNonBlocking));
-  QH_HIP(hipEventCreateWithFlags(&c->hp_end_ev, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
-  QH_HIP(hipEventCreateWithFlags(&c->hp_user_ev, hipEventDisableTiming));
-  QH_HIP(hipHostMalloc((void **)&c->h_ends, 64 * sizeof(unsigned long long)));
+  // (blocking-sync events: the returner thread sleeps in its waits instead
+  // of spinning a CPU of the process's quota)
+  const unsigned wait_flags = hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0);
+  int rv = 0;
+  if ((rv = make_stream(c, &c->s_h2d)) || (rv = make_stream(c, &c->s_d2h)) ||
+      (rv = make_stream(c, &c->s_end)) || (rv = make_event(c, &c->hp_end_ev, wait_flags)) ||
+      (rv = make_event(c, &c->hp_user_ev)) ||
+      (rv = reserve(c, kBufEnds, 64 * sizeof(unsigned long long), qhs::kExact)))
+    return rv;
   // (QHUFF_HOST_MAPPED_ENDS, development: the packing kernel stores each
   // slice's end through the device address of this mapped buffer instead
   // of a copy command; measured slower, 6.7 against 4.9 ms per 2^20
   // strings: a kernel that writes host memory ends with a system-scope
   // release, which writes back L2)
   if (QH_DEV_KNOBS && getenv("QHUFF_HOST_MAPPED_ENDS") &&
-      hipHostGetDevicePointer((void **)&c->d_ends, c->h_ends, 0) != hipSuccess) {
+      hipHostGetDevicePointer((void **)&c->d_ends, mem(c, kBufEnds), 0) != hipSuccess) {
     (void)hipGetLastError();
     c->d_ends = nullptr;
   }
   c->hp_ev.resize(2 * kHostSlices, nullptr);
-  // (blocking-sync events: the returner thread sleeps in its waits instead
-  // of spinning a CPU of the process's quota)
   for (auto &e : c->hp_ev)
-    QH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | (QH_HP_BLOCKING ? hipEventBlockingSync : 0)));
+    if ((rv = make_event(c, &e, wait_flags))) return rv;
   return 0;
 }
 
@@ -1101,8 +1055,9 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
   const uint64_t o_in = al(extent), o_slots = o_in + al(n * 16), o_out = o_slots + al(sb[ns]);
   const uint64_t o_tmp = o_out + al(n * 16), o_dense = o_tmp + al(n * 16);
   const uint64_t o_carry = o_dense + al(dcap + 16), total = o_carry + 256;
-  if ((rv = grow(c, &c->hp_buf, &c->hp_cap, total))) return rv;
-  uint8_t *base = (uint8_t *)c->hp_buf;
+  if ((rv = reserve(c, kBufHostPipe, total))) return rv;
+  uint8_t *base = mem<uint8_t>(c, kBufHostPipe);
+  unsigned long long *const h_ends = mem<unsigned long long>(c, kBufEnds);
   uint8_t *d_src = base, *d_slots = base + o_slots, *d_dense = base + o_dense;
   SpanIn *d_in = (SpanIn *)(base + o_in);
   SpanOut *d_out = (SpanOut *)(base + o_out), *d_tmp = (SpanOut *)(base + o_tmp);
@@ -1163,13 +1118,13 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
       // without waiting for any of them)
       if (!c->d_ends && QH_HP_END_RETURNER) {
         QH_HIP(hipStreamWaitEvent(c->s_end, ev_dec[k], 0));
-        QH_HIP(hipMemcpyAsync(c->h_ends + k, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->s_end));
+        QH_HIP(hipMemcpyAsync(h_ends + k, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->s_end));
         QH_HIP(hipEventRecord(c->hp_end_ev, c->s_end));
         QH_HIP(hipEventSynchronize(c->hp_end_ev));
       } else {
         QH_HIP(hipEventSynchronize(ev_dec[k]));
       }
-      const uint64_t end = std::min<uint64_t>(c->h_ends[k], dcap);
+      const uint64_t end = std::min<uint64_t>(h_ends[k], dcap);
       QH_HIP(hipStreamWaitEvent(c->s_d2h, ev_dec[k], 0));
       if (end > done)
         QH_HIP(hipMemcpyAsync(dst + done, d_dense + done, end - done, hipMemcpyDeviceToHost, c->s_d2h));
@@ -1210,7 +1165,7 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
                           c->d_ends ? c->d_ends + k : nullptr, (uint64_t *)(d_tmp + i0[k])) ||
         hipGetLastError() != hipSuccess ||
         (!c->d_ends && !QH_HP_END_RETURNER &&
-         hipMemcpyAsync(c->h_ends + k, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+         hipMemcpyAsync(h_ends + k, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
         hipEventRecord(ev_dec[k], c->stream) != hipSuccess) {
       rv = QH_ERR_FATAL;
       break;
@@ -1228,22 +1183,14 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
 
 // Whether decode_device fuses the field check for the configured decoder.
 bool decoder_checks(const qh_ctx *c) {
-  return c->dec_kind >= kDecPeek0 && c->dec_kind < kDecPeek0 + kNumPeek &&
-         kPeekVariants[c->dec_kind - kDecPeek0].fn_check != nullptr;
+  return variant(c).fn_check != nullptr;
 }
 
 // host-mode staging buffer k (0 = src, 1 = spans in, 2 = dst, 3 = spans out)
 int stage(qh_ctx *c, int k, size_t bytes, void **p) {
-  if (bytes == 0) bytes = 16;
-  if (c->h_cap[k] < bytes) {
-    if (c->h_buf[k]) hipFree(c->h_buf[k]);
-    c->h_buf[k] = nullptr;
-    c->h_cap[k] = 0;
-    QH_HIP(hipMalloc(&c->h_buf[k], bytes));
-    c->h_cap[k] = bytes;
-  }
-  *p = c->h_buf[k];
-  return 0;
+  const int rv = reserve(c, kBufStage0 + k, bytes ? bytes : 16, qhs::kExact);
+  *p = mem(c, kBufStage0 + k);
+  return rv;
 }
 
 uint64_t src_extent(const qh_span_in *in, size_t n) {
@@ -1320,7 +1267,7 @@ QH_EXPORT int qh_debug_long(qh_ctx *c, const uint8_t *src, uint32_t slen, uint8_
   int rv = check_ctx(c);
   if (rv) return rv;
   if (slen < 32) return QH_ERR_INVALID_ARGUMENT;
-  const DecTables *t = (const DecTables *)c->d_dtab;
+  const DecTables *t = mem<const DecTables>(c, kBufDtab);
   if (nw == 1)
     hipLaunchKernelGGL(qhk::qh_k_debug_long<1>, dim3(1), dim3(64), 0, c->stream, src, slen, dst, t, res, trace);
   else if (nw == 4)
@@ -1349,10 +1296,18 @@ static bool stream_all_cus(hipStream_t stream, int num_cus) {
 }
 
 // The decode table blob with its leading-ones table filled in.
-static bool upload_dec_tables(void *d_dtab) {
+static const DecTables *dec_tables() {
   static DecTables t = kDecTables;
   static const bool ok = build_utab(t.utab);
-  return ok && hipMemcpy(d_dtab, &t, sizeof(DecTables), hipMemcpyHostToDevice) == hipSuccess;
+  return ok ? &t : nullptr;
+}
+
+// A table of the context, allocated at its size and filled (src null: zeroed).
+static int upload(qh_ctx *c, int id, const void *src, size_t bytes) {
+  if (reserve(c, id, bytes, qhs::kExact)) return QH_ERR_NOMEM;
+  const hipError_t e = src ? hipMemcpy(mem(c, id), src, bytes, hipMemcpyHostToDevice)
+                           : hipMemset(mem(c, id), 0, bytes);
+  return e == hipSuccess ? 0 : QH_ERR_FATAL;
 }
 
 QH_EXPORT int qh_ctx_new(qh_ctx **pctx, int device, void *stream) {
@@ -1376,13 +1331,12 @@ QH_EXPORT int qh_ctx_new(qh_ctx **pctx, int device, void *stream) {
   if (hipGetDeviceProperties(&prop, device) == hipSuccess &&
       prop.multiProcessorCount > 0)
     c->num_cus = prop.multiProcessorCount;
-  c->dec_kind = kDecPeek0;
+  c->dec_kind = kDecWindows;
 #if QH_DEV_KNOBS
   {  // decoder: the window decoder (QH_DECODER_WINDOWS, "peek11s") unless
      // qh_ctx_set_decoder picks another; in development builds
-     // QHUFF_DECODER=<variant name> selects any kPeekVariants entry (the
-     // development variants' host side is dev/patches/dev_variants_api.patch;
-     // an unknown name is reported and ignored), and the other QHUFF_*
+     // QHUFF_DECODER=<variant name> selects any kPeekVariants entry (an
+     // unknown name is reported and ignored), and the other QHUFF_*
      // variables set the development knobs.  The product library reads none
      // of them: its results and its kernels do not depend on the
      // environment (qh_ctx_set_option sets the tuning options explicitly).
@@ -1401,45 +1355,34 @@ QH_EXPORT int qh_ctx_new(qh_ctx **pctx, int device, void *stream) {
     bool known = !dv;
     for (int k = 0; dv && k < kNumPeek; ++k)
       if (strcmp(dv, kPeekVariants[k].name) == 0) {
-        c->dec_kind = kDecPeek0 + k;
+        c->dec_kind = k;
         known = true;
       }
-    if (!known && strcmp(dv, "fsm") && strcmp(dv, "lut") && strcmp(dv, "fsm2") && strcmp(dv, "run"))
+    if (!known)
       fprintf(stderr, "qhuff: QHUFF_DECODER=%s is not a decoder of this build; ignored\n", dv);
   }
 #endif
   // NULL selects the HIP default (null) stream, as HIP/ROCm libraries do.
   c->stream = (hipStream_t)stream;
   c->all_cus = stream_all_cus(c->stream, c->num_cus);
-  if (hipMalloc(&c->d_fsm, sizeof(kFsmPacked)) != hipSuccess ||
-      hipMalloc(&c->d_sym, sizeof(kSymPacked)) != hipSuccess ||
-      hipMalloc(&c->d_dtab, sizeof(DecTables)) != hipSuccess ||
-      hipMalloc(&c->d_stats2, 2 * sizeof(DevStats)) != hipSuccess ||
-      hipMalloc(&c->d_wcount, 8 * sizeof(uint32_t)) != hipSuccess)
-    return fail(QH_ERR_NOMEM);
-  if (hipMemcpy(c->d_fsm, kFsmPacked, sizeof(kFsmPacked),
-                hipMemcpyHostToDevice) != hipSuccess ||
-      !upload_dec_tables(c->d_dtab) ||
-      hipMemcpy(c->d_sym, kSymPacked, sizeof(kSymPacked),
-                hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(c->d_stats2, 0, 2 * sizeof(DevStats)) != hipSuccess ||
-      hipMemset(c->d_wcount, 0, 8 * sizeof(uint32_t)) != hipSuccess)
-    return fail(QH_ERR_FATAL);
-  c->d_stats = c->d_stats2;
+  const DecTables *const dt = dec_tables();
+  if (!dt) return fail(QH_ERR_FATAL);
+  int rv = 0;
+  if ((rv = upload(c, kBufSym, kSymPacked, sizeof(kSymPacked))) ||
+      (rv = upload(c, kBufDtab, dt, sizeof(DecTables))) ||
+      (rv = upload(c, kBufStats, nullptr, 2 * sizeof(DevStats))))
+    return fail(rv);
+  c->d_stats = mem<DevStats>(c, kBufStats);
   for (int k = 0; k < 5; ++k) {  // peek tables, W = 8 + k
     std::vector<uint32_t> t(1u << (8 + k));
     build_peek_table(t.data(), 8 + k);
-    if (hipMalloc(&c->d_peek[k], t.size() * 4) != hipSuccess) return fail(QH_ERR_NOMEM);
-    if (hipMemcpy(c->d_peek[k], t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(QH_ERR_FATAL);
+    if ((rv = upload(c, kBufPeek0 + k, t.data(), t.size() * 4))) return fail(rv);
   }
 #ifdef QH_DEV_VARIANTS
   for (int k = 0; k < 3; ++k) {  // pair tables, W = 12 + k
     std::vector<uint32_t> t(1u << (12 + k));
     build_pair_table(t.data(), 12 + k);
-    if (hipMalloc(&c->d_ptab[k], t.size() * 4) != hipSuccess) return fail(QH_ERR_NOMEM);
-    if (hipMemcpy(c->d_ptab[k], t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(QH_ERR_FATAL);
+    if ((rv = upload(c, kBufPtab0 + k, t.data(), t.size() * 4))) return fail(rv);
   }
 #endif
   *pctx = c;
@@ -1450,64 +1393,11 @@ QH_EXPORT void qh_ctx_del(qh_ctx *c) {
   if (!c) return;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  for (auto &e : c->events) {
-    hipEventDestroy(e.a);
-    hipEventDestroy(e.b);
-  }
-  for (auto e : c->pool) hipEventDestroy(e);
-  if (c->d_fsm) hipFree(c->d_fsm);
-  if (c->d_dtab) hipFree(c->d_dtab);
-  for (int k = 0; k < 5; ++k)
-    if (c->d_peek[k]) hipFree(c->d_peek[k]);
-  if (c->d_peekq) hipFree(c->d_peekq);
-  for (int k = 0; k < 3; ++k)
-    if (c->d_ptab[k]) hipFree(c->d_ptab[k]);
-  if (c->d_junk) hipFree(c->d_junk);
-  if (c->q_wbase) hipFree(c->q_wbase);
-  if (c->d_perm) hipFree(c->d_perm);
-  if (c->d_sym) hipFree(c->d_sym);
-  if (c->d_pair) hipFree(c->d_pair);
-  if (c->d_stats2) hipFree(c->d_stats2);
-  if (c->d_btot2) hipFree(c->d_btot2);
-  if (c->d_tile_state) hipFree(c->d_tile_state);
-  if (c->d_blk) hipFree(c->d_blk);
-  if (c->d_wcount) hipFree(c->d_wcount);
-  if (c->d_cwl) hipFree(c->d_cwl);
-  for (int k = 0; k < 4; ++k)
-    if (c->h_buf[k]) hipFree(c->h_buf[k]);
-  if (c->fr_buf) hipFree(c->fr_buf);
-  if (c->fr_lb) hipFree(c->fr_lb);
-  if (c->dn_buf) hipFree(c->dn_buf);
-  if (c->sec_buf) hipFree(c->sec_buf);
-  if (c->fr_h) hipHostFree(c->fr_h);
-  if (c->fr_ev) hipEventDestroy(c->fr_ev);
-  if (c->ll_buf) hipFree(c->ll_buf);
-  if (c->es_buf) hipFree(c->es_buf);
-  if (c->pw_buf) hipFree(c->pw_buf);
-  if (c->hp_buf) hipFree(c->hp_buf);
-  for (auto e : c->hp_ev) hipEventDestroy(e);
-  for (auto e : c->sp_ev) hipEventDestroy(e);
-  if (c->sp_buf) hipFree(c->sp_buf);
-  if (c->sp_dense) hipFree(c->sp_dense);
-  if (c->h_ends) hipHostFree(c->h_ends);
-  if (c->s_h2d) hipStreamDestroy(c->s_h2d);
-  if (c->s_d2h) hipStreamDestroy(c->s_d2h);
-  if (c->s_end) hipStreamDestroy(c->s_end);
-  if (c->hp_end_ev) hipEventDestroy(c->hp_end_ev);
-  if (c->hp_user_ev) hipEventDestroy(c->hp_user_ev);
-  if (c->es_ebuf) hipFree(c->es_ebuf);
-  if (c->es_loff) hipFree(c->es_loff);
-  if (c->s_ehint) (void)hipStreamSynchronize(c->s_ehint);
-  if (c->d_ehint) hipFree(c->d_ehint);
-  if (c->h_ehint) hipHostFree(c->h_ehint);
-  if (c->ehint_src) hipEventDestroy(c->ehint_src);
-  if (c->ehint_done) hipEventDestroy(c->ehint_done);
-  if (c->s_ehint) hipStreamDestroy(c->s_ehint);
-  if (c->es_h) hipHostFree(c->es_h);
-  if (c->es_ev) hipEventDestroy(c->es_ev);
-  if (c->d_ew) hipFree(c->d_ew);
-  if (c->d_sched) hipFree(c->d_sched);
-  if (c->d_srec) hipFree(c->d_srec);
+  for (hipStream_t s : c->owned_streams) (void)hipStreamSynchronize(s);
+  for (hipEvent_t e : c->owned_ev) hipEventDestroy(e);
+  HipAlloc a{c->stream};
+  for (qhs::Scratch &b : c->buf) qhs::release(a, b);
+  for (hipStream_t s : c->owned_streams) hipStreamDestroy(s);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1515,7 +1405,7 @@ QH_EXPORT void qh_ctx_del(qh_ctx *c) {
 QH_EXPORT int qh_ctx_set_decoder(qh_ctx *c, int kind) {
   if (!c) return QH_ERR_INVALID_ARGUMENT;
   if (kind == QH_DECODER_WINDOWS) {
-    c->dec_kind = kDecPeek0;
+    c->dec_kind = kDecWindows;
   } else if (kind == QH_DECODER_WAVES) {
     c->dec_kind = kDecWaves;
   } else if (kind == QH_DECODER_SORTED) {

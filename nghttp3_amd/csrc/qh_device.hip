@@ -17,10 +17,11 @@
 //   qh_k_lookup_tokens QPACK framing, validation and tokens
 //   qh_k_encsec_*      representation writer of whole field sections
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
-// Development variants (decoders fsm / fsm2 / lut / run / queue / other
-// peek widths and shapes, the chunk-engine and streaming encoders) build
-// only with -DQH_DEV_VARIANTS (make dev -> libqhuff_dev.so); the kernels
-// that exist only for them live outside the package, in dev/csrc (-I).
+// Development variants (the pair decoder, the segment encoder) build only
+// with -DQH_DEV_VARIANTS (make dev -> libqhuff_dev.so); the kernels that
+// exist only for them live outside the package, in dev/csrc (-I).  The older
+// variants (fsm / fsm2 / lut / run / queue decoders, the chunk-engine and
+// streaming encoders, the zero-copy host path) are in the history at 30ebdce.
 
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,7 @@
 
 #include "../../include/qhuff.h"
 #include "qh_tables.h"
+#include "qh_scratch.h"
 
 #define QH_VERSION "0.2.0"
 
@@ -49,20 +51,9 @@
 #include "qh_dec_common.inc"  // decode table blob, slot reservation
 #include "qh_check.inc"       // field name / value checks (device)
 #include "qh_sched.inc"       // batch-wide length-class schedule (QH_DECODER_SORTED)
-#ifdef QH_DEV_VARIANTS         // development variants (make dev): not shipped
-#include "qh_lane_dec.inc"   // (dev/csrc) decoder: 4-bit FSM, one string per lane
-#include "qh_lane_dec2.inc"  // decoder: 4-bit FSM, two strings per lane
-#include "qh_lut_dec.inc"    // decoder: 12-bit table, one string per lane
-#endif
 #include "qh_peek_dec.inc"   // decoders (windows: default; waves): W-bit peek table + leading-ones table
-#ifdef QH_DEV_VARIANTS
+#ifdef QH_DEV_VARIANTS         // development variants (make dev): not shipped
 #include "qh_pair_dec.inc"   // (dev/csrc) decoder: two codes per lookup, waves fed from a group queue
-#endif
-#ifdef QH_DEV_VARIANTS
-#include "qh_dec3.inc"       // decoder: plan + task-queue lanes
-#endif
-#ifdef QH_DEV_VARIANTS
-#include "qh_dec_q.inc"      // decoder: per-wave string queues
 #endif
 #include "qh_lane_enc.inc"   // encoder: lengths (stream, lanes), codes (lanes: the default)
 #include "qh_enc_waves.inc"   // encoder codes (QH_ENCODER_WAVES): per-wave chunks, LDS rings
@@ -70,7 +61,6 @@
 #include "qh_enc_region.inc"  // encoder codes over each window's region (QH_ENCODER_REGION, opt-in)
 #ifdef QH_DEV_VARIANTS
 #include "qh_enc_seg.inc"    // (dev/csrc) encoder, one pass over equal-size segments per lane
-#include "qh_enc_stream.inc" // encoder codes: streaming region rounds
 #endif
 #include "qh_synth.inc"      // synthetic inputs for bench/tests
 #include "qh_host.inc"   // host-memory decode: dense packing kernels

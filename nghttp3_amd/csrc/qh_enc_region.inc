@@ -125,34 +125,6 @@ __device__ __forceinline__ RgRegion rg_region(const uint8_t *src, uint64_t soff,
   return g;
 }
 
-// Four codes (table entries e: code16 << 16 | length) with padded lengths l
-// (code length + the pad after it) as one MSB-first value ch:cl of
-// l0 + .. + l3 bits (a byte outside the strings: entry 0, length 0).  With
-// codes of <= 12 bits and pads of <= 7 two codes fit a word.
-__device__ __forceinline__ void rg_quad(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3,
-                                        uint32_t l0, uint32_t l1, uint32_t l2, uint32_t &ch,
-                                        uint32_t &cl) {
-  const uint32_t c01 = (e0 & ~127u) | ((e1 & ~127u) >> l0);
-  const uint32_t c23 = (e2 & ~127u) | ((e3 & ~127u) >> l2);
-  const uint64_t t = ((uint64_t)c23 << 32) >> (l0 + l1);  // (l0 + l1 <= 38)
-  ch = c01 | (uint32_t)(t >> 32);
-  cl = (uint32_t)t;
-}
-
-// OR the lq-bit value ch:cl into the stage at bit `at` (stage-relative).
-__device__ __forceinline__ void rg_put(uint32_t *stage, uint32_t at, uint32_t ch, uint32_t cl,
-                                       uint32_t lq) {
-  uint32_t *w = stage + (at >> 5);
-  const uint32_t sh = at & 31u;
-  if (QH_RG_ABL & 1) {
-    if (ch == 0x12345u && cl == 0x777u && lq == 5u) *w = sh;
-    return;
-  }
-  if (lq) atomicOr(w, __builtin_amdgcn_alignbit(0u, ch, sh));
-  if (sh + lq > 32u) atomicOr(w + 1, __builtin_amdgcn_alignbit(ch, cl, sh));
-  if (sh + lq > 64u) atomicOr(w + 2, __builtin_amdgcn_alignbit(cl, 0u, sh));
-}
-
 // One code (any length) at stage bit `at`.
 __device__ __forceinline__ void rg_put1(uint32_t *stage, uint32_t at, uint2 f) {
   uint32_t *w = stage + (at >> 5);

@@ -332,14 +332,14 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
   const uint64_t o_in2 = al(ns * 4), o_eout = o_in2 + al(ns * 16);
   const uint64_t total = o_eout + al(ns * 16);
-  int rv = grow(c, &c->es_buf, &c->es_cap, total);
+  int rv = reserve(c, kBufEncSec, total);
   if (rv) return rv;
-  uint8_t *base = (uint8_t *)c->es_buf;
+  uint8_t *base = mem<uint8_t>(c, kBufEncSec);
   uint32_t *hlen = (uint32_t *)base;
   qhk::SpanIn *in2 = (qhk::SpanIn *)(base + o_in2);
   qhk::SpanOut *eout = (qhk::SpanOut *)(base + o_eout);
   const uint64_t lcap = nl != kLinesUnknown ? nl : c->es_nl_hint;
-  if ((rv = grow(c, &c->es_loff, &c->es_loff_cap, lcap * 8 + 64))) return rv;
+  if ((rv = reserve(c, kBufEncSecLoff, lcap * 8 + 64))) return rv;
   // the sections scan's tile states behind a header (word 0 the tile counter,
   // 1 the dst bytes of all sections, 2 the picked strings' bytes, 3 an
   // error, 4 look-back timeouts, 5 the line total), zeroed with one memset
@@ -351,7 +351,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   const int cgrid = chunk_grid(c, ns ? ns : 1, c->enc_bpc);
   const uint64_t hwords = kHdr + tps + (uint64_t)cgrid;
   if ((rv = ensure_tile_state(c, hwords * qhk::kScanTile))) return rv;
-  uint64_t *hdr = c->d_tile_state;
+  uint64_t *hdr = mem<uint64_t>(c, kBufTileState);
   unsigned long long *ctr = reinterpret_cast<unsigned long long *>(hdr + 2);  // picked bytes
   int32_t *err = reinterpret_cast<int32_t *>(hdr + 3);
   uint64_t *const btot = hdr + kHdr + tps;
@@ -377,7 +377,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
     hipLaunchKernelGGL(qhk::qh_k_encsec_size,
                        dim3((unsigned)((nb * qhk::kSecLanes + 255) / 256)), dim3(256), 0,
                        c->stream, e.lines, e.line_start, nb, e.pfx, (const qhk::SpanIn *)e.strs,
-                       ns, (const uint32_t *)hlen, (uint64_t *)c->es_loff, cap, sec, err,
+                       ns, (const uint32_t *)hlen, mem<uint64_t>(c, kBufEncSecLoff), cap, sec, err,
                        reinterpret_cast<unsigned long long *>(hdr + 5));
     QH_HIP(hipGetLastError());
     return 0;
@@ -391,29 +391,28 @@ int encsec_device(qh_ctx *c, EncSec &e) {
                        reinterpret_cast<unsigned long long *>(hdr + 4));
     QH_HIP(hipGetLastError());
   }
-  if (!c->es_h) {
-    QH_HIP(hipHostMalloc((void **)&c->es_h, 8 * sizeof(uint64_t)));
-    QH_HIP(hipEventCreateWithFlags(&c->es_ev, hipEventDisableTiming));
-  }
+  if (!c->es_ev && ((rv = reserve(c, kBufEncSecHost, 8 * sizeof(uint64_t), qhs::kExact)) ||
+                    (rv = make_event(c, &c->es_ev))))
+    return rv;
   // dst bytes, picked bytes, error, look-back timeouts, lines
-  QH_HIP(hipMemcpyAsync(c->es_h, hdr + 1, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  QH_HIP(hipMemcpyAsync(mem(c, kBufEncSecHost), hdr + 1, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipEventRecord(c->es_ev, c->stream));
   // The picked strings' codes do not wait for the host: they are queued
   // now into the picked-bytes scratch as it stands (sized by earlier calls),
   // and encoded again below only if this call's picked bytes outgrew it.
   // (The window encoder, the context's default, takes the count pass's
   // lengths; another configured encoder runs whole.)
-  const bool picked_path = (c->codes_kind == 0 || c->codes_kind == 4 || c->codes_kind == 5) && c->enc_kind == 0;
+  const bool picked_path = c->codes_kind == 0 || c->codes_kind == 4 || c->codes_kind == 5;
   auto encode_picked_strings = [&](uint64_t cap) -> int {
     if (!ns) return 0;
-    if (picked_path) return encode_picked(c, e.plain, in2, ns, cgrid, btot, (uint8_t *)c->es_ebuf, cap, eout);
-    return encode_device(c, e.plain, in2, ns, (uint8_t *)c->es_ebuf, cap, eout);
+    if (picked_path) return encode_picked(c, e.plain, in2, ns, cgrid, btot, mem<uint8_t>(c, kBufEncSecCodes), cap, eout);
+    return encode_device(c, e.plain, in2, ns, mem<uint8_t>(c, kBufEncSecCodes), cap, eout);
   };
-  const uint64_t spec_cap = c->es_ecap;
+  const uint64_t spec_cap = c->buf[kBufEncSecCodes].cap;
   if (spec_cap >= 64 && (rv = encode_picked_strings(spec_cap))) return rv;
   QH_HIP(hipEventSynchronize(c->es_ev));
   uint64_t h[5];
-  memcpy(h, c->es_h, sizeof(h));
+  memcpy(h, mem(c, kBufEncSecHost), sizeof(h));
   if ((int32_t)(h[2] & 0xFFFFFFFFu)) return QH_ERR_INVALID_ARGUMENT;
   if (h[3]) {
     fprintf(stderr, "qhuff: section scan look-back timed out\n");
@@ -423,7 +422,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   e.nlines = nl;
   c->es_nl_hint = std::max<uint64_t>(c->es_nl_hint, nl);
   if (nl > lcap) {  // (more lines than the offsets had room for: size again)
-    if ((rv = grow(c, &c->es_loff, &c->es_loff_cap, nl * 8 + 64)) || (rv = size_pass(nl))) return rv;
+    if ((rv = reserve(c, kBufEncSecLoff, nl * 8 + 64)) || (rv = size_pass(nl))) return rv;
   }
   e.need = h[0];
   if (e.need > e.dst_cap) return QH_ERR_NOMEM;
@@ -434,7 +433,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
     // eout; grow once they are done, pick again for the lengths and block
     // totals, and encode again)
     QH_HIP(hipStreamSynchronize(c->stream));
-    if ((rv = grow(c, &c->es_ebuf, &c->es_ecap, picked + 64))) return rv;
+    if ((rv = reserve(c, kBufEncSecCodes, picked + 64))) return rv;
     if (spec_cap >= 64 && ns) {
       // (the pick adds every picked string's bytes to ctr again: zeroed with
       // the block totals, so the device's picked-bytes total stays right)
@@ -448,8 +447,8 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   Timed t(c, "qh_k_encsec_write");
   hipLaunchKernelGGL(qhk::qh_k_encsec_write, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
                      c->stream, e.plain, (const qhk::SpanIn *)e.strs, (const uint32_t *)hlen,
-                     (const uint8_t *)c->es_ebuf, (const qhk::SpanOut *)eout, e.lines,
-                     e.line_start, nb, nl, e.pfx, (const uint64_t *)c->es_loff,
+                     mem<const uint8_t>(c, kBufEncSecCodes), (const qhk::SpanOut *)eout, e.lines,
+                     e.line_start, nb, nl, e.pfx, mem<const uint64_t>(c, kBufEncSecLoff),
                      (const qhk::SpanOut *)sec, e.dst);
   QH_HIP(hipGetLastError());
   return 0;

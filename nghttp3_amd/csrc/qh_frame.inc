@@ -467,36 +467,29 @@ int frame_count_launch(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, 
   f.tot[0] = f.tot[1] = f.tot[2] = 0;
   f.slots = f.nlong = 0;
   if (n == 0) return 0;
-  if (!c->fr_h) {
-    QH_HIP(hipHostMalloc((void **)&c->fr_h, 8 * sizeof(uint64_t)));
-    QH_HIP(hipEventCreateWithFlags(&c->fr_ev, hipEventDisableTiming));
-  }
+  int rv = 0;
+  if (!c->fr_ev && ((rv = reserve(c, kBufFrameHost, 8 * sizeof(uint64_t), qhs::kExact)) ||
+                    (rv = make_event(c, &c->fr_ev))))
+    return rv;
   const uint64_t grid = (n + qhk::kFrCount - 1) / qhk::kFrCount;
   if (grid > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
-  int rv = 0;
   c->last_n = n;  // (the count kernel zeroes the stats)
   // the four counts per block, then kFrLines line starts per block
   const size_t cnt_b = 4 * n * sizeof(qhk::SpanOut);
-  if ((rv = grow(c, &c->fr_buf, &c->fr_cap, cnt_b + (size_t)qhk::kFrLines * 2 * n + 64))) return rv;
+  if ((rv = reserve(c, kBufFrame, cnt_b + (size_t)qhk::kFrLines * 2 * n + 64))) return rv;
   // the look-back regions (two: this call's, zeroed by the previous call's
   // count, and the next call's, zeroed by this one)
   const uint64_t words = qhk::kFrHdr + 4 * grid;
-  if (words > c->fr_lb_words) {
-    if (c->fr_lb) {
-      QH_HIP(hipStreamSynchronize(c->stream));
-      hipFree(c->fr_lb);
-    }
-    c->fr_lb = nullptr;
-    c->fr_lb_words = 0;
-    uint64_t cap = 1024;
-    while (cap < words) cap *= 2;
-    if (cap > 0xffffffffull) return QH_ERR_INVALID_ARGUMENT;
-    QH_HIP(hipMalloc(&c->fr_lb, 2 * cap * sizeof(uint64_t)));
-    QH_HIP(hipMemsetAsync(c->fr_lb, 0, 2 * cap * sizeof(uint64_t), c->stream));
-    c->fr_lb_words = cap;
-  }
-  uint64_t *const lb = c->fr_lb + c->fr_par * c->fr_lb_words;
-  uint64_t *const lz = c->fr_lb + (c->fr_par ^ 1) * c->fr_lb_words;
+  if (words > 0x80000000ull) return QH_ERR_INVALID_ARGUMENT;  // (a half's words: 32 bits)
+  bool fresh = false;
+  if ((rv = reserve(c, kBufFrameLb, 2 * words * sizeof(uint64_t), qhs::Policy{2 * 1024 * sizeof(uint64_t)},
+                    &fresh)))
+    return rv;
+  const qhs::Scratch &lbs = c->buf[kBufFrameLb];
+  if (fresh) QH_HIP(hipMemsetAsync(lbs.p, 0, lbs.cap, c->stream));
+  const uint64_t lb_words = lbs.cap / (2 * sizeof(uint64_t));
+  uint64_t *const lb = mem<uint64_t>(c, kBufFrameLb) + c->fr_par * lb_words;
+  uint64_t *const lz = mem<uint64_t>(c, kBufFrameLb) + (c->fr_par ^ 1) * lb_words;
   c->fr_par ^= 1;
   {
     Timed t(c, "qh_k_frame_count");
@@ -506,21 +499,21 @@ int frame_count_launch(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, 
     const bool xheads = grid >= 256 && c->num_cus == 256 && c->all_cus;
     const uint64_t lgrid = xheads ? (grid + 7) / 8 * 8 : grid;
     hipLaunchKernelGGL(qhk::qh_k_frame_count, dim3((unsigned)lgrid), dim3(64), 0, c->stream, src,
-                       (const qhk::SpanIn *)blocks, (uint64_t)n, opts, (qhk::SpanOut *)c->fr_buf,
-                       f.status, f.pfx, lb, lz, (uint32_t)c->fr_lb_words, c->d_stats,
-                       (uint16_t *)((uint8_t *)c->fr_buf + cnt_b),
+                       (const qhk::SpanIn *)blocks, (uint64_t)n, opts, mem<qhk::SpanOut>(c, kBufFrame),
+                       f.status, f.pfx, lb, lz, (uint32_t)lb_words, c->d_stats,
+                       (uint16_t *)(mem<uint8_t>(c, kBufFrame) + cnt_b),
                        xheads ? 8u : 1u);
     QH_HIP(hipGetLastError());
   }
   // the four totals, look-back timeouts, long Huffman strings, totals in
-  QH_HIP(hipMemcpyAsync(c->fr_h, lb + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  QH_HIP(hipMemcpyAsync(mem(c, kBufFrameHost), lb + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipEventRecord(c->fr_ev, c->stream));
   return 0;
 }
 int frame_count_wait(qh_ctx *c, size_t n, FrameOut &f) {
   if (n == 0) return 0;
   QH_HIP(hipEventSynchronize(c->fr_ev));
-  const uint64_t *const h = c->fr_h;
+  const uint64_t *const h = mem<const uint64_t>(c, kBufFrameHost);
   if (h[4] || h[6] != 1) {  // a look-back gave up, or a tile was never taken: the offsets are wrong
     fprintf(stderr, "qhuff: framing look-back timed out (%llu waves, totals %s)\n",
             (unsigned long long)h[4], h[6] == 1 ? "in" : "missing");
@@ -556,10 +549,10 @@ int frame_write(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, size_t 
   if (grid > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
   Timed t(c, "qh_k_frame_write");
   hipLaunchKernelGGL(qhk::qh_k_frame_write_lines, dim3((unsigned)grid), dim3(256), 0, c->stream, src,
-                     (const qhk::SpanIn *)blocks, (uint64_t)n, opts, (const qhk::SpanOut *)c->fr_buf,
+                     (const qhk::SpanIn *)blocks, (uint64_t)n, opts, mem<const qhk::SpanOut>(c, kBufFrame),
                      (const int32_t *)f.status, f.lines, f.spans, f.huff, f.aux, f.line_start,
                      f.span_start,
-                     (const uint16_t *)((const uint8_t *)c->fr_buf + 4 * n * sizeof(qhk::SpanOut)),
+                     (const uint16_t *)(mem<const uint8_t>(c, kBufFrame) + 4 * n * sizeof(qhk::SpanOut)),
                      (uint64_t)f.lines_cap, (uint64_t)f.spans_cap,
                      f.huff ? (uint64_t)f.huff_cap : ~0ull);
   QH_HIP(hipGetLastError());

@@ -202,10 +202,10 @@ struct SecLayout {
   uint64_t cap = 0;
 };
 int sec_layout(qh_ctx *c, uint64_t cap, bool verdicts, SecLayout &L) {
-  const int rv = grow(c, &c->sec_buf, &c->sec_cap,
-                      cap * (sizeof(qh_span_in) + sizeof(qh_span_out) + sizeof(uint64_t) + 1) + 512);
+  const int rv = reserve(c, kBufSec,
+                         cap * (sizeof(qh_span_in) + sizeof(qh_span_out) + sizeof(uint64_t) + 1) + 512);
   if (rv) return rv;
-  L.huff = reinterpret_cast<qh_span_in *>(c->sec_buf);
+  L.huff = mem<qh_span_in>(c, kBufSec);
   L.hout = reinterpret_cast<qh_span_out *>(L.huff + cap);
   L.aux = reinterpret_cast<uint64_t *>(L.hout + cap);
   L.hverdict = verdicts ? reinterpret_cast<int8_t *>(L.aux + cap) : nullptr;
@@ -255,10 +255,10 @@ int sections_finish(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, siz
     // [0]: carry in, [1]: carry out, the groups' decoded bytes, then the
     // slots (+16: dense_tile_copy loads 16 bytes at a short string's start)
     const size_t st_b = ((2 + groups) * sizeof(uint64_t) + 255) & ~(size_t)255;
-    if ((rv = grow(c, &c->dn_buf, &c->dn_cap, st_b + f.slots + 16))) return rv;
-    unsigned long long *state = (unsigned long long *)c->dn_buf;
-    btot = (uint64_t *)c->dn_buf + 2;
-    dec_dst = (uint8_t *)c->dn_buf + st_b;
+    if ((rv = reserve(c, kBufDense, st_b + f.slots + 16))) return rv;
+    unsigned long long *state = mem<unsigned long long>(c, kBufDense);
+    btot = mem<uint64_t>(c, kBufDense) + 2;
+    dec_dst = mem<uint8_t>(c, kBufDense) + st_b;
     dec_cap = f.slots;
     if (!pk->carry_in) {
       QH_HIP(hipMemsetAsync(state, 0, sizeof(uint64_t), c->stream));
@@ -304,10 +304,10 @@ int sections_finish(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, siz
 // packing kernel wrote nothing at or past dst_cap.
 int packed_need(qh_ctx *c, const SecPack &pk, qh_sections *s) {
   if (!s->nspans) return 0;
-  QH_HIP(hipMemcpyAsync(c->fr_h + 7, pk.carry_out, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  QH_HIP(hipMemcpyAsync(mem<uint64_t>(c, kBufFrameHost) + 7, pk.carry_out, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipEventRecord(c->fr_ev, c->stream));
   QH_HIP(hipEventSynchronize(c->fr_ev));
-  s->dst_need = c->fr_h[7];
+  s->dst_need = mem<const uint64_t>(c, kBufFrameHost)[7];
   return s->dst_need > s->dst_cap ? QH_ERR_NOMEM : 0;
 }
 
@@ -551,12 +551,13 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
   qh_section_prefix *d_pf = s->prefixes ? (qh_section_prefix *)((uint8_t *)d_st + 3 * st_b) : nullptr;
   unsigned long long *d_carry = (unsigned long long *)((uint8_t *)d_st + 3 * st_b + pf_b);  // [0..nsl]
   const uint64_t dcap = std::min<uint64_t>(s->dst_cap, block_bytes * 8 / 5);
-  if ((rv = grow(c, &c->sp_dense, &c->sp_dense_cap, dcap + 16))) return rv;
-  if ((rv = grow(c, &c->sp_buf, &c->sp_cap, std::max<uint64_t>(c->sp_hint, 1u << 20)))) return rv;
-  uint8_t *d_dense = (uint8_t *)c->sp_dense;
+  if ((rv = reserve(c, kBufSliceDense, dcap + 16))) return rv;
+  if ((rv = reserve(c, kBufSlice, std::max<uint64_t>(c->sp_hint, 1u << 20)))) return rv;
+  uint8_t *d_dense = mem<uint8_t>(c, kBufSliceDense);
+  unsigned long long *const h_ends = mem<unsigned long long>(c, kBufEnds);
   while (c->sp_ev.size() < nsl) {
     hipEvent_t e = nullptr;
-    QH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if ((rv = make_event(c, &e))) return rv;
     c->sp_ev.push_back(e);
   }
   QH_HIP(hipMemsetAsync(d_carry, 0, 8, c->stream));
@@ -585,10 +586,10 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
       const SecSlice &x = sl[k];
       hipEvent_t ev = c->sp_ev[k];
       QH_HIP(hipStreamWaitEvent(c->s_end, ev, 0));
-      QH_HIP(hipMemcpyAsync(c->h_ends, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->s_end));
+      QH_HIP(hipMemcpyAsync(h_ends, d_carry + k + 1, 8, hipMemcpyDeviceToHost, c->s_end));
       QH_HIP(hipEventRecord(c->hp_end_ev, c->s_end));
       QH_HIP(hipEventSynchronize(c->hp_end_ev));
-      const uint64_t end = std::min<uint64_t>(c->h_ends[0], dcap);
+      const uint64_t end = std::min<uint64_t>(h_ends[0], dcap);
       QH_HIP(hipStreamWaitEvent(c->s_d2h, ev, 0));
       auto back = [&](void *h, const void *dv, size_t b) -> int {
         if (h && b) QH_HIP(hipMemcpyAsync(h, dv, b, hipMemcpyDeviceToHost, c->s_d2h));
@@ -659,7 +660,7 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
     take(3, s->verdict ? ns : 0);
     take(4, s->token ? ns * sizeof(int32_t) : 0);
     arena_all += need;
-    if (arena + need > c->sp_cap) {
+    if (arena + need > c->buf[kBufSlice].cap) {
       // wait until the earlier slices' copies out of the arena are done
       {
         std::unique_lock<std::mutex> g(mu);
@@ -670,10 +671,10 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
         rv = QH_ERR_FATAL;
         break;
       }
-      if ((rv = grow(c, &c->sp_buf, &c->sp_cap, need))) break;
+      if ((rv = reserve(c, kBufSlice, need))) break;
       arena = 0;
     }
-    uint8_t *d = (uint8_t *)c->sp_buf + arena;
+    uint8_t *d = mem<uint8_t>(c, kBufSlice) + arena;
     arena += need;
     qh_sections ds = *s;
     ds.lines = (qh_field_line *)(d + off[0]);

@@ -884,8 +884,9 @@ def test_encode_dst_cap_too_small(codec, corpus):
         assert d[o[j]:o[j] + l[j]].tobytes() == want
 
 
-# The two shipped decoders (qh_ctx_set_decoder); the development variants
-# (make dev) are timed by dev/scripts/dec_variants.py, not shipped.
+# The shipped decoders (qh_ctx_set_decoder); make dev adds the pair decoder
+# and the measurement entries of kPeekVariants (dev/scripts/dec_variants.py),
+# not shipped.  The older variants are in the history at 30ebdce.
 DECODERS = ["windows", "waves", "sorted"]
 # (development: QHUFF_LIB=nghttp3_amd/lib/libqhuff_dev.so QH_TEST_DEV_DECODERS=
 # peek11su,... adds those variants of the development build to these tests)
