@@ -224,10 +224,14 @@ QH_EXPORT int qh_ctx_set_encoder(qh_ctx *ctx, int kind);
  * QH_OPT_SECTIONS_SLICE_BLOCKS: header blocks per slice of the pipelined
  *   host-memory qh_decode_sections_batch (QH_SECTIONS_PACKED); 0 (default)
  *   lets the library choose.  Any value gives the same results.
+ * QH_OPT_EMIT_LONG_MIN: qh_emit_fields_batch copies a name or value of at
+ *   least `value` bytes with a wave instead of a lane; 0 (default) lets the
+ *   library choose (else 16 .. 2^30).
  * No reference counterpart (the reference codec has no batch kernels). */
 #define QH_OPT_LONG_MIN 1
 #define QH_OPT_LENS_LANE_PASS 2
 #define QH_OPT_SECTIONS_SLICE_BLOCKS 3
+#define QH_OPT_EMIT_LONG_MIN 4
 QH_EXPORT int qh_ctx_set_option(qh_ctx *ctx, int option, int64_t value);
 QH_EXPORT void *qh_ctx_stream(qh_ctx *ctx);
 /* Wait for all work queued on the context's stream. */
@@ -317,7 +321,8 @@ QH_EXPORT int qh_synth_fill(qh_ctx *ctx, uint64_t seed, uint64_t first,
  * into field lines plus (off, len, flags) string spans, ready for
  * qh_decode_batch (pass only the spans with QH_SPAN_HUFFMAN; the others are
  * raw octets).  Indices are returned as encoded (static, base-relative or
- * post-base); resolving them against the tables is the QPACK layer's job.
+ * post-base); qh_qpack_emit_fields / qh_emit_fields_batch below resolve them
+ * against the static table and a dynamic table state.
  * Replaces the framing of nghttp3_qpack_decoder_read_request
  * (lib/nghttp3_qpack.c:3347-3800) and nghttp3_qpack_decoder_read_encoder
  * (:2815-3150) around the per-string Huffman calls (:2737-2763). */
@@ -626,6 +631,158 @@ QH_EXPORT int32_t qh_qpack_lookup_token(const uint8_t *name, size_t namelen);
 QH_EXPORT int qh_lookup_tokens_batch(qh_ctx *ctx, const uint8_t *src,
                                      const qh_span_in *in, size_t n,
                                      int32_t *token, int where);
+
+/* ---- The decoder's dynamic table and field emission ---------------------
+ * What nghttp3_qpack_decoder_read_request hands its caller after the steps
+ * above: a list of (name, value, token, flags) per field section, every
+ * index resolved against the static table and a dynamic table state.
+ *
+ * The dynamic table (host C, csrc/qh_emit.c) replaces the decoder side of
+ * nghttp3_qpack_decoder_read_encoder's effects: set_max_dtable_capacity
+ * (lib/nghttp3_qpack.c:3159-3185), rel2abs (:3952-3969), the inserts
+ * (:3187-3306) and the eviction of context_dtable_add (:2071-2127).  It is
+ * kept as an append-only log: entry a (absolute index) is record
+ * entries[ent_base + a], its name and value bytes [name_off, +name_len) and
+ * [value_off, +value_len) of the byte log.  Entries and bytes are only ever
+ * appended, so a view (one table state) taken earlier stays valid after
+ * later qh_dtable_apply calls, and `entries` / `bytes` prefixes uploaded
+ * earlier stay valid on the device (the arrays themselves may move when
+ * they grow: read the pointers again after an apply). */
+typedef struct qh_dyn_entry { /* 32 B */
+  uint64_t name_off, value_off;
+  uint32_t name_len, value_len;
+  int32_t token; /* qh_qpack_lookup_token(name) at insert */
+  uint32_t reserved;
+} qh_dyn_entry;
+
+typedef struct qh_dtable_view { /* one table state, 40 B */
+  int64_t ent_base;      /* entry a is entries[ent_base + a]              */
+  uint64_t live_lo;      /* lowest absolute index not evicted             */
+  uint64_t insert_count; /* next_absidx (qpack.c:2787-2798: an index is
+                            valid iff live_lo <= a < insert_count)        */
+  uint64_t max_entries;  /* hard_max_dtable_capacity / 32 (:3915-3950)    */
+  uint64_t reserved;
+} qh_dtable_view;
+
+typedef struct qh_dtable qh_dtable;
+
+/* A table whose hard maximum capacity, and initial capacity, is hard_max
+ * (nghttp3_qpack_decoder_init + the CLI's set_max_dtable_capacity). */
+QH_EXPORT int qh_dtable_new(qh_dtable **pdt, uint64_t hard_max);
+QH_EXPORT void qh_dtable_del(qh_dtable *dt);
+/* Applies encoder-stream instructions as qh_qpack_scan_encoder_stream wrote
+ * them (insts, spans; string k is src[spans[k].off, +len), or, if
+ * spans[k].flags has QH_SPAN_HUFFMAN, the decoded bytes dec[strs[k].off,
+ * +strs[k].len) -- decoded by the caller with the scalar drop-in or
+ * qh_decode_batch; dec / strs may be NULL when no string is Huffman-coded).
+ * Returns 0, or QH_ERR_QPACK_ENCODER_STREAM_ERROR at the first failing
+ * instruction with the earlier ones applied: a capacity above the hard
+ * maximum (:3163-3165), an entry larger than the capacity (:2085-2087 via
+ * :3187-3306), a relative index that is not live or a static index >= 99
+ * (:3952-3969).  QH_ERR_NOMEM when the log cannot grow. */
+QH_EXPORT int qh_dtable_apply(qh_dtable *dt, const qh_field_line *insts,
+                              size_t ninsts, const uint8_t *src,
+                              const qh_span_in *spans, const uint8_t *dec,
+                              const qh_span_out *strs);
+/* The current state, and the logs (*n: records / bytes so far). */
+QH_EXPORT int qh_dtable_get_view(const qh_dtable *dt, qh_dtable_view *view);
+QH_EXPORT const qh_dyn_entry *qh_dtable_entries(const qh_dtable *dt, size_t *n);
+QH_EXPORT const uint8_t *qh_dtable_bytes(const qh_dtable *dt, size_t *n);
+
+/* Where a field's name / value bytes are. */
+#define QH_IN_SRC 0    /* raw string in the block bytes (off into src)     */
+#define QH_IN_DST 1    /* decoded Huffman string (off into sections dst)   */
+#define QH_IN_STATIC 2 /* off = static index (qh_qpack_static_entry)       */
+#define QH_IN_DYN 3    /* off into the dynamic table's byte log            */
+#define QH_IN_OUT 4    /* materialised: off into qh_emit.out               */
+
+typedef struct qh_field { /* 32 B, one per emitted field line */
+  uint64_t name_off, value_off;
+  uint32_t name_len, value_len;
+  int32_t token; /* nv->token, qpack.c:4028, :4067, :4090, :4130 */
+  uint8_t name_where, value_where; /* QH_IN_* */
+  uint8_t flags; /* QH_FL_NEVER (NGHTTP3_NV_FLAG_NEVER_INDEX) */
+  uint8_t reserved;
+} qh_field;
+
+#define QH_EMIT_BLOCKED 1 /* status: Required Insert Count > insert_count,
+                             qpack.c:3428-3433 */
+#define QH_EMIT_QIF 0x1u  /* opts: out is QIF text, name TAB value LF per
+                             field and one more LF per emitted block
+                             (examples/qpack_decode.cc:179-190) */
+
+/* Field emission: replaces the prefix handling of read_request
+ * (reconstruct_ricnt qpack.c:3915-3950, Base :3414-3422, the blocked
+ * verdict :3428-3433), brel2abs / pbrel2abs (:3971-4017) and the emit_*
+ * functions (:4020-4136) for the blocks of a finished
+ * qh_decode_sections_batch result `s` (prefixes given; src and blocks as in
+ * that call).  Block b is decoded against views[block_view[b]] (views[0]
+ * when block_view is NULL; no dynamic table -- hard maximum 0, insert count
+ * 0 -- when views is NULL), whose entries are dyn_entries[ent_base + a] and
+ * whose bytes are in dyn_bytes.  sel lists the blocks to emit, each at most
+ * once (NULL: all, nsel = nblocks); every output is indexed by position in
+ * sel.  Per selected block, in the reference's order:
+ *   1. the prefix: a Required Insert Count that does not reconstruct, or a
+ *      negative Base, gives -401 whatever the framing status is (a block
+ *      whose prefix did not parse has an all-zero prefix and passes);
+ *   2. ricnt > insert_count: QH_EMIT_BLOCKED, no fields -- also when the
+ *      block's lines hold a framing or Huffman error, which the reference
+ *      has not read yet;
+ *   3. a sections status of -401 stays;
+ *   4. status 0: every line's index is resolved (static < 99; base-relative
+ *      base >= idx + 1; absidx < ricnt; live); the first failure gives -401
+ *      and no fields, else one qh_field per line: name and token from the
+ *      entry (indexed and name-reference lines; a static entry's token is
+ *      its name's) or from strs / token of the line's name, value from the
+ *      entry (indexed lines) or strs of the line's value; a literal string
+ *      is QH_IN_DST if its span has QH_SPAN_HUFFMAN, else QH_IN_SRC;
+ *      QH_FL_NEVER is carried over, indexed lines get 0 (:4029);
+ *   5. -109: the reference validates an index as it reads it, before the
+ *      value's length (:3537-3542), so an invalid index before the oversize
+ *      string, or in the cut line itself, makes the verdict -401.
+ * status[p] is 0, QH_EMIT_BLOCKED or the error; ricnt[p] (optional) the
+ * reconstructed Required Insert Count (0 when it does not reconstruct);
+ * fields [field_start[p], field_start[p + 1]) are block p's (empty for a
+ * failed or blocked block).  With out != NULL every field's name and value
+ * bytes are copied back to back into out in block, line, name-then-value
+ * order (with QH_EMIT_QIF as QIF text) and the records say QH_IN_OUT;
+ * out_blocks[p] (optional) is block p's bytes in out.  nfields, out_need
+ * (the bytes out needs under opts, whether or not out is given) and
+ * nblocked are filled in; when fields_cap or out_cap (out != NULL) is too
+ * small the call returns QH_ERR_NOMEM with those totals exact, status and
+ * ricnt written, nothing written to fields or out, and field_start /
+ * out_blocks unspecified.
+ * QH_ERR_INVALID_ARGUMENT: unknown opts bits, s->prefixes == NULL,
+ * block_view without views.
+ * qh_qpack_emit_fields is host C over host pointers; qh_emit_fields_batch
+ * is the same over pointers in HBM (where must be QH_WHERE_DEVICE; `s` and
+ * `e` themselves are host structs of device pointers), asynchronous on the
+ * context stream after one host wait for the totals. */
+typedef struct qh_emit {
+  qh_field *fields;
+  size_t fields_cap;     /* >= s->nlines always suffices */
+  uint32_t *field_start; /* nsel + 1 */
+  int32_t *status;       /* nsel */
+  uint64_t *ricnt;       /* nsel, optional */
+  uint8_t *out;          /* optional */
+  uint64_t out_cap;
+  qh_span_in *out_blocks; /* nsel, optional */
+  /* filled in by the call */
+  uint64_t nfields, out_need, nblocked;
+} qh_emit;
+
+QH_EXPORT int qh_qpack_emit_fields(
+    const uint8_t *src, const qh_span_in *blocks, size_t nblocks,
+    const qh_sections *s, const qh_dtable_view *views,
+    const uint32_t *block_view, const qh_dyn_entry *dyn_entries,
+    const uint8_t *dyn_bytes, const uint32_t *sel, size_t nsel, uint32_t opts,
+    qh_emit *e);
+QH_EXPORT int qh_emit_fields_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *blocks, size_t nblocks,
+    const qh_sections *s, const qh_dtable_view *views,
+    const uint32_t *block_view, const qh_dyn_entry *dyn_entries,
+    const uint8_t *dyn_bytes, const uint32_t *sel, size_t nsel, uint32_t opts,
+    qh_emit *e, int where);
 
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);

@@ -35,8 +35,12 @@ QH_ENCODER_REGION = 4
 QH_OPT_LONG_MIN = 1
 QH_OPT_LENS_LANE_PASS = 2
 QH_OPT_SECTIONS_SLICE_BLOCKS = 3
+QH_OPT_EMIT_LONG_MIN = 4
 QH_SECTIONS_DTABLE0 = 0x1
 QH_SECTIONS_PACKED = 0x2
+QH_IN_SRC, QH_IN_DST, QH_IN_STATIC, QH_IN_DYN, QH_IN_OUT = range(5)
+QH_EMIT_BLOCKED = 1
+QH_EMIT_QIF = 0x1
 
 NGHTTP3_QPACK_HUFFMAN_FLAG_ACCEPTED = 0x01
 NGHTTP3_QPACK_HUFFMAN_FLAG_SYM = 0x02
@@ -66,6 +70,35 @@ class qh_batch_stats(ctypes.Structure):
         ("lane_steps", ctypes.c_uint64),
         ("wave_steps", ctypes.c_uint64),
     ]
+
+
+class qh_dyn_entry(ctypes.Structure):
+    _fields_ = [("name_off", ctypes.c_uint64), ("value_off", ctypes.c_uint64),
+                ("name_len", ctypes.c_uint32), ("value_len", ctypes.c_uint32),
+                ("token", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class qh_dtable_view(ctypes.Structure):
+    _fields_ = [("ent_base", ctypes.c_int64), ("live_lo", ctypes.c_uint64),
+                ("insert_count", ctypes.c_uint64), ("max_entries", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64)]
+
+
+class qh_field(ctypes.Structure):
+    _fields_ = [("name_off", ctypes.c_uint64), ("value_off", ctypes.c_uint64),
+                ("name_len", ctypes.c_uint32), ("value_len", ctypes.c_uint32),
+                ("token", ctypes.c_int32), ("name_where", ctypes.c_uint8),
+                ("value_where", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8)]
+
+
+class qh_emit(ctypes.Structure):
+    """include/qhuff.h qh_emit (outputs of qh_qpack_emit_fields / qh_emit_fields_batch)."""
+    _fields_ = [("fields", ctypes.c_void_p), ("fields_cap", ctypes.c_size_t),
+                ("field_start", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("ricnt", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_cap", ctypes.c_uint64),
+                ("out_blocks", ctypes.c_void_p), ("nfields", ctypes.c_uint64),
+                ("out_need", ctypes.c_uint64), ("nblocked", ctypes.c_uint64)]
 
 
 class nghttp3_qpack_huffman_decode_context(ctypes.Structure):
@@ -124,6 +157,15 @@ EXPORTED_FUNCTIONS = (
     "qh_qpack_write_literal",
     "qh_qpack_literal_bound",
     "qh_qpack_write_sections",
+    # the decoder's dynamic table and field emission (csrc/qh_emit.c, csrc/qh_emit.inc)
+    "qh_dtable_new",
+    "qh_dtable_del",
+    "qh_dtable_apply",
+    "qh_dtable_get_view",
+    "qh_dtable_entries",
+    "qh_dtable_bytes",
+    "qh_qpack_emit_fields",
+    "qh_emit_fields_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

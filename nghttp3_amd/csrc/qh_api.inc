@@ -32,6 +32,8 @@ enum BufId {
   kBufEncSec,       // qh_encode_sections_batch: per-string scratch
   kBufEncSecCodes,  // ... the picked Huffman strings
   kBufEncSecLoff,   // ... per-line offsets
+  kBufEmit,         // qh_emit_fields_batch: per-block counts, per-line records, long strings
+  kBufEmitStatic,   // ... the static table: 99 records, then their bytes
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage0,     // host-mode staging: src, spans in, dst, spans out
   kBufPinned0 = kBufStage0 + 4,  // from here on: pinned host memory
@@ -39,6 +41,7 @@ enum BufId {
   kBufFrameHost,   // framing's totals read back (8 words)
   kBufEnds,        // host pipelines: a slice's dense end (64 words)
   kBufEncSecHost,  // the sections encoder's totals read back (8 words)
+  kBufEmitHost,    // field emission's totals read back (8 words)
   kNumBuf
 };
 
@@ -111,6 +114,7 @@ struct qh_ctx {
   uint64_t sp_hint = 0;
   uint64_t es_nl_hint = 0;  // the most lines a call has seen (kBufEncSecLoff's capacity)
   hipEvent_t es_ev = nullptr;  // recorded after the copy into kBufEncSecHost
+  uint32_t emit_long_min = 0;  // QH_OPT_EMIT_LONG_MIN (0: kEmitLongMin, qh_emit.inc)
   // fused encoder (qh_enc_fused.inc): the halves of kBufEw are used by
   // alternate calls
   int ew_par = 0;
@@ -1448,6 +1452,10 @@ QH_EXPORT int qh_ctx_set_option(qh_ctx *c, int option, int64_t value) {
     case QH_OPT_SECTIONS_SLICE_BLOCKS:
       if (value < 0) return QH_ERR_INVALID_ARGUMENT;
       c->sec_slice_blocks = (uint64_t)value;
+      return 0;
+    case QH_OPT_EMIT_LONG_MIN:
+      if (value != 0 && (value < 16 || value > (1ll << 30))) return QH_ERR_INVALID_ARGUMENT;
+      c->emit_long_min = (uint32_t)value;
       return 0;
     default:
       return QH_ERR_INVALID_ARGUMENT;

@@ -16,6 +16,7 @@
 //   qh_k_frame_*, qh_k_sections_post, qh_k_check_fields,
 //   qh_k_lookup_tokens QPACK framing, validation and tokens
 //   qh_k_encsec_*      representation writer of whole field sections
+//   qh_k_emit_*        field emission: index resolution, names and values gathered
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
 // Development variants (the pair decoder, the segment encoder) build only
 // with -DQH_DEV_VARIANTS (make dev -> libqhuff_dev.so); the kernels that
@@ -69,4 +70,5 @@
 #include "qh_frame.inc"     // QPACK field-section framing on the device
 #include "qh_sections.inc"  // whole field sections: frame -> decode -> fold / check / tokens
 #include "qh_enc_sections.inc"  // whole field sections out: count -> pick -> encode -> write
+#include "qh_emit.inc"          // decoded fields: resolve indices -> scan -> gather names and values
 

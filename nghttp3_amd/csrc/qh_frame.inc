@@ -98,6 +98,7 @@ __device__ __forceinline__ void frame_init(scan_out &o, uint32_t opts) {
   o.nlong = 0;
   o.lstarts = nullptr;
   o.lstarts_cap = 0;
+  o.chk = nullptr;
 }
 
 #include "qh_frame_fast.h"  // kFrLines, frame_count_fast (host-testable)

@@ -63,6 +63,39 @@ QH_HD static inline int read_varint(uint64_t *res, const uint8_t **pp, const uin
 #define QH_LONG_MIN 4096u /* qh_peek_dec.inc kDeferMin */
 #endif
 
+/* Index checks against a table state, applied where an index is read (the
+ * reference validates an index before it reads the value's length,
+ * qpack.c:3537-3542): brel2abs / pbrel2abs (:3971-4017) over the section's
+ * reconstructed Required Insert Count and Base, and validate_index
+ * (:2787-2798) as live_lo <= absidx < insert_count. */
+typedef struct qh_idx_check {
+  uint64_t ricnt, base, live_lo, insert_count;
+} qh_idx_check;
+
+/* A field line's index resolved: 0 (static; *abs = the index), 1 (dynamic;
+ * *abs = the absolute index) or -1 (DECOMPRESSION_FAILED). */
+QH_HD static inline int qh_idx_resolve(const qh_idx_check *c, uint8_t opcode, uint8_t flags,
+                                       uint64_t index, uint64_t *abs) {
+  uint64_t a;
+  if (opcode == QH_FL_INDEXED || opcode == QH_FL_INDEXED_NAME) {
+    if (!(flags & QH_FL_DYNAMIC)) {
+      *abs = index;
+      return index < QH_QPACK_STATIC_ENTRIES ? 0 : -1; /* :3989-3992 */
+    }
+    if (c->base < index + 1) { /* :3979-3983 */
+      return -1;
+    }
+    a = c->base - index - 1;
+  } else { /* post-base, :4007-4015 */
+    a = index + c->base;
+  }
+  if (a >= c->ricnt || a < c->live_lo || a >= c->insert_count) {
+    return -1;
+  }
+  *abs = a;
+  return 1;
+}
+
 typedef struct scan_out {
   qh_field_line *lines;
   size_t lines_cap, nlines;
@@ -86,6 +119,10 @@ typedef struct scan_out {
    * into the section, for its first lstarts_cap lines */
   uint16_t *lstarts;
   uint32_t lstarts_cap;
+  /* (field emission's second look at a HEADER_TOO_LARGE block, qh_emit_core.h)
+   * every index checked against this table state as it is read; NULL
+   * everywhere else */
+  const qh_idx_check *chk;
 } scan_out;
 
 /* One string literal: H bit at bit `prefix` of the first byte, then the
@@ -268,6 +305,12 @@ QH_HD static inline int scan_section(scan_out *o, const uint8_t *src, size_t src
         }
       } else if (l->index >= QH_QPACK_STATIC_ENTRIES) {
         return bad;
+      }
+      if (o->chk) {
+        uint64_t absidx;
+        if (qh_idx_resolve(o->chk, opcode, flags, l->index, &absidx) < 0) {
+          return bad;
+        }
       }
     } else {
       rv = read_string(o, &l->name, src, src_off, &p, end, 3,

@@ -43,6 +43,20 @@ PREFIX_DTYPE = np.dtype([("ricnt", "<u8"), ("delta_base", "<u8"), ("sign", "<u4"
                          ("reserved", "<u4")])
 
 
+# include/qhuff.h qh_field, qh_dyn_entry, qh_dtable_view
+FIELD_DTYPE = np.dtype([("name_off", "<u8"), ("value_off", "<u8"), ("name_len", "<u4"),
+                        ("value_len", "<u4"), ("token", "<i4"), ("name_where", "u1"),
+                        ("value_where", "u1"), ("flags", "u1"), ("reserved", "u1")])
+DYN_ENTRY_DTYPE = np.dtype([("name_off", "<u8"), ("value_off", "<u8"), ("name_len", "<u4"),
+                            ("value_len", "<u4"), ("token", "<i4"), ("reserved", "<u4")])
+VIEW_DTYPE = np.dtype([("ent_base", "<i8"), ("live_lo", "<u8"), ("insert_count", "<u8"),
+                       ("max_entries", "<u8"), ("reserved", "<u8")])
+assert FIELD_DTYPE.itemsize == 32 and DYN_ENTRY_DTYPE.itemsize == 32 and VIEW_DTYPE.itemsize == 40
+IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
+EMIT_BLOCKED = 1
+EMIT_QIF = 0x1
+
+
 class qh_section_prefix(ctypes.Structure):
     _fields_ = [("ricnt", ctypes.c_uint64), ("delta_base", ctypes.c_uint64),
                 ("sign", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
@@ -118,6 +132,24 @@ def _load():
         lib.qh_encode_sections_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, u64, vp,
                                                  c.POINTER(u64), i32]
         lib.qh_encode_sections_batch.restype = i32
+        lib.qh_dtable_new.argtypes = [c.POINTER(vp), u64]
+        lib.qh_dtable_new.restype = i32
+        lib.qh_dtable_del.argtypes = [vp]
+        lib.qh_dtable_del.restype = None
+        lib.qh_dtable_apply.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        lib.qh_dtable_apply.restype = i32
+        lib.qh_dtable_get_view.argtypes = [vp, vp]
+        lib.qh_dtable_get_view.restype = i32
+        lib.qh_dtable_entries.argtypes = [vp, c.POINTER(sz)]
+        lib.qh_dtable_entries.restype = vp
+        lib.qh_dtable_bytes.argtypes = [vp, c.POINTER(sz)]
+        lib.qh_dtable_bytes.restype = vp
+        emit_args = [vp, vp, sz, c.POINTER(qh_sections), vp, vp, vp, vp, vp, sz, c.c_uint32,
+                     c.POINTER(_lib.qh_emit)]
+        lib.qh_qpack_emit_fields.argtypes = emit_args
+        lib.qh_qpack_emit_fields.restype = i32
+        lib.qh_emit_fields_batch.argtypes = [vp] + emit_args + [i32]
+        lib.qh_emit_fields_batch.restype = i32
         _L = lib
     return _L
 
@@ -382,7 +414,7 @@ class FieldSectionDecoder:
         self.opts = SECTIONS_DTABLE0 if dtable0 else 0
         self._spare = None  # the last decode_blocks result's arrays (_host_bufs)
 
-    def decode_blocks_dev(self, src, blocks, bufs=None, packed=False):
+    def decode_blocks_dev(self, src, blocks, bufs=None, packed=False, prefixes=False):
         """src uint8 and blocks int64 [n,2] (SPAN_IN layout) torch tensors in
         HBM.  Returns a dict of torch tensors (lines, spans, strs, verdict,
         tokens, line_start, span_start, status, dst) plus the totals
@@ -390,7 +422,9 @@ class FieldSectionDecoder:
         reuses its allocations.  Asynchronous after the framing sync.
         ``packed`` (QH_SECTIONS_PACKED): the decoded Huffman strings back to
         back in dst (dst_need: their bytes) instead of the slot layout; the
-        call then also waits for the decode."""
+        call then also waits for the decode.  ``prefixes``: also every
+        block's section prefix as encoded (uint8 [n * 24], PREFIX_DTYPE),
+        which ``emit_fields_dev`` needs."""
         import torch
         dev = src.device
         n = blocks.shape[0]
@@ -407,6 +441,9 @@ class FieldSectionDecoder:
                  "span_start": torch.empty(n + 1, dtype=torch.int32, device=dev),
                  "status": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
                  "dst": torch.empty(64, dtype=torch.uint8, device=dev)}
+        if prefixes and b.get("prefixes") is None:
+            b["prefixes"] = torch.empty(max(b["n"], 1) * PREFIX_DTYPE.itemsize, dtype=torch.uint8,
+                                        device=dev)
         opts = self.opts | (_lib.QH_SECTIONS_PACKED if packed else 0)
         if packed and b["dst"].numel() < cap * 8 // 5:  # (the bound that always suffices)
             b["dst"] = torch.empty(cap * 8 // 5, dtype=torch.uint8, device=dev)
@@ -415,7 +452,8 @@ class FieldSectionDecoder:
         for _ in range(2):  # a second try only when dst was too small
             st = qh_sections(p(b["lines"]), cap, p(b["spans"]), cap, p(b["strs"]), p(b["verdict"]),
                              p(b["tokens"]), p(b["line_start"]), p(b["span_start"]), p(b["status"]),
-                             None, p(b["dst"]), b["dst"].numel(), 0, 0, 0, 0)
+                             p(b["prefixes"]) if prefixes else None, p(b["dst"]),
+                             b["dst"].numel(), 0, 0, 0, 0)
             rv = lib.qh_decode_sections_batch(self.codec._ctx, ctypes.c_void_p(src.data_ptr()),
                                               ctypes.c_void_p(blocks.data_ptr()), n, opts,
                                               ctypes.byref(st), _lib.QH_WHERE_DEVICE)
@@ -480,7 +518,7 @@ class FieldSectionDecoder:
             self._host_empty(raw, "dst", dst_size, np.uint8, pinned)
         return raw
 
-    def decode_blocks(self, src, blocks, packed=False, bufs=None, pinned=False):
+    def decode_blocks(self, src, blocks, packed=False, bufs=None, pinned=False, prefixes=False):
         """Host arrays in and out: -> dict with lines, spans, strs
         (SPAN_OUT_DTYPE: Huffman strings in dst, raw strings in src),
         huffman (bool per span), verdict, tokens, line_start, span_start,
@@ -491,7 +529,10 @@ class FieldSectionDecoder:
         previous result) has its arrays written again when they are large
         enough; ``pinned`` allocates the arrays in page-locked memory.  The
         arrays are allocated uninitialised, and those of the last result
-        are taken again once that result has been dropped."""
+        are taken again once that result has been dropped.  (``prefixes``:
+        accepted for symmetry with decode_blocks_dev; the host result always
+        holds them.)"""
+        del prefixes
         lib = _load()
         src = _u8(src)
         if src.size == 0:
@@ -534,6 +575,221 @@ class FieldSectionDecoder:
         del dst, spans
         self._spare = raw
         return res
+
+
+    # ---- field emission (qh_qpack_emit_fields / qh_emit_fields_batch) ----
+
+    @staticmethod
+    def _sections_struct(res, ptr):
+        """The qh_sections of a finished decode result (its pointers through
+        `ptr`)."""
+        if res.get("prefixes") is None:
+            raise ValueError("emit_fields needs a result decoded with prefixes=True")
+        n = lambda k: ptr(res[k]) if res.get(k) is not None else None
+        return qh_sections(n("lines"), int(res["nlines"]), n("spans"), int(res["nspans"]), n("strs"),
+                           n("verdict"), n("tokens"), n("line_start"), n("span_start"), n("status"),
+                           n("prefixes"), n("dst"), 0, int(res["nlines"]), int(res["nspans"]),
+                           int(res["nhuff"]), int(res["dst_need"]))
+
+    @staticmethod
+    def emit_fields(res, src, blocks, table=None, views=None, block_view=None, sel=None,
+                    qif=False, materialise=True, entries=None, dyn_bytes=None):
+        """Host arrays: the header list of every selected block of `res` (a
+        decode_blocks result over src, blocks), indices resolved against the
+        static table and `table` (a DynamicTable: its current state) or
+        `views` (VIEW_DTYPE; block b decodes against views[block_view[b]],
+        views[0] without block_view; entries / dyn_bytes default to
+        table's).  -> dict: fields (FIELD_DTYPE), field_start, status (0,
+        EMIT_BLOCKED, -401, -109), ricnt, out and out_blocks (materialise:
+        the names and values back to back, QIF text with ``qif``), nfields,
+        out_need, nblocked.  Runs on the host (qh_qpack_emit_fields; no
+        context or GPU is involved, hence a static method)."""
+        lib = _load()
+        src = _u8(src)
+        blocks = np.ascontiguousarray(blocks, dtype=SPAN_IN_DTYPE)
+        if table is not None:
+            views = table.view() if views is None else views
+            entries, dyn_bytes = table.entries(), table.bytes()
+        vw = None if views is None else np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
+        bv = None if block_view is None else np.ascontiguousarray(block_view, dtype=np.uint32)
+        sl = None if sel is None else np.ascontiguousarray(sel, dtype=np.uint32)
+        ents = None if entries is None else np.ascontiguousarray(entries, dtype=DYN_ENTRY_DTYPE)
+        dbytes = None if dyn_bytes is None else _u8(dyn_bytes)
+        nsel = blocks.size if sl is None else sl.size
+        st = FieldSectionDecoder._sections_struct(res, lambda a: a.ctypes.data)
+        o = {"fields": np.zeros(max(int(res["nlines"]), 1), dtype=FIELD_DTYPE),
+             "field_start": np.zeros(nsel + 1, dtype=np.uint32),
+             "status": np.zeros(max(nsel, 1), dtype=np.int32),
+             "ricnt": np.zeros(max(nsel, 1), dtype=np.uint64),
+             "out_blocks": np.zeros(max(nsel, 1), dtype=SPAN_IN_DTYPE),
+             "out": np.zeros(1, dtype=np.uint8) if materialise else None}
+        opt = lambda a: None if a is None else _vp(a)
+        for _ in range(2):  # a second try once out_need is known
+            e = _lib.qh_emit(o["fields"].ctypes.data, o["fields"].size, o["field_start"].ctypes.data,
+                             o["status"].ctypes.data, o["ricnt"].ctypes.data,
+                             o["out"].ctypes.data if materialise else None,
+                             o["out"].size if materialise else 0, o["out_blocks"].ctypes.data, 0, 0, 0)
+            rv = lib.qh_qpack_emit_fields(_vp(src), _vp(blocks), blocks.size, ctypes.byref(st),
+                                          opt(vw), opt(bv), opt(ents), opt(dbytes), opt(sl), nsel,
+                                          EMIT_QIF if qif else 0, ctypes.byref(e))
+            if rv == _lib.QH_ERR_NOMEM and materialise and e.out_need > o["out"].size:
+                o["out"] = np.zeros(int(e.out_need), dtype=np.uint8)
+                continue
+            _lib.check(rv, "qh_qpack_emit_fields")
+            break
+        return {"fields": o["fields"][:e.nfields], "field_start": o["field_start"],
+                "status": o["status"][:nsel], "ricnt": o["ricnt"][:nsel],
+                "out_blocks": o["out_blocks"][:nsel],
+                "out": o["out"][:e.out_need] if materialise else None,
+                "nfields": int(e.nfields), "out_need": int(e.out_need), "nblocked": int(e.nblocked)}
+
+    def emit_fields_dev(self, res, src, blocks, table=None, views=None, block_view=None, sel=None,
+                        qif=False, materialise=True, entries=None, dyn_bytes=None, bufs=None):
+        """Device-resident form (qh_emit_fields_batch): `res` a
+        decode_blocks_dev(..., prefixes=True) result over the torch tensors
+        src, blocks.  `table` is a DynamicTable (uploaded with to_device: only
+        the tail since the last upload crosses) or views / entries /
+        dyn_bytes / block_view / sel are torch tensors already in HBM (views
+        uint8 [nviews * 40], entries uint8 [n * 32], block_view and sel
+        int32).  -> dict of torch tensors (fields uint8 [nfields * 32],
+        field_start int32, status int32, ricnt int64, out uint8, out_blocks
+        int64 [nsel, 2]) plus nfields, out_need, nblocked; `bufs` (a previous
+        result) reuses its allocations.  One host wait, for the totals."""
+        import torch
+        lib = _load()
+        dev = src.device
+        if table is not None:
+            d = table.to_device(dev)
+            views = d["views"] if views is None else views
+            entries, dyn_bytes = d["entries"], d["bytes"]
+        n = blocks.shape[0]
+        nsel = n if sel is None else sel.shape[0]
+        nl = max(int(res["nlines"]), 1)
+        b = bufs or {}
+        if b.get("nl", -1) < nl or b.get("nsel", -1) < nsel:
+            b = {"nl": nl, "nsel": nsel,
+                 "fields": torch.empty(nl * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev),
+                 "field_start": torch.empty(nsel + 1, dtype=torch.int32, device=dev),
+                 "status": torch.empty(max(nsel, 1), dtype=torch.int32, device=dev),
+                 "ricnt": torch.empty(max(nsel, 1), dtype=torch.int64, device=dev),
+                 "out_blocks": torch.empty((max(nsel, 1), 2), dtype=torch.int64, device=dev),
+                 "out": torch.empty(64, dtype=torch.uint8, device=dev)}
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        st = self._sections_struct(res, lambda t: t.data_ptr())
+        for _ in range(2):  # a second try once out_need is known
+            e = _lib.qh_emit(b["fields"].data_ptr(), b["nl"], b["field_start"].data_ptr(),
+                             b["status"].data_ptr(), b["ricnt"].data_ptr(),
+                             b["out"].data_ptr() if materialise else None,
+                             b["out"].numel() if materialise else 0, b["out_blocks"].data_ptr(),
+                             0, 0, 0)
+            rv = lib.qh_emit_fields_batch(self.codec._ctx, p(src), p(blocks), n, ctypes.byref(st),
+                                          p(views), p(block_view), p(entries), p(dyn_bytes), p(sel),
+                                          nsel, EMIT_QIF if qif else 0, ctypes.byref(e),
+                                          _lib.QH_WHERE_DEVICE)
+            if rv == _lib.QH_ERR_NOMEM and materialise and e.out_need > b["out"].numel():
+                b["out"] = torch.empty(int(e.out_need), dtype=torch.uint8, device=dev)
+                continue
+            _lib.check(rv, "qh_emit_fields_batch")
+            break
+        b.update({"nfields": int(e.nfields), "out_need": int(e.out_need),
+                  "nblocked": int(e.nblocked)})
+        return b
+
+
+class DynamicTable:
+    """The decoder's dynamic table (qh_dtable_*): ``apply`` feeds it
+    encoder-stream bytes, ``view`` is its current state (one VIEW_DTYPE
+    record; it stays valid after later applies, the log being append-only),
+    ``entries`` / ``bytes`` the log, ``to_device`` its copy in HBM."""
+
+    def __init__(self, hard_max: int):
+        self._lib = _load()
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.qh_dtable_new(ctypes.byref(h), hard_max), "qh_dtable_new")
+        self._h = h
+        self._dev = None  # to_device's tensors and how much of the log they hold
+
+    def close(self):
+        if self._h:
+            self._lib.qh_dtable_del(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, record_bytes) -> int:
+        """Scans the encoder-stream bytes, decodes their Huffman strings (the
+        scalar drop-in) and applies the complete instructions.  Returns the
+        bytes consumed (a trailing partial instruction is left to the
+        caller); raises QhError with the reference's error (-402, -109)."""
+        from .qpack_huffman import HuffmanDecodeContext, huffman_decode, huffman_decode_context_init
+        buf = _u8(record_bytes)
+        rv, insts, spans = scan_encoder_stream(buf)
+        _lib.check(rv, "qh_qpack_scan_encoder_stream")
+        strs = np.zeros(max(spans.size, 1), dtype=SPAN_OUT_DTYPE)
+        dec = bytearray()
+        for k, s in enumerate(spans):
+            if s["flags"] & SPAN_HUFFMAN:
+                ctx = HuffmanDecodeContext()
+                huffman_decode_context_init(ctx)
+                out = huffman_decode(ctx, buf[int(s["off"]):int(s["off"]) + int(s["len"])], True)
+                if isinstance(out, int):
+                    raise _lib.QhError(QH_ERR_QPACK_ENCODER_STREAM_ERROR, "encoder stream Huffman string")
+                strs[k] = (len(dec), len(out), 0)
+                dec += out
+        d = _u8(bytes(dec))
+        insts = np.ascontiguousarray(insts)
+        spans = np.ascontiguousarray(spans)
+        _lib.check(self._lib.qh_dtable_apply(self._h, _vp(insts), insts.size, _vp(buf), _vp(spans),
+                                             _vp(d), _vp(strs)), "qh_dtable_apply")
+        return int(rv)
+
+    def view(self):
+        v = np.zeros(1, dtype=VIEW_DTYPE)
+        _lib.check(self._lib.qh_dtable_get_view(self._h, _vp(v)), "qh_dtable_get_view")
+        return v
+
+    def _log(self, fn, dtype):
+        n = ctypes.c_size_t(0)
+        p = fn(self._h, ctypes.byref(n))
+        if not n.value:
+            return np.zeros(0, dtype=dtype)
+        nbytes = n.value * np.dtype(dtype).itemsize
+        return np.frombuffer(ctypes.string_at(p, nbytes), dtype=dtype)
+
+    def entries(self):
+        """A copy of the entry log (DYN_ENTRY_DTYPE; entry a is record a)."""
+        return self._log(self._lib.qh_dtable_entries, DYN_ENTRY_DTYPE)
+
+    def bytes(self):
+        """A copy of the byte log."""
+        return self._log(self._lib.qh_dtable_bytes, np.uint8)
+
+    def to_device(self, device):
+        """-> {"views" uint8 [40], "entries" uint8 [n * 32], "bytes" uint8}
+        torch tensors on `device` holding the current state and the log.
+        Only the records and bytes appended since the last upload are
+        copied (the tensors are kept, with room to grow)."""
+        import torch
+        ents, byts = self.entries(), self.bytes()
+        d = self._dev
+        if d is None or d["device"] != torch.device(device):
+            d = self._dev = {"device": torch.device(device), "ne": 0, "nb": 0,
+                             "entries": torch.empty(0, dtype=torch.uint8, device=device),
+                             "bytes": torch.empty(0, dtype=torch.uint8, device=device)}
+        for key, have, host in (("entries", "ne", ents.view(np.uint8)), ("bytes", "nb", byts)):
+            if host.size > d[key].numel():  # grow: keep what is there
+                t = torch.empty(max(2 * host.size, 4096), dtype=torch.uint8, device=device)
+                t[:d[have]] = d[key][:d[have]]
+                d[key] = t
+            if host.size > d[have]:
+                d[key][d[have]:host.size] = torch.from_numpy(host[d[have]:].copy()).to(device)
+                d[have] = host.size
+        views = torch.from_numpy(self.view().view(np.uint8).copy()).to(device)
+        return {"views": views, "entries": d["entries"], "bytes": d["bytes"]}
 
 
 def static_entry(idx: int):

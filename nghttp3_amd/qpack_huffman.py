@@ -190,9 +190,12 @@ class HuffmanBatchCodec:
         encoded bytes; 0 = off) and 'lens_lane_pass' (1: every string's
         encoded length counted a lane per string) and 'sections_slice_blocks'
         (header blocks per slice of the pipelined host-memory field-section
-        decode; 0 = chosen by the library)."""
+        decode; 0 = chosen by the library) and 'emit_long_min' (field
+        emission copies a string of at least that many bytes with a wave; 0 =
+        chosen by the library)."""
         k = {"long_min": _lib.QH_OPT_LONG_MIN, "lens_lane_pass": _lib.QH_OPT_LENS_LANE_PASS,
-             "sections_slice_blocks": _lib.QH_OPT_SECTIONS_SLICE_BLOCKS}[option]
+             "sections_slice_blocks": _lib.QH_OPT_SECTIONS_SLICE_BLOCKS,
+             "emit_long_min": _lib.QH_OPT_EMIT_LONG_MIN}[option]
         _lib.check(self._lib.qh_ctx_set_option(self._ctx, k, int(value)), "qh_ctx_set_option")
 
     def sync(self):
