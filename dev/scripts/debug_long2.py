@@ -16,7 +16,7 @@ def main():
     import oracle
     import test_long_model as M
     from nghttp3_amd import HuffmanBatchCodec, synth, _lib
-    M._TABLE = M._codes()
+    M.init_table()
     lib = _lib.load()
     lib.qh_debug_long.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
                                                           ctypes.c_void_p, ctypes.c_void_p]

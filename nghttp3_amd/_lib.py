@@ -255,6 +255,11 @@ def load():
     lib.qh_synth_spans.restype = i32
     lib.qh_synth_fill.argtypes = [vp, u64, u64, vp, u64, vp, u32]
     lib.qh_synth_fill.restype = i32
+    # development entry, not in include/qhuff.h (csrc/qh_api.inc: one string
+    # through long_string_coop with 1, 4 or 16 waves, res[2] and the segment
+    # trace in device memory); tests/test_gpu_edges.py drives it
+    lib.qh_debug_long.argtypes = [vp, vp, u32, vp, i32, vp, vp]
+    lib.qh_debug_long.restype = i32
     lib.qh_version.argtypes = []
     lib.qh_version.restype = c.c_char_p
     _lib = lib

@@ -166,10 +166,18 @@ __device__ void long_string_coop(const uint16_t *ut, uint8_t *lw, LongChain *ch,
         const uint32_t t = lane == 0 ? p0 : prev;
         const bool chg = act && (lane > 0 || with0) && t != sc;
         if (__builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(chg) != 0 ? 1u : 0u) == 0) break;
+        // t < base: the walk before this lane stopped at an error, short of
+        // the lane's bits.  A walk from t would fail there again, and t is
+        // outside the lane's window and mask: the lane takes that result
+        // without walking (none of its symbols, its end t, the error).
+        const bool fell = chg && t < base;
+        const bool go = chg && !fell;
         uint32_t k2 = 0;
         bool er2 = false, sy = false;
-        const uint32_t at = long_walk<false, true>(ut, w, base, chg ? t : base, chg ? lim : base, nbits, head,
+        const uint32_t aw = long_walk<false, true>(ut, w, base, go ? t : base, go ? lim : base, nbits, head,
                                                    k2, er2, lo, hi, sy);
+        const uint32_t at = fell ? t : aw;
+        er2 = fell || er2;
         // from `at` on, the speculative walk (sy), or none of it
         const uint32_t cs = sy ? long_below(lo, hi, at - base) : ms;
         sc = chg ? t : sc;

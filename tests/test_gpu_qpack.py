@@ -486,6 +486,52 @@ def _dev_result(g, nblocks):
             "status": g["status"][:nblocks].cpu().numpy(), "dst": g["dst"].cpu().numpy()}
 
 
+def run_sections(codec, src, blocks, opts, dst_cap, where, tail=0, fill=0xA5):
+    """One qh_decode_sections_batch call with the caps that always suffice
+    (total block bytes + 1 lines and spans) and a dst of dst_cap bytes
+    followed by `tail` more, all set to `fill`; where: "device" or "host".
+    -> (rv, the qh_sections as the call left it, the result as
+    _check_against_oracle reads it, dst with its tail)."""
+    import ctypes
+    import torch
+    from nghttp3_amd import _lib
+    n = blocks.size
+    cap = int(blocks["len"].sum()) + 1
+    widths = (("lines", 24), ("spans", 16), ("strs", 16), ("verdict", 1), ("tokens", 4))
+    if where == "device":
+        t = {k: torch.zeros(cap * w, dtype=torch.uint8, device="cuda") for k, w in widths}
+        t.update({k: torch.zeros((n + 1) * 4, dtype=torch.uint8, device="cuda")
+                  for k in ("line_start", "span_start", "status")})
+        t["dst"] = torch.full((dst_cap + tail,), fill, dtype=torch.uint8, device="cuda")
+        d_src = torch.from_numpy(src).cuda()
+        d_blk = torch.from_numpy(blocks.view(np.int64).reshape(-1, 2).copy()).cuda()
+        p = lambda k: t[k].data_ptr()
+        src_p, blk_p = ctypes.c_void_p(d_src.data_ptr()), ctypes.c_void_p(d_blk.data_ptr())
+    else:
+        t = {k: np.zeros(cap * w, np.uint8) for k, w in widths}
+        t.update({k: np.zeros((n + 1) * 4, np.uint8) for k in ("line_start", "span_start", "status")})
+        t["dst"] = np.full(dst_cap + tail, fill, np.uint8)
+        p = lambda k: t[k].ctypes.data
+        src_p, blk_p = qpack._vp(src), qpack._vp(blocks)
+    st = qpack.qh_sections(p("lines"), cap, p("spans"), cap, p("strs"), p("verdict"), p("tokens"),
+                           p("line_start"), p("span_start"), p("status"), None, p("dst"), dst_cap,
+                           0, 0, 0, 0)
+    rv = qpack._load().qh_decode_sections_batch(codec._ctx, src_p, blk_p, n, opts, ctypes.byref(st),
+                                                _lib.QH_WHERE_DEVICE if where == "device"
+                                                else _lib.QH_WHERE_HOST)
+    if where == "device":
+        torch.cuda.synchronize()
+        t = {k: v.cpu().numpy() for k, v in t.items()}
+    ns, nl = int(st.nspans), int(st.nlines)
+    res = {"spans": t["spans"].view(SPAN_IN_DTYPE)[:ns], "strs": t["strs"].view(qpack.SPAN_OUT_DTYPE)[:ns],
+           "verdict": t["verdict"].view(np.int8)[:ns], "tokens": t["tokens"].view(np.int32)[:ns],
+           "span_start": t["span_start"].view(np.uint32)[:n + 1],
+           "line_start": t["line_start"].view(np.uint32)[:n + 1],
+           "lines": t["lines"].view(qpack.FIELD_LINE_DTYPE)[:nl],
+           "status": t["status"].view(np.int32)[:n], "dst": t["dst"][:dst_cap]}
+    return rv, st, res, t["dst"]
+
+
 @pytest.mark.parametrize("dtable0", [False, True])
 def test_sections_long_and_binary_values_match_oracle(dec, dec0, refdata, dtable0):
     """qh_decode_sections_batch on the strings nghttp3 accepts beyond short

@@ -30,6 +30,7 @@ class Bits:
         # ones past the string (the decoder's padding feed)
         self.v = int.from_bytes(enc + b"\xff" * 16, "big")
         self.tot = 8 * (len(enc) + 16)
+        self.codes = {}  # position -> _code_at's answer (re-walks meet positions again)
 
     def get(self, pos, n):
         return (self.v >> (self.tot - pos - n)) & ((1 << n) - 1)
@@ -37,9 +38,14 @@ class Bits:
 
 def _code_at(b: Bits, pos):
     """utab_lookup: (length, symbol) of the code at pos; symbol 256 = EOS."""
+    hit = b.codes.get(pos)
+    if hit is not None:
+        return hit
+    v = b.get(pos, 30)  # (one read of the longest code's bits; ones past the string)
     for n in range(5, 31):
-        s = _TABLE.get((n, b.get(pos, n)))
+        s = _TABLE.get((n, v >> (30 - n)))
         if s is not None:
+            b.codes[pos] = (n, s)
             return n, s
     raise AssertionError("no code")
 
@@ -64,14 +70,21 @@ def long_walk(b, base, s, lim, mask, rec, sync):
     return pos, syms, False, False
 
 
-def long_decode_model(enc: bytes, trace=None):
+def long_decode_model(enc: bytes, trace=None, counts=None):
     """-> (status, decoded bytes) as long_string_coop computes them; trace
     (a list) receives per segment (first-code start, decoded bytes, error so
-    far, next start) as qh_debug_long reports them."""
+    far, next start) as qh_debug_long reports them, after segment 0's 64
+    per-lane tuples (its trace words 4096...).  counts (a dict) receives
+    "segments", "rounds" (iterations of resolve's loop, the one that finds
+    nothing to change included: two per segment at the least) and
+    "unsynced" (re-walks that ran to the lane's end without meeting a
+    recorded code start)."""
     b = Bits(enc)
     nbits = b.nbits
     nseg = (nbits + SEG - 1) // SEG
     p0, out, bad = 0, bytearray(), False
+    if counts is not None:
+        counts.update(segments=nseg, rounds=0, unsynced=0)
     for k in range(nseg):
         lanes = []
         for lane in range(64):
@@ -86,6 +99,8 @@ def long_decode_model(enc: bytes, trace=None):
 
         def resolve(with0):
             while True:
+                if counts is not None:
+                    counts["rounds"] += 1
                 prev = [L["e"] for L in lanes]
                 changed = False
                 for j, L in enumerate(lanes):
@@ -93,7 +108,10 @@ def long_decode_model(enc: bytes, trace=None):
                     if not (L["act"] and (j > 0 or with0) and t != L["sc"]):
                         continue
                     changed = True
+                    # (t < base: the lane before stopped at an error; the walk
+                    # from t fails there again, which the kernel takes as given)
                     at, head, er2, sy = long_walk(b, L["base"], t, L["lim"], L["mask"], False, True)
+                    assert t >= L["base"] or (at, head, er2, sy) == (t, [], True, False)
                     L["sc"], L["head"] = t, head
                     if sy:
                         L["c"] = sum(1 for x in L["mask"] if x < at)
@@ -101,6 +119,8 @@ def long_decode_model(enc: bytes, trace=None):
                     else:
                         L["c"] = len(L["spec"])
                         L["e"], L["er"] = at, er2
+                        if counts is not None:
+                            counts["unsynced"] += 1
                 if not changed:
                     return
 
@@ -122,10 +142,17 @@ def long_decode_model(enc: bytes, trace=None):
     return (-108, b"") if bad else (0, bytes(out))
 
 
+def init_table():
+    """Build the code table of the model (for importers: tests/test_edge_cases.py,
+    tests/test_gpu_edges.py, dev/scripts)."""
+    global _TABLE
+    if _TABLE is None:
+        _TABLE = _codes()
+
+
 @pytest.fixture(scope="module", autouse=True)
 def table():
-    global _TABLE
-    _TABLE = _codes()
+    init_table()
 
 
 def _cases():
