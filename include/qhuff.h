@@ -784,6 +784,41 @@ QH_EXPORT int qh_emit_fields_batch(
     const uint8_t *dyn_bytes, const uint32_t *sel, size_t nsel, uint32_t opts,
     qh_emit *e, int where);
 
+/* ---- Field representations on the GPU (SURVEY.md section 8(a) rows a9 /
+ * a10) -------------------------------------------------------------------
+ * qh_qpack_plan_fields on the GPU: the choice of
+ * nghttp3_qpack_encoder_encode_nv at capacity 0 (qpack.c:1455-1628), its
+ * indexing mode (:1307-1371) and nghttp3_qpack_lookup_stable (:1630-1660)
+ * for every field of a batch, one lane per field; lines byte for byte those
+ * of the host function (same source, csrc/qh_plan_core.h).
+ * QH_WHERE_DEVICE: all pointers in HBM, asynchronous on the context stream,
+ * no host wait.  QH_WHERE_HOST: staged, blocking.  Strings are read as
+ * qh_check_fields_batch reads them (no padding is needed).  nfields may be
+ * at most 2^30 (a line's name / value index is an int32). */
+QH_EXPORT int qh_plan_fields_batch(qh_ctx *ctx, const uint8_t *plain,
+                                   const qh_span_in *strs, size_t nfields,
+                                   const uint8_t *never, qh_field_line *lines,
+                                   int where);
+
+/* Fields to field sections in one call: section b is fields
+ * [field_start[b], field_start[b+1]) (nsections + 1 entries, nfields in all:
+ * field_start[nsections] must be nfields), planned as above (the token is
+ * computed from the name as the reference does, :1477; of a qh_field only
+ * name_off, name_len, value_off, value_len -- offsets into plain -- and
+ * flags & QH_FL_NEVER are read), then written as qh_encode_sections_batch
+ * writes them (qpack.c:1817-2069; prefixes all zero: no dynamic-table
+ * reference is ever chosen).  Takes qh_emit_fields_batch's `fields`,
+ * `field_start` and `out` as they are.  A section whose range is empty is
+ * its two prefix bytes.  Returns and the QH_ERR_NOMEM contract are those of
+ * qh_encode_sections_batch (*dst_need exact, nothing written);
+ * QH_WHERE_DEVICE keeps that call's single host wait and adds none. */
+QH_EXPORT int qh_encode_fields_batch(qh_ctx *ctx, const uint8_t *plain,
+                                     const qh_field *fields, size_t nfields,
+                                     const uint32_t *field_start,
+                                     size_t nsections, uint8_t *dst,
+                                     uint64_t dst_cap, qh_span_in *sections,
+                                     uint64_t *dst_need, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

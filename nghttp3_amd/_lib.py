@@ -166,6 +166,9 @@ EXPORTED_FUNCTIONS = (
     "qh_dtable_bytes",
     "qh_qpack_emit_fields",
     "qh_emit_fields_batch",
+    # field representations on the GPU (csrc/qh_plan.inc)
+    "qh_plan_fields_batch",
+    "qh_encode_fields_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -33,7 +33,8 @@ enum BufId {
   kBufEncSecCodes,  // ... the picked Huffman strings
   kBufEncSecLoff,   // ... per-line offsets
   kBufEmit,         // qh_emit_fields_batch: per-block counts, per-line records, long strings
-  kBufEmitStatic,   // ... the static table: 99 records, then their bytes
+  kBufEmitStatic,   // ... the static table: 99 records, their bytes, the planner's chains and token tables
+  kBufPlan,         // qh_encode_fields_batch: the planned fields' spans and lines
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage0,     // host-mode staging: src, spans in, dst, spans out
   kBufPinned0 = kBufStage0 + 4,  // from here on: pinned host memory

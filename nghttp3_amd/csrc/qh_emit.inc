@@ -34,11 +34,28 @@
 // (qh_emit.c) the static table as 99 records over one blob
 extern "C" void qh_emit_static_blob(const qh_static_rec **recs, const uint8_t **bytes,
                                     size_t *nbytes);
+// (qh_static.c) the entries of each static name as a chain
+extern "C" void qh_plan_static_chains(const int8_t **first, const int8_t **next);
 
 namespace qhk {
 
 constexpr uint32_t kEmLanes = 16;
 constexpr uint32_t kEmStatRecs = 2048;  // the records' room ahead of the blob (99 * 20 B)
+constexpr uint32_t kEmStatBlob = 2048;  // the blob's room (about 1.6 KB)
+constexpr uint32_t kEmStatValueMax = 64;  // no static value is longer (the longest has 53 bytes)
+
+// Behind the blob, for the planner (qh_plan.inc): the entries of a name as
+// chains (qh_plan_core.h) and the token tables of qh_tokens.h.
+struct EmStatExtra {
+  int8_t first[112];  // per token < 99: the name's first entry, or -1
+  int8_t next[112];   // per entry: the next entry of the same name, or -1
+  uint8_t tok_start[48];
+  uint16_t tok_off[64];
+  int16_t tok_val[64];
+  uint8_t tok_pool[800];
+};
+constexpr uint32_t kEmStatImage = kEmStatRecs + kEmStatBlob + sizeof(EmStatExtra);
+static_assert(sizeof(EmStatExtra) % 16 == 0, "the image is copied in 16-byte pieces");
 
 // A string too long for one lane: n bytes from -> to.
 struct EmLong {
@@ -263,16 +280,39 @@ namespace {
 
 constexpr uint32_t kEmitLongMin = 256;  // qh_ctx::emit_long_min's default (DESIGN.md section 3.5)
 
+// (the host's copy of the token tables; the kernels' is qh_validate.inc's)
+namespace qht {
+#define QH_TOKEN_CONST static const
+#include "qh_tokens.h"
+#undef QH_TOKEN_CONST
+}  // namespace qht
+
 int emit_static(qh_ctx *c) {
   if (c->buf[kBufEmitStatic].p) return 0;
   const qh_static_rec *recs;
   const uint8_t *bytes;
   size_t nbytes;
   qh_emit_static_blob(&recs, &bytes, &nbytes);
-  std::vector<uint8_t> img(qhk::kEmStatRecs + nbytes + 16, 0);
+  if (nbytes > qhk::kEmStatBlob) return QH_ERR_FATAL;  // (cannot happen: the table is fixed)
+  std::vector<uint8_t> img(qhk::kEmStatImage, 0);
   static_assert(QH_QPACK_STATIC_ENTRIES * sizeof(qh_static_rec) <= qhk::kEmStatRecs, "records");
   memcpy(img.data(), recs, QH_QPACK_STATIC_ENTRIES * sizeof(qh_static_rec));
   memcpy(img.data() + qhk::kEmStatRecs, bytes, nbytes);
+  for (size_t i = 0; i < QH_QPACK_STATIC_ENTRIES; ++i)
+    if (recs[i].value_len > qhk::kEmStatValueMax) return QH_ERR_FATAL;  // (cannot happen either)
+  qhk::EmStatExtra x{};
+  const int8_t *first, *next;
+  qh_plan_static_chains(&first, &next);
+  memcpy(x.first, first, QH_QPACK_STATIC_ENTRIES);
+  memcpy(x.next, next, QH_QPACK_STATIC_ENTRIES);
+  static_assert(sizeof(x.tok_start) >= sizeof(qht::qh_token_start) && sizeof(x.tok_off) >= sizeof(qht::qh_token_off) &&
+                    sizeof(x.tok_val) >= sizeof(qht::qh_token_val) && sizeof(x.tok_pool) >= sizeof(qht::qh_token_pool),
+                "token tables");
+  memcpy(x.tok_start, qht::qh_token_start, sizeof(qht::qh_token_start));
+  memcpy(x.tok_off, qht::qh_token_off, sizeof(qht::qh_token_off));
+  memcpy(x.tok_val, qht::qh_token_val, sizeof(qht::qh_token_val));
+  memcpy(x.tok_pool, qht::qh_token_pool, sizeof(qht::qh_token_pool));
+  memcpy(img.data() + qhk::kEmStatRecs + qhk::kEmStatBlob, &x, sizeof(x));
   return upload(c, kBufEmitStatic, img.data(), img.size());
 }
 

@@ -172,7 +172,11 @@ int encode(const char *outfile, const char *infile) {
   }
   const size_t nsec = field_start.size() - 1, nfields = strs.size() / 2;
   if (text.empty()) text.push_back(0);
-  std::vector<qh_field_line> lines(nfields ? nfields : 1);
+  // --scalar plans on the host (qh_qpack_plan_fields) and writes with the C
+  // writer; the GPU path hands the fields to qh_encode_fields_batch, which
+  // plans them on the device
+  std::vector<qh_field_line> lines(config.scalar ? (nfields ? nfields : 1) : 0);
+  std::vector<qh_field> fields(config.scalar ? 0 : (nfields ? nfields : 1));
   std::vector<qh_span_in> sections(nsec ? nsec : 1);
   std::vector<uint8_t> dst;
   uint64_t need = 0;
@@ -180,9 +184,16 @@ int encode(const char *outfile, const char *infile) {
   const int reps = config.time_reps > 0 ? config.time_reps : 1;
   for (int r = 0; r < reps; ++r) {
     double t0 = now_ms();
-    if (qh_qpack_plan_fields(text.data(), strs.data(), nfields, nullptr, lines.data()) != 0) {
-      std::cerr << "qh_qpack_plan_fields failed" << std::endl;
-      return -1;
+    if (config.scalar) {
+      if (qh_qpack_plan_fields(text.data(), strs.data(), nfields, nullptr, lines.data()) != 0) {
+        std::cerr << "qh_qpack_plan_fields failed" << std::endl;
+        return -1;
+      }
+    } else {
+      for (size_t i = 0; i < nfields; ++i) {
+        const qh_span_in &nm = strs[2 * i], &v = strs[2 * i + 1];
+        fields[i] = qh_field{nm.off, v.off, nm.len, v.len, -1, QH_IN_OUT, QH_IN_OUT, 0, 0};
+      }
     }
     double t1 = now_ms();
     int rv;
@@ -194,9 +205,9 @@ int encode(const char *outfile, const char *infile) {
       need = nsec ? sections[nsec - 1].off + sections[nsec - 1].len : 0;
     } else {
       for (int k = 0; k < 2; ++k) {
-        rv = qh_encode_sections_batch(ctx(), text.data(), strs.data(), strs.size(), lines.data(),
-                                      field_start.data(), nsec, nullptr, dst.data(), dst.size(),
-                                      sections.data(), &need, QH_WHERE_HOST);
+        rv = qh_encode_fields_batch(ctx(), text.data(), fields.data(), nfields, field_start.data(),
+                                    nsec, dst.data(), dst.size(), sections.data(), &need,
+                                    QH_WHERE_HOST);
         if (rv == QH_ERR_NOMEM && need > dst.size()) {
           dst.resize(need);
           continue;

@@ -24,6 +24,14 @@
 
 #include "../../include/qhuff.h"
 
+/* The choice itself is qh_plan_core.h, the source the kernel of qh_plan.inc
+ * compiles; here its bytes are read with memcmp. */
+#define QH_EMIT_TOKEN(p, n) qh_qpack_lookup_token((p), (n))
+#define QH_PLAN_TOKEN(t, plain, off, len) qh_qpack_lookup_token((plain) + (off), (len))
+#define QH_PLAN_VALUE(v, plain, off, len) const uint8_t *const v = (plain) + (off)
+#define QH_PLAN_EQ(tb, v, len) (memcmp((tb), (v), (len)) == 0)
+#include "qh_plan_core.h"
+
 #define QH_NSTATIC 99
 
 static const char *const kStaticName[QH_NSTATIC] = {
@@ -90,7 +98,8 @@ static const char *const kStaticValue[QH_NSTATIC] = {
 
 /* Per entry: its name's token, and the next entry of the same name (or -1);
  * per token < 99: the name's first entry (or -1). */
-static int32_t g_tok[QH_NSTATIC], g_next[QH_NSTATIC], g_first[QH_NSTATIC];
+static int32_t g_tok[QH_NSTATIC];
+static int8_t g_next[QH_NSTATIC], g_first[QH_NSTATIC];
 static pthread_once_t g_once = PTHREAD_ONCE_INIT;
 
 static void static_init(void) {
@@ -110,9 +119,17 @@ static void static_init(void) {
     }
     for (j = i + 1; j < QH_NSTATIC && g_tok[j] != t; ++j)
       ;
-    g_next[i] = j < QH_NSTATIC ? j : -1;
-    g_first[t] = i;
+    g_next[i] = (int8_t)(j < QH_NSTATIC ? j : -1);
+    g_first[t] = (int8_t)i;
   }
+}
+
+/* (library-internal, like qh_emit_static_blob: qh_plan.inc uploads the same
+ * chains to the device) */
+void qh_plan_static_chains(const int8_t **first, const int8_t **next) {
+  pthread_once(&g_once, static_init);
+  *first = g_first;
+  *next = g_next;
 }
 
 QH_EXPORT int qh_qpack_static_entry(size_t idx, const uint8_t **name,
@@ -136,51 +153,24 @@ QH_EXPORT int qh_qpack_static_entry(size_t idx, const uint8_t **name,
   return 0;
 }
 
-#define QH_TOKEN_AUTHORIZATION 45 /* nghttp3.h nghttp3_qpack_token */
-#define QH_TOKEN_COOKIE 68
+void qh_emit_static_blob(const qh_static_rec **recs, const uint8_t **bytes, size_t *nbytes);
 
 QH_EXPORT int qh_qpack_plan_fields(const uint8_t *plain, const qh_span_in *strs,
                                    size_t nfields, const uint8_t *never,
                                    qh_field_line *lines) {
-  size_t i;
+  qh_plan_tab t;
+  size_t i, nbytes;
   if (nfields && (plain == NULL || strs == NULL || lines == NULL)) {
     return QH_ERR_INVALID_ARGUMENT;
   }
   pthread_once(&g_once, static_init);
+  qh_emit_static_blob(&t.stat, &t.bytes, &nbytes);
+  t.first = g_first;
+  t.next = g_next;
+  t.tok = NULL;
   for (i = 0; i < nfields; ++i) {
     const qh_span_in *nm = &strs[2 * i], *v = &strs[2 * i + 1];
-    const uint8_t *name = plain + nm->off, *value = plain + v->off;
-    int nv_never = never && never[i];
-    int32_t token = qh_qpack_lookup_token(name, nm->len);
-    qh_field_line *l = &lines[i];
-    memset(l, 0, sizeof(*l));
-    l->flags = nv_never ? QH_FL_NEVER : 0;
-    l->name = (int32_t)(2 * i);
-    l->value = (int32_t)(2 * i + 1);
-    if (token >= 0 && token < QH_NSTATIC && g_first[token] >= 0) {
-      int mode_never = nv_never || token == QH_TOKEN_AUTHORIZATION ||
-                       (token == QH_TOKEN_COOKIE && v->len < 20);
-      int32_t e = g_first[token];
-      if (!mode_never) {
-        for (; e >= 0; e = g_next[e]) {
-          size_t vl = strlen(kStaticValue[e]);
-          if (vl == v->len && memcmp(kStaticValue[e], value, vl) == 0) {
-            break;
-          }
-        }
-        if (e >= 0) {
-          l->opcode = QH_FL_INDEXED;
-          l->index = (uint64_t)e;
-          l->name = l->value = -1;
-          continue;
-        }
-      }
-      l->opcode = QH_FL_INDEXED_NAME;
-      l->index = (uint64_t)g_first[token];
-      l->name = -1;
-      continue;
-    }
-    l->opcode = QH_FL_LITERAL;
+    qh_plan_field(&t, plain, nm->off, nm->len, v->off, v->len, never && never[i], i, &lines[i]);
   }
   return 0;
 }

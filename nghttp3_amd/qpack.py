@@ -132,6 +132,10 @@ def _load():
         lib.qh_encode_sections_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, u64, vp,
                                                  c.POINTER(u64), i32]
         lib.qh_encode_sections_batch.restype = i32
+        lib.qh_plan_fields_batch.argtypes = [vp, vp, vp, sz, vp, vp, i32]
+        lib.qh_plan_fields_batch.restype = i32
+        lib.qh_encode_fields_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, u64, vp, c.POINTER(u64), i32]
+        lib.qh_encode_fields_batch.restype = i32
         lib.qh_dtable_new.argtypes = [c.POINTER(vp), u64]
         lib.qh_dtable_new.restype = i32
         lib.qh_dtable_del.argtypes = [vp]
@@ -818,11 +822,40 @@ def plan_fields(plain, strs, never=None):
     return lines[:nf]
 
 
+def plan_fields_host(codec: HuffmanBatchCodec, plain, strs, never=None):
+    """plan_fields on the GPU over host arrays (qh_plan_fields_batch,
+    staged): the same lines, byte for byte."""
+    lib = _load()
+    plain = _u8(plain)
+    if plain.size == 0:
+        plain = np.zeros(1, dtype=np.uint8)
+    strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
+    nf = strs.size // 2
+    lines = np.zeros(max(nf, 1), dtype=FIELD_LINE_DTYPE)
+    nv = None if never is None else np.ascontiguousarray(never, dtype=np.uint8)
+    _lib.check(lib.qh_plan_fields_batch(codec._ctx, _vp(plain), _vp(strs), nf,
+                                        None if nv is None else _vp(nv), _vp(lines),
+                                        _lib.QH_WHERE_HOST), "qh_plan_fields_batch")
+    return lines[:nf]
+
+
+def plan_fields_dev(codec: HuffmanBatchCodec, plain, strs, never, lines):
+    """Device-resident form over torch tensors (plain uint8, strs int64
+    [2 * nfields, 2] in SPAN_IN layout, never uint8 [nfields] or None, lines
+    uint8 [nfields * 24]); asynchronous on the codec stream, no host wait."""
+    lib = _load()
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    _lib.check(lib.qh_plan_fields_batch(codec._ctx, p(plain), p(strs), strs.shape[0] // 2, p(never),
+                                        p(lines), _lib.QH_WHERE_DEVICE), "qh_plan_fields_batch")
+
+
 class FieldSectionEncoder:
     """Whole field sections out of one qh_encode_sections_batch call: the
     count kernels, Huffman iff shorter, the encode kernels over the picked
     strings, then the representation writer kernel (byte for byte
-    qh_qpack_write_sections)."""
+    qh_qpack_write_sections).  ``encode_fields`` / ``encode_fields_dev``
+    start from fields instead of planned lines (qh_encode_fields_batch: the
+    plan kernel, then the same writer)."""
 
     def __init__(self, device: int = 0, codec: HuffmanBatchCodec | None = None):
         self.codec = codec or HuffmanBatchCodec(device)
@@ -868,4 +901,45 @@ class FieldSectionEncoder:
                                           dst.numel(), p(sections), ctypes.byref(need),
                                           _lib.QH_WHERE_DEVICE)
         _lib.check(rv, "qh_encode_sections_batch")
+        return need.value
+
+    def encode_fields(self, plain, fields, field_start):
+        """Host arrays: fields (FIELD_DTYPE; offsets into plain) of sections
+        [field_start[b], field_start[b + 1]) -> (dst uint8, sections
+        SPAN_IN_DTYPE), the bytes of write_sections(plan_fields(...))."""
+        lib = _load()
+        plain = _u8(plain)
+        if plain.size == 0:
+            plain = np.zeros(1, dtype=np.uint8)
+        fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
+        if fields.size == 0:
+            fields = np.zeros(1, dtype=FIELD_DTYPE)[:0]
+        field_start = np.ascontiguousarray(field_start, dtype=np.uint32)
+        nsec = field_start.size - 1
+        sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
+        need = ctypes.c_uint64(0)
+        dst = np.zeros(64, dtype=np.uint8)
+        for _ in range(2):
+            rv = lib.qh_encode_fields_batch(self.codec._ctx, _vp(plain), _vp(fields), fields.size,
+                                            _vp(field_start), nsec, _vp(dst), dst.size, _vp(sections),
+                                            ctypes.byref(need), _lib.QH_WHERE_HOST)
+            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
+                dst = np.zeros(int(need.value), dtype=np.uint8)
+                continue
+            _lib.check(rv, "qh_encode_fields_batch")
+            break
+        return dst[:need.value], sections[:nsec]
+
+    def encode_fields_dev(self, plain, fields, nfields, field_start, dst, sections):
+        """Device-resident form over torch tensors, emit_fields_dev's as they
+        are: plain uint8 (its `out`), fields uint8 [>= nfields * 32],
+        field_start int32 [nsec + 1], dst uint8, sections int64 [nsec, 2].
+        Returns dst_need; raises on QH_ERR_NOMEM."""
+        lib = _load()
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        need = ctypes.c_uint64(0)
+        rv = lib.qh_encode_fields_batch(self.codec._ctx, p(plain), p(fields), int(nfields),
+                                        p(field_start), field_start.shape[0] - 1, p(dst), dst.numel(),
+                                        p(sections), ctypes.byref(need), _lib.QH_WHERE_DEVICE)
+        _lib.check(rv, "qh_encode_fields_batch")
         return need.value
