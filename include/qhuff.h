@@ -819,6 +819,113 @@ QH_EXPORT int qh_encode_fields_batch(qh_ctx *ctx, const uint8_t *plain,
                                      uint64_t dst_cap, qh_span_in *sections,
                                      uint64_t *dst_need, int where);
 
+/* ---- Field representations against a dynamic table state ----------------
+ * The choice nghttp3_qpack_encoder_encode_nv (qpack.c:1455-1628) makes when
+ * nothing can be inserted: every insert and the duplicate sit behind
+ * qpack_encoder_can_index_nv / _duplicate (:1518-1521, :1544, :1570-1574,
+ * :1608), which end in qpack_encoder_can_index (:1378-1413) and answer 0
+ * while the table has no room and its oldest entry is pinned by an
+ * unacknowledged section (:1408-1410).  The choice is then a function of
+ * the field, the table state and (krcnt, allow_blocking): references to
+ * entries already in the table, in this order (static lookup :1630-1660,
+ * dynamic lookup :1662-1685 over encoder_qpack_map_find :799-835):
+ *   1. a static entry with the name and value: Indexed (static);
+ *   2. the newest referenceable entry with the name and value: Indexed
+ *      (dynamic), QH_FL_DYNAMIC, index = base - a - 1 (:1824-1837);
+ *   3. a static name: Literal With Name Reference (static);
+ *   4. the newest referenceable entry with the name: Literal With Name
+ *      Reference (dynamic), index = base - a - 1 (:1911-1930), N from the
+ *      field's flag alone;
+ *   5. Literal With Literal Name.
+ * Entry a is referenceable iff live_lo <= a < insert_count in the section's
+ * view and a + 1 <= ref_limit (:816, :819).  In NEVER mode (the flag,
+ * authorization, a cookie under 20 bytes, :1307-1321) no value is matched
+ * (:1643-1645, :822-824): steps 1 and 2 do not apply.  base is the view's
+ * insert_count (:1163); no index is post-base.
+ * Per section: max_cnt / min_cnt = the largest / smallest a + 1 over the
+ * entries its lines reference (0 / UINT64_MAX when there is none), what
+ * qpack_encoder_add_stream_ref records (:1193-1194), and the prefix of
+ * write_field_section_prefix (:2424-2460): ricnt = max_cnt ? max_cnt %
+ * (2 * max_entries) + 1 : 0, sign 0, delta_base = base - max_cnt (so a
+ * section without a dynamic reference has delta_base = base, as the
+ * reference writes it).
+ *
+ * A key per log entry lets the lookup read an entry's bytes only when the
+ * key already agrees (a hash never decides: the name's bytes, when its
+ * token is -1, and the value's are always compared).  The log is
+ * append-only, so keys are: keys[first, first + n) are computed from
+ * entries[first, first + n); a caller extends its array as the log grows. */
+typedef struct qh_dyn_key { /* 16 B, one per log entry */
+  uint32_t name_id;    /* the token, or 0x80000000 | hash of the name bytes
+                          when the token is -1 */
+  uint32_t name_len, value_len;
+  uint32_t value_hash; /* 32-bit hash of the value bytes */
+} qh_dyn_key;
+
+/* The table states of a planning call: a host struct; its pointers are host
+ * pointers for the host function and QH_WHERE_HOST, HBM for QH_WHERE_DEVICE.
+ * Section b is planned against views[section_view[b]]; an index >= nviews,
+ * or a view whose max_entries is 0, plans as no table.  An entry is never
+ * matched when its record lies outside [0, nentries) or its strings outside
+ * [0, nbytes). */
+typedef struct qh_plan_dyn {
+  const qh_dtable_view *views;
+  size_t nviews;
+  const uint32_t *section_view; /* nsections; NULL: views[0] */
+  const uint64_t *ref_limit;    /* nsections; NULL: the view's insert_count
+                                   (blocking allowed); else krcnt */
+  const qh_dyn_entry *dyn_entries;
+  size_t nentries;
+  const qh_dyn_key *dyn_keys; /* nentries */
+  const uint8_t *dyn_bytes;
+  uint64_t nbytes;
+} qh_plan_dyn;
+
+/* keys[first, first + n) of the log (entries, nentries; bytes, nbytes); an
+ * entry whose strings do not lie in the log gets zero hashes.  Host C, and
+ * on the GPU one lane per entry (strings read as qh_check_fields_batch reads
+ * them; QH_WHERE_DEVICE asynchronous, QH_WHERE_HOST staged and blocking). */
+QH_EXPORT int qh_qpack_dyn_keys(const qh_dyn_entry *entries, size_t nentries,
+                                const uint8_t *bytes, uint64_t nbytes,
+                                size_t first, size_t n, qh_dyn_key *keys);
+QH_EXPORT int qh_dyn_keys_batch(qh_ctx *ctx, const qh_dyn_entry *entries,
+                                size_t nentries, const uint8_t *bytes,
+                                uint64_t nbytes, size_t first, size_t n,
+                                qh_dyn_key *keys, int where);
+
+/* The lines, prefixes and reference counts of nsections sections: section b
+ * is fields [field_start[b], field_start[b + 1]) of (strs, never) as
+ * qh_qpack_plan_fields takes them.  prefixes (nsections) is required when
+ * nsections > 0; max_cnt / min_cnt (nsections) are optional.  With dyn ==
+ * NULL or nviews == 0 the lines are qh_qpack_plan_fields's and the prefixes
+ * all zero.  Host C; qh_plan_fields_dyn_batch is the same on the GPU, lines
+ * byte for byte (csrc/qh_plan_core.h is the source of both), with no host
+ * wait for QH_WHERE_DEVICE.  QH_ERR_INVALID_ARGUMENT: dyn_keys NULL with
+ * nentries > 0, section_view without views, nfields > 2^30. */
+QH_EXPORT int qh_qpack_plan_fields_dyn(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, qh_field_line *lines, qh_section_prefix *prefixes,
+    uint64_t *max_cnt, uint64_t *min_cnt);
+QH_EXPORT int qh_plan_fields_dyn_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, qh_field_line *lines, qh_section_prefix *prefixes,
+    uint64_t *max_cnt, uint64_t *min_cnt, int where);
+
+/* qh_encode_fields_batch with the plan above: the fields planned against
+ * dyn into context scratch, the prefixes formed on the device, then the
+ * sections written as qh_encode_sections_batch writes them.  max_cnt /
+ * min_cnt (nsections, optional) are what the caller keeps to pin its
+ * entries until the sections are acknowledged.  Returns and the
+ * QH_ERR_NOMEM contract are qh_encode_sections_batch's; QH_WHERE_DEVICE
+ * keeps that call's single host wait and adds none. */
+QH_EXPORT int qh_encode_fields_dyn_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_field *fields, size_t nfields,
+    const uint32_t *field_start, size_t nsections, const qh_plan_dyn *dyn,
+    uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint64_t *max_cnt, uint64_t *min_cnt, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

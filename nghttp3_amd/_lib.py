@@ -169,6 +169,12 @@ EXPORTED_FUNCTIONS = (
     # field representations on the GPU (csrc/qh_plan.inc)
     "qh_plan_fields_batch",
     "qh_encode_fields_batch",
+    # ... against a frozen dynamic table (csrc/qh_static.c, csrc/qh_plan_dyn.inc)
+    "qh_qpack_dyn_keys",
+    "qh_dyn_keys_batch",
+    "qh_qpack_plan_fields_dyn",
+    "qh_plan_fields_dyn_batch",
+    "qh_encode_fields_dyn_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -72,4 +72,5 @@
 #include "qh_enc_sections.inc"  // whole field sections out: count -> pick -> encode -> write
 #include "qh_emit.inc"          // decoded fields: resolve indices -> scan -> gather names and values
 #include "qh_plan.inc"          // fields -> field lines (the encoder's static-table choice) -> sections
+#include "qh_plan_dyn.inc"      // ... against a frozen dynamic table: keys, references, prefixes
 

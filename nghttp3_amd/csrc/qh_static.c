@@ -174,3 +174,93 @@ QH_EXPORT int qh_qpack_plan_fields(const uint8_t *plain, const qh_span_in *strs,
   }
   return 0;
 }
+
+/* ---- the choice against a frozen dynamic table (qh_plan_core.h) ---- */
+
+QH_EXPORT int qh_qpack_dyn_keys(const qh_dyn_entry *entries, size_t nentries,
+                                const uint8_t *bytes, uint64_t nbytes,
+                                size_t first, size_t n, qh_dyn_key *keys) {
+  size_t i;
+  if (first > nentries || n > nentries - first) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (n && (entries == NULL || keys == NULL || (nbytes && bytes == NULL))) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  for (i = first; i < first + n; ++i) {
+    const qh_dyn_entry *e = &entries[i];
+    const int ok = qh_dyn_entry_ok(e, nbytes);
+    qh_dyn_key *k = &keys[i];
+    k->name_id = qh_dyn_name_id(
+      e->token, ok && e->token == -1 ? qh_dyn_hash(bytes + e->name_off, e->name_len) : 0);
+    k->name_len = e->name_len;
+    k->value_len = e->value_len;
+    k->value_hash = ok ? qh_dyn_hash(bytes + e->value_off, e->value_len) : 0;
+  }
+  return 0;
+}
+
+QH_EXPORT int qh_qpack_plan_fields_dyn(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, qh_field_line *lines, qh_section_prefix *prefixes,
+    uint64_t *max_cnt, uint64_t *min_cnt) {
+  static const qh_plan_dyn none;
+  qh_plan_tab t;
+  size_t b, nbytes;
+  if (nfields && (plain == NULL || strs == NULL || lines == NULL)) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (nsections && (field_start == NULL || prefixes == NULL)) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (nfields > ((size_t)1 << 30) || (nsections == 0 && nfields)) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (dyn && dyn->section_view && dyn->views == NULL) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (dyn == NULL || dyn->nviews == 0) {
+    dyn = &none;
+  }
+  if (dyn->nviews &&
+      (dyn->views == NULL || (dyn->nentries && (dyn->dyn_keys == NULL || dyn->dyn_entries == NULL)) ||
+       (dyn->nbytes && dyn->dyn_bytes == NULL))) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (nsections && (field_start[0] != 0 || field_start[nsections] != nfields)) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  pthread_once(&g_once, static_init);
+  qh_emit_static_blob(&t.stat, &t.bytes, &nbytes);
+  t.first = g_first;
+  t.next = g_next;
+  t.tok = NULL;
+  for (b = 0; b < nsections; ++b) {
+    qh_plan_dyn_sec s;
+    uint64_t mx = 0, mn = UINT64_MAX;
+    size_t i;
+    if (field_start[b] > field_start[b + 1] || field_start[b + 1] > nfields) {
+      return QH_ERR_INVALID_ARGUMENT;
+    }
+    qh_plan_dyn_section(dyn, b, &s);
+    for (i = field_start[b]; i < field_start[b + 1]; ++i) {
+      const qh_span_in *nm = &strs[2 * i], *v = &strs[2 * i + 1];
+      uint64_t ref1;
+      qh_plan_field_dyn(&t, dyn, &s, plain, nm->off, nm->len, v->off, v->len,
+                        never && never[i], i, &lines[i], &ref1);
+      if (ref1) {
+        mx = ref1 > mx ? ref1 : mx;
+        mn = ref1 < mn ? ref1 : mn;
+      }
+    }
+    qh_plan_prefix(&s, mx, &prefixes[b]);
+    if (max_cnt) {
+      max_cnt[b] = mx;
+    }
+    if (min_cnt) {
+      min_cnt[b] = mn;
+    }
+  }
+  return 0;
+}

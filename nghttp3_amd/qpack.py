@@ -52,6 +52,9 @@ DYN_ENTRY_DTYPE = np.dtype([("name_off", "<u8"), ("value_off", "<u8"), ("name_le
 VIEW_DTYPE = np.dtype([("ent_base", "<i8"), ("live_lo", "<u8"), ("insert_count", "<u8"),
                        ("max_entries", "<u8"), ("reserved", "<u8")])
 assert FIELD_DTYPE.itemsize == 32 and DYN_ENTRY_DTYPE.itemsize == 32 and VIEW_DTYPE.itemsize == 40
+DYN_KEY_DTYPE = np.dtype([("name_id", "<u4"), ("name_len", "<u4"), ("value_len", "<u4"),
+                          ("value_hash", "<u4")])
+assert DYN_KEY_DTYPE.itemsize == 16
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -60,6 +63,15 @@ EMIT_QIF = 0x1
 class qh_section_prefix(ctypes.Structure):
     _fields_ = [("ricnt", ctypes.c_uint64), ("delta_base", ctypes.c_uint64),
                 ("sign", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class qh_plan_dyn(ctypes.Structure):
+    """include/qhuff.h qh_plan_dyn (the table states of a planning call)."""
+    _fields_ = [("views", ctypes.c_void_p), ("nviews", ctypes.c_size_t),
+                ("section_view", ctypes.c_void_p), ("ref_limit", ctypes.c_void_p),
+                ("dyn_entries", ctypes.c_void_p), ("nentries", ctypes.c_size_t),
+                ("dyn_keys", ctypes.c_void_p), ("dyn_bytes", ctypes.c_void_p),
+                ("nbytes", ctypes.c_uint64)]
 
 
 SECTIONS_DTABLE0 = 0x1
@@ -136,6 +148,18 @@ def _load():
         lib.qh_plan_fields_batch.restype = i32
         lib.qh_encode_fields_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, u64, vp, c.POINTER(u64), i32]
         lib.qh_encode_fields_batch.restype = i32
+        lib.qh_qpack_dyn_keys.argtypes = [vp, sz, vp, u64, sz, sz, vp]
+        lib.qh_qpack_dyn_keys.restype = i32
+        lib.qh_dyn_keys_batch.argtypes = [vp, vp, sz, vp, u64, sz, sz, vp, i32]
+        lib.qh_dyn_keys_batch.restype = i32
+        dynp = c.POINTER(qh_plan_dyn)
+        lib.qh_qpack_plan_fields_dyn.argtypes = [vp, vp, sz, vp, vp, sz, dynp, vp, vp, vp, vp]
+        lib.qh_qpack_plan_fields_dyn.restype = i32
+        lib.qh_plan_fields_dyn_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz, dynp, vp, vp, vp, vp, i32]
+        lib.qh_plan_fields_dyn_batch.restype = i32
+        lib.qh_encode_fields_dyn_batch.argtypes = [vp, vp, vp, sz, vp, sz, dynp, vp, u64, vp,
+                                                   c.POINTER(u64), vp, vp, i32]
+        lib.qh_encode_fields_dyn_batch.restype = i32
         lib.qh_dtable_new.argtypes = [c.POINTER(vp), u64]
         lib.qh_dtable_new.restype = i32
         lib.qh_dtable_del.argtypes = [vp]
@@ -272,9 +296,10 @@ def write_literal(fb: int, prefix: int, name: bytes, value: bytes) -> bytes:
                   bound=lib.qh_qpack_literal_bound(nm.size, v.size))
 
 
-def write_sections(plain, strs, lines, line_start):
+def write_sections(plain, strs, lines, line_start, prefixes=None):
     """Batch writer (qh_qpack_write_sections): -> (dst uint8, sections
-    SPAN_IN_DTYPE), every section with a zero prefix."""
+    SPAN_IN_DTYPE), every section with a zero prefix, or with prefixes[b]
+    (PREFIX_DTYPE)."""
     lib = _load()
     plain = _u8(plain)
     strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
@@ -284,8 +309,10 @@ def write_sections(plain, strs, lines, line_start):
     cap = int(strs["len"].sum(dtype=np.uint64)) + 20 * lines.size + 20 * nsec + 1
     dst = np.zeros(cap, dtype=np.uint8)
     sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
+    pf = None if prefixes is None else np.ascontiguousarray(prefixes, dtype=PREFIX_DTYPE)
     _lib.check(lib.qh_qpack_write_sections(_vp(plain), _vp(strs), _vp(lines), _vp(line_start), nsec,
-                                           None, _vp(dst), cap, _vp(sections)),
+                                           None if pf is None else _vp(pf), _vp(dst), cap,
+                                           _vp(sections)),
                "qh_qpack_write_sections")
     end = int(sections["off"][nsec - 1] + sections["len"][nsec - 1]) if nsec else 0
     return dst[:end], sections[:nsec]
@@ -772,19 +799,34 @@ class DynamicTable:
         """A copy of the byte log."""
         return self._log(self._lib.qh_dtable_bytes, np.uint8)
 
-    def to_device(self, device):
-        """-> {"views" uint8 [40], "entries" uint8 [n * 32], "bytes" uint8}
-        torch tensors on `device` holding the current state and the log.
-        Only the records and bytes appended since the last upload are
-        copied (the tensors are kept, with room to grow)."""
-        import torch
+    def keys(self):
+        """The entry log's keys (DYN_KEY_DTYPE, qh_qpack_dyn_keys): kept, and
+        only the tail appended since the last call is computed."""
         ents, byts = self.entries(), self.bytes()
+        have = getattr(self, "_keys", None)
+        if have is None:
+            have = np.zeros(0, dtype=DYN_KEY_DTYPE)
+        if ents.size > have.size:
+            have = dyn_keys(ents, byts, first=have.size, keys=have)
+        self._keys = have
+        return have
+
+    def to_device(self, device):
+        """-> {"views" uint8 [40], "entries" uint8 [n * 32], "bytes" uint8,
+        "keys" uint8 [n * 16], "nentries", "nbytes"} torch tensors on
+        `device` holding the current state, the log and its keys.  Only the
+        records, keys and bytes appended since the last upload are copied
+        (the tensors are kept, with room to grow)."""
+        import torch
+        ents, byts, keys = self.entries(), self.bytes(), self.keys()
         d = self._dev
         if d is None or d["device"] != torch.device(device):
-            d = self._dev = {"device": torch.device(device), "ne": 0, "nb": 0,
+            d = self._dev = {"device": torch.device(device), "ne": 0, "nb": 0, "nk": 0,
                              "entries": torch.empty(0, dtype=torch.uint8, device=device),
-                             "bytes": torch.empty(0, dtype=torch.uint8, device=device)}
-        for key, have, host in (("entries", "ne", ents.view(np.uint8)), ("bytes", "nb", byts)):
+                             "bytes": torch.empty(0, dtype=torch.uint8, device=device),
+                             "keys": torch.empty(0, dtype=torch.uint8, device=device)}
+        for key, have, host in (("entries", "ne", ents.view(np.uint8)), ("bytes", "nb", byts),
+                                ("keys", "nk", keys.view(np.uint8))):
             if host.size > d[key].numel():  # grow: keep what is there
                 t = torch.empty(max(2 * host.size, 4096), dtype=torch.uint8, device=device)
                 t[:d[have]] = d[key][:d[have]]
@@ -793,7 +835,136 @@ class DynamicTable:
                 d[key][d[have]:host.size] = torch.from_numpy(host[d[have]:].copy()).to(device)
                 d[have] = host.size
         views = torch.from_numpy(self.view().view(np.uint8).copy()).to(device)
-        return {"views": views, "entries": d["entries"], "bytes": d["bytes"]}
+        return {"views": views, "entries": d["entries"], "bytes": d["bytes"], "keys": d["keys"],
+                "nentries": int(ents.size), "nbytes": int(byts.size)}
+
+
+def dyn_keys(entries, dyn_bytes, first: int = 0, keys=None):
+    """qh_qpack_dyn_keys: the keys (DYN_KEY_DTYPE) of the log (entries
+    DYN_ENTRY_DTYPE, dyn_bytes).  `keys` holds those of entries [0, first)
+    already; the rest is computed and the whole array returned."""
+    lib = _load()
+    ents = np.ascontiguousarray(entries, dtype=DYN_ENTRY_DTYPE)
+    byts = _u8(dyn_bytes)
+    out = np.zeros(max(ents.size, 1), dtype=DYN_KEY_DTYPE)
+    if first:
+        out[:first] = np.ascontiguousarray(keys, dtype=DYN_KEY_DTYPE)[:first]
+    _lib.check(lib.qh_qpack_dyn_keys(_vp(ents), ents.size, _vp(byts), byts.size, first,
+                                     ents.size - first, _vp(out)), "qh_qpack_dyn_keys")
+    return out[:ents.size]
+
+
+def dyn_keys_dev(codec: HuffmanBatchCodec, entries, nentries, dyn_bytes, nbytes, first, n, keys):
+    """qh_dyn_keys_batch over torch tensors in HBM (entries uint8 [>= nentries
+    * 32], dyn_bytes uint8, keys uint8 [>= nentries * 16]): keys [first,
+    first + n); asynchronous on the codec stream."""
+    lib = _load()
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    _lib.check(lib.qh_dyn_keys_batch(codec._ctx, p(entries), nentries, p(dyn_bytes), nbytes, first, n,
+                                     p(keys), _lib.QH_WHERE_DEVICE), "qh_dyn_keys_batch")
+
+
+def _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_bytes):
+    """-> (qh_plan_dyn or None, the arrays it points into) from host arrays:
+    `table` (a DynamicTable: its log, keys and, without `views`, its current
+    state) or views / entries / keys / dyn_bytes."""
+    if table is not None:
+        views = table.view() if views is None else views
+        entries, dyn_bytes, keys = table.entries(), table.bytes(), table.keys()
+    if views is None:
+        if section_view is not None:
+            raise ValueError("section_view without views")
+        return None, ()
+    vw = np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
+    sv = None if section_view is None else np.ascontiguousarray(section_view, dtype=np.uint32)
+    rl = None if ref_limit is None else np.ascontiguousarray(ref_limit, dtype=np.uint64)
+    ents = np.zeros(0, DYN_ENTRY_DTYPE) if entries is None else \
+        np.ascontiguousarray(entries, dtype=DYN_ENTRY_DTYPE)
+    byts = _u8(b"" if dyn_bytes is None else dyn_bytes)
+    ks = dyn_keys(ents, byts) if keys is None else np.ascontiguousarray(keys, dtype=DYN_KEY_DTYPE)
+    opt = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    d = qh_plan_dyn(opt(vw), vw.size, opt(sv), opt(rl), opt(ents), ents.size, opt(ks), opt(byts),
+                    byts.size)
+    return d, (vw, sv, rl, ents, ks, byts)
+
+
+def _plan_dyn_dev(table, device, views, section_view, ref_limit, entries, keys, dyn_bytes,
+                  nentries=None, nbytes=None):
+    """The same from torch tensors in HBM (views uint8 [nviews * 40],
+    section_view int32, ref_limit int64, entries uint8 [n * 32], keys uint8
+    [n * 16], dyn_bytes uint8); `table` is uploaded with to_device."""
+    if table is not None:
+        d = table.to_device(device)
+        views = d["views"] if views is None else views
+        entries, keys, dyn_bytes = d["entries"], d["keys"], d["bytes"]
+        nentries, nbytes = d["nentries"], d["nbytes"]
+    if views is None:
+        if section_view is not None:
+            raise ValueError("section_view without views")
+        return None, ()
+    p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    if nentries is None:
+        nentries = 0 if entries is None else entries.numel() // DYN_ENTRY_DTYPE.itemsize
+    ne = nentries
+    nb = (0 if dyn_bytes is None else dyn_bytes.numel()) if nbytes is None else nbytes
+    d = qh_plan_dyn(p(views), views.numel() // VIEW_DTYPE.itemsize, p(section_view), p(ref_limit),
+                    p(entries), ne, p(keys), p(dyn_bytes), nb)
+    return d, (views, section_view, ref_limit, entries, keys, dyn_bytes)
+
+
+def plan_fields_dyn(plain, strs, never, field_start, table=None, views=None, section_view=None,
+                    ref_limit=None, entries=None, keys=None, dyn_bytes=None, codec=None):
+    """qh_qpack_plan_fields_dyn: the fields (strs[2i], strs[2i+1]) of
+    sections [field_start[b], field_start[b+1]) planned against a frozen
+    dynamic table (`table`, or views / entries / keys / dyn_bytes; section b
+    against views[section_view[b]], referencing entries a + 1 <=
+    ref_limit[b]).  -> dict: lines, prefixes (PREFIX_DTYPE), max_cnt, min_cnt.
+    With `codec` the same on the GPU over the host arrays
+    (qh_plan_fields_dyn_batch, staged)."""
+    lib = _load()
+    plain = _u8(plain)
+    if plain.size == 0:
+        plain = np.zeros(1, dtype=np.uint8)
+    strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
+    nf = strs.size // 2
+    fs = np.ascontiguousarray(field_start, dtype=np.uint32)
+    nsec = fs.size - 1
+    nv = None if never is None else np.ascontiguousarray(never, dtype=np.uint8)
+    d, keep = _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_bytes)
+    lines = np.zeros(max(nf, 1), dtype=FIELD_LINE_DTYPE)
+    pfx = np.zeros(max(nsec, 1), dtype=PREFIX_DTYPE)
+    mx = np.zeros(max(nsec, 1), dtype=np.uint64)
+    mn = np.zeros(max(nsec, 1), dtype=np.uint64)
+    dp = None if d is None else ctypes.byref(d)
+    args = (_vp(plain), _vp(strs), nf, None if nv is None else _vp(nv), _vp(fs), nsec, dp, _vp(lines),
+            _vp(pfx), _vp(mx), _vp(mn))
+    if codec is None:
+        _lib.check(lib.qh_qpack_plan_fields_dyn(*args), "qh_qpack_plan_fields_dyn")
+    else:
+        _lib.check(lib.qh_plan_fields_dyn_batch(codec._ctx, *args, _lib.QH_WHERE_HOST),
+                   "qh_plan_fields_dyn_batch")
+    del keep
+    return {"lines": lines[:nf], "prefixes": pfx[:nsec], "max_cnt": mx[:nsec], "min_cnt": mn[:nsec]}
+
+
+def plan_fields_dyn_dev(codec: HuffmanBatchCodec, plain, strs, never, field_start, lines, prefixes,
+                        max_cnt=None, min_cnt=None, table=None, views=None, section_view=None,
+                        ref_limit=None, entries=None, keys=None, dyn_bytes=None, nentries=None,
+                        nbytes=None):
+    """Device-resident form over torch tensors (plan_fields_dev's, plus
+    field_start int32 [nsec + 1], prefixes uint8 [nsec * 24], max_cnt /
+    min_cnt int64 [nsec] or None); asynchronous on the codec stream, no host
+    wait."""
+    lib = _load()
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    d, keep = _plan_dyn_dev(table, plain.device, views, section_view, ref_limit, entries, keys,
+                            dyn_bytes, nentries, nbytes)
+    _lib.check(lib.qh_plan_fields_dyn_batch(codec._ctx, p(plain), p(strs), strs.shape[0] // 2,
+                                            p(never), p(field_start), field_start.shape[0] - 1,
+                                            None if d is None else ctypes.byref(d), p(lines),
+                                            p(prefixes), p(max_cnt), p(min_cnt),
+                                            _lib.QH_WHERE_DEVICE), "qh_plan_fields_dyn_batch")
+    return keep
 
 
 def static_entry(idx: int):
@@ -903,11 +1074,19 @@ class FieldSectionEncoder:
         _lib.check(rv, "qh_encode_sections_batch")
         return need.value
 
-    def encode_fields(self, plain, fields, field_start):
+    def encode_fields(self, plain, fields, field_start, table=None, views=None, section_view=None,
+                      ref_limit=None, entries=None, keys=None, dyn_bytes=None):
         """Host arrays: fields (FIELD_DTYPE; offsets into plain) of sections
         [field_start[b], field_start[b + 1]) -> (dst uint8, sections
-        SPAN_IN_DTYPE), the bytes of write_sections(plan_fields(...))."""
+        SPAN_IN_DTYPE), the bytes of write_sections(plan_fields(...)).  With
+        `table` (a DynamicTable) or `views` (with entries / keys / dyn_bytes;
+        `section_view` / `ref_limit` as plan_fields_dyn takes them) the
+        fields are planned against it (qh_encode_fields_dyn_batch) and the
+        result is (dst, sections, max_cnt, min_cnt)."""
         lib = _load()
+        if table is not None or views is not None:
+            return self._encode_fields_dyn(plain, fields, field_start, table, views, section_view,
+                                           ref_limit, entries, keys, dyn_bytes)
         plain = _u8(plain)
         if plain.size == 0:
             plain = np.zeros(1, dtype=np.uint8)
@@ -930,14 +1109,66 @@ class FieldSectionEncoder:
             break
         return dst[:need.value], sections[:nsec]
 
-    def encode_fields_dev(self, plain, fields, nfields, field_start, dst, sections):
+    def _encode_fields_dyn(self, plain, fields, field_start, table, views, section_view, ref_limit,
+                           entries, keys, dyn_bytes):
+        lib = _load()
+        plain = _u8(plain)
+        if plain.size == 0:
+            plain = np.zeros(1, dtype=np.uint8)
+        fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
+        if fields.size == 0:
+            fields = np.zeros(1, dtype=FIELD_DTYPE)[:0]
+        field_start = np.ascontiguousarray(field_start, dtype=np.uint32)
+        nsec = field_start.size - 1
+        d, keep = _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_bytes)
+        sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
+        mx = np.zeros(max(nsec, 1), dtype=np.uint64)
+        mn = np.zeros(max(nsec, 1), dtype=np.uint64)
+        need = ctypes.c_uint64(0)
+        dst = np.zeros(64, dtype=np.uint8)
+        for _ in range(2):
+            rv = lib.qh_encode_fields_dyn_batch(
+                self.codec._ctx, _vp(plain), _vp(fields), fields.size, _vp(field_start), nsec,
+                None if d is None else ctypes.byref(d), _vp(dst), dst.size, _vp(sections),
+                ctypes.byref(need), _vp(mx), _vp(mn), _lib.QH_WHERE_HOST)
+            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
+                dst = np.zeros(int(need.value), dtype=np.uint8)
+                continue
+            _lib.check(rv, "qh_encode_fields_dyn_batch")
+            break
+        del keep
+        return dst[:need.value], sections[:nsec], mx[:nsec], mn[:nsec]
+
+    def encode_fields_dev(self, plain, fields, nfields, field_start, dst, sections, table=None,
+                          views=None, section_view=None, ref_limit=None, max_cnt=None, min_cnt=None,
+                          entries=None, keys=None, dyn_bytes=None, nentries=None, nbytes=None):
         """Device-resident form over torch tensors, emit_fields_dev's as they
         are: plain uint8 (its `out`), fields uint8 [>= nfields * 32],
         field_start int32 [nsec + 1], dst uint8, sections int64 [nsec, 2].
-        Returns dst_need; raises on QH_ERR_NOMEM."""
+        Returns dst_need; raises on QH_ERR_NOMEM.  With `table` (uploaded
+        with to_device) or views / entries / keys / dyn_bytes tensors the
+        fields are planned against the table (qh_encode_fields_dyn_batch);
+        max_cnt / min_cnt (int64 [nsec]) then receive every section's
+        reference counts, and the result is (dst_need, max_cnt, min_cnt)."""
         lib = _load()
         p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         need = ctypes.c_uint64(0)
+        if table is not None or views is not None:
+            import torch
+            nsec = field_start.shape[0] - 1
+            d, keep = _plan_dyn_dev(table, plain.device, views, section_view, ref_limit, entries,
+                                    keys, dyn_bytes, nentries, nbytes)
+            if max_cnt is None:
+                max_cnt = torch.empty(max(nsec, 1), dtype=torch.int64, device=plain.device)
+            if min_cnt is None:
+                min_cnt = torch.empty(max(nsec, 1), dtype=torch.int64, device=plain.device)
+            rv = lib.qh_encode_fields_dyn_batch(self.codec._ctx, p(plain), p(fields), int(nfields),
+                                                p(field_start), nsec, ctypes.byref(d), p(dst),
+                                                dst.numel(), p(sections), ctypes.byref(need),
+                                                p(max_cnt), p(min_cnt), _lib.QH_WHERE_DEVICE)
+            _lib.check(rv, "qh_encode_fields_dyn_batch")
+            del keep  # (the call has waited for the totals)
+            return need.value, max_cnt, min_cnt
         rv = lib.qh_encode_fields_batch(self.codec._ctx, p(plain), p(fields), int(nfields),
                                         p(field_start), field_start.shape[0] - 1, p(dst), dst.numel(),
                                         p(sections), ctypes.byref(need), _lib.QH_WHERE_DEVICE)

@@ -1,0 +1,300 @@
+"""qh_dyn_keys_batch, qh_plan_fields_dyn_batch and qh_encode_fields_dyn_batch
+(the kernels of csrc/qh_plan_dyn.inc) against the host functions on the
+cases of tests/dyn_plan_cases.py: keys, lines (24 raw bytes each), prefixes,
+max_cnt and min_cnt byte for byte, from HBM and through host memory; the
+sections byte for byte the host writer's, the QH_ERR_NOMEM contract, garbage
+in the unread qh_field members; the closure fields -> sections -> fields on
+the device against the same views; the static planner's results when there
+is no table; scratch reuse.  Every output has a sentinel behind it that must
+survive, and every input lies on a 4 KiB boundary, so that the page-edge
+case's strings end where the case says."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import dyn_plan_cases as dc
+import plan_cases as pc
+from nghttp3_amd import _lib, qpack
+from nghttp3_amd.qpack_huffman import SPAN_IN_DTYPE
+
+pytestmark = pytest.mark.gpu
+
+PATTERN = 0xA5
+CASES = dc.names()
+UINT64_MAX = (1 << 64) - 1
+
+
+@pytest.fixture(scope="module")
+def enc(codec):
+    return qpack.FieldSectionEncoder(codec=codec)
+
+
+def _cuda(a):
+    """The array's bytes as a uint8 tensor in HBM that starts on a 4 KiB
+    boundary (and is never null)."""
+    import torch
+    a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    t = torch.empty(a.size + 2 * dc.PAGE, dtype=torch.uint8, device="cuda")
+    at = (-t.data_ptr()) % dc.PAGE
+    v = t[at:at + a.size]
+    if a.size:
+        v.copy_(torch.from_numpy(a.copy()))
+    return v
+
+
+def _filled(nbytes):
+    """An output of nbytes with a 64-byte sentinel behind it."""
+    import torch
+    return torch.full((nbytes + 64,), PATTERN, dtype=torch.uint8, device="cuda")
+
+
+def _host(t, nbytes):
+    got = t.cpu().numpy().reshape(-1).view(np.uint8)
+    assert (got[nbytes:] == PATTERN).all(), "the sentinel behind an output was written"
+    return got[:nbytes]
+
+
+class Dev:
+    """A case's inputs in HBM."""
+
+    def __init__(self, name):
+        import torch
+        h = dc.host(name)
+        tab = h["tab"]
+        self.h, self.tab = h, tab
+        self.n = h["strs"].size // 2
+        self.nsec = h["fs"].size - 1
+        self.plain = _cuda(h["plain"])
+        self.strs = _cuda(h["strs"]).view(torch.int64).reshape(-1, 2)
+        self.never = _cuda(h["never"])
+        self.fs = _cuda(h["fs"]).view(torch.int32)
+        self.dyn = dict(views=_cuda(tab["views"]),
+                        section_view=None if h["sv"] is None else _cuda(h["sv"]).view(torch.int32),
+                        ref_limit=None if h["rl"] is None else _cuda(h["rl"]).view(torch.int64),
+                        entries=_cuda(tab["entries"]), keys=_cuda(tab["keys"]),
+                        dyn_bytes=_cuda(tab["bytes"]), nentries=tab["entries"].size,
+                        nbytes=tab["bytes"].size)
+
+
+def plan_dev(codec, d):
+    """-> (lines, prefixes, max_cnt, min_cnt) bytes of one device call."""
+    import torch
+    lines, pfx = _filled(d.n * 24), _filled(d.nsec * 24)
+    mx, mn = _filled(d.nsec * 8), _filled(d.nsec * 8)
+    keep = qpack.plan_fields_dyn_dev(codec, d.plain, d.strs, d.never, d.fs, lines, pfx,
+                                     mx[:d.nsec * 8].view(torch.int64), mn[:d.nsec * 8].view(torch.int64),
+                                     **d.dyn)
+    codec.sync()
+    del keep
+    return (_host(lines, d.n * 24).tobytes(), _host(pfx, d.nsec * 24).tobytes(),
+            _host(mx, d.nsec * 8).tobytes(), _host(mn, d.nsec * 8).tobytes())
+
+
+def want_plan(h):
+    p = h["plan"]
+    return (p["lines"].tobytes(), p["prefixes"].tobytes(), p["max_cnt"].tobytes(), p["min_cnt"].tobytes())
+
+
+@pytest.mark.parametrize("name", ["strings", "page-edges", "size-65", "mixed-corpus", "two-logs"])
+def test_keys_on_the_device(codec, name):
+    tab = dc.host(name)["tab"]
+    ne, nb = tab["entries"].size, tab["bytes"].size
+    d_e, d_b = _cuda(tab["entries"]), _cuda(tab["bytes"])
+    one, two = _filled(ne * 16), _filled(ne * 16)
+    qpack.dyn_keys_dev(codec, d_e, ne, d_b, nb, 0, ne, one)
+    cut = ne // 3
+    qpack.dyn_keys_dev(codec, d_e, ne, d_b, nb, 0, cut, two)
+    qpack.dyn_keys_dev(codec, d_e, ne, d_b, nb, cut, ne - cut, two)
+    codec.sync()
+    want = tab["keys"].tobytes()
+    assert _host(one, ne * 16).tobytes() == want
+    assert _host(two, ne * 16).tobytes() == want
+    # and through host memory
+    lib = qpack._load()
+    got = np.full((ne + 1) * 16, PATTERN, dtype=np.uint8).view(qpack.DYN_KEY_DTYPE)
+    rv = lib.qh_dyn_keys_batch(codec._ctx, qpack._vp(tab["entries"]), ne, qpack._vp(tab["bytes"]), nb, 0,
+                               ne, qpack._vp(got), _lib.QH_WHERE_HOST)
+    assert rv == 0 and got[:ne].tobytes() == want and got[ne:].tobytes() == bytes([PATTERN]) * 16
+
+
+def test_a_table_s_device_keys_grow_at_the_tail():
+    import torch
+    c = dc.by_name("size-65")
+    t = qpack.DynamicTable(dc.BIG)
+    try:
+        parts = dc.chunks(c.tables[0][1][:30]) + dc.chunks(c.tables[0][1][30:])
+        for data, _ in parts:
+            if data:
+                t.apply(data)
+            d = t.to_device(torch.device("cuda", 0))
+            ne = t.entries().size
+            assert d["nentries"] == ne and d["nbytes"] == t.bytes().size
+            assert d["keys"].cpu().numpy()[:ne * 16].tobytes() == \
+                qpack.dyn_keys(t.entries(), t.bytes()).tobytes()
+            assert d["entries"].cpu().numpy()[:ne * 32].tobytes() == t.entries().tobytes()
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_plan_on_the_device_and_through_host_memory(codec, name):
+    d = Dev(name)
+    assert plan_dev(codec, d) == want_plan(d.h)
+    h, tab = d.h, d.tab
+    got = qpack.plan_fields_dyn(h["plain"], h["strs"], h["never"], h["fs"], views=tab["views"],
+                                section_view=h["sv"], ref_limit=h["rl"], entries=tab["entries"],
+                                keys=tab["keys"], dyn_bytes=tab["bytes"], codec=codec)
+    assert (got["lines"].tobytes(), got["prefixes"].tobytes(), got["max_cnt"].tobytes(),
+            got["min_cnt"].tobytes()) == want_plan(h)
+
+
+def fields_of(strs, never, garbage=False):
+    """qh_field records as qh_emit_fields_batch writes them with `out`; with
+    garbage in the members the planner does not read."""
+    n = strs.size // 2
+    f = np.zeros(n, dtype=qpack.FIELD_DTYPE)
+    f["name_off"], f["name_len"] = strs["off"][0::2], strs["len"][0::2]
+    f["value_off"], f["value_len"] = strs["off"][1::2], strs["len"][1::2]
+    f["flags"] = (np.asarray(never, np.uint8) != 0) * qpack.FL_NEVER
+    f["name_where"] = f["value_where"] = qpack.IN_OUT
+    f["token"] = -1
+    if garbage:
+        rng = np.random.default_rng(0x5EED0A12)
+        f["name_where"] = rng.integers(0, 256, n)
+        f["value_where"] = rng.integers(0, 256, n)
+        f["token"] = rng.integers(-2 ** 31, 2 ** 31, n)
+        f["reserved"] = rng.integers(0, 256, n)
+        f["flags"] |= (rng.integers(0, 64, n) << 2).astype(np.uint8)  # (bits other than QH_FL_NEVER)
+    return f
+
+
+def encode_dev(enc, d, d_fields, cap):
+    """-> (rv, need, dst, sections, max_cnt, min_cnt) of one raw
+    qh_encode_fields_dyn_batch call."""
+    import torch
+    dst = _filled(cap)
+    sec, mx, mn = _filled(d.nsec * 16), _filled(d.nsec * 8), _filled(d.nsec * 8)
+    need = ctypes.c_uint64(0)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    dyn, keep = qpack._plan_dyn_dev(None, d.plain.device, d.dyn["views"], d.dyn["section_view"],
+                                    d.dyn["ref_limit"], d.dyn["entries"], d.dyn["keys"],
+                                    d.dyn["dyn_bytes"], d.dyn["nentries"], d.dyn["nbytes"])
+    rv = qpack._load().qh_encode_fields_dyn_batch(enc.codec._ctx, p(d.plain), p(d_fields), d.n, p(d.fs),
+                                                 d.nsec, ctypes.byref(dyn), p(dst), cap, p(sec),
+                                                 ctypes.byref(need), p(mx), p(mn), _lib.QH_WHERE_DEVICE)
+    enc.codec.sync()
+    del keep
+    return (rv, need.value, _host(dst, cap), _host(sec, d.nsec * 16).view(SPAN_IN_DTYPE),
+            _host(mx, d.nsec * 8).tobytes(), _host(mn, d.nsec * 8).tobytes())
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_encode_fields_against_a_table(enc, name):
+    d = Dev(name)
+    h, tab = d.h, d.tab
+    want_dst, want_sec = h["dst"], h["sections"]
+    need = want_dst.size
+    for garbage in (False, True):
+        d_fields = _cuda(fields_of(h["strs"], h["never"], garbage))
+        rv, got_need, dst, sec, mx, mn = encode_dev(enc, d, d_fields, need + 32)
+        assert rv == 0 and got_need == need
+        assert sec.tobytes() == want_sec.tobytes()
+        assert dst[:need].tobytes() == want_dst.tobytes() and (dst[need:] == PATTERN).all()
+        assert mx == h["plan"]["max_cnt"].tobytes() and mn == h["plan"]["min_cnt"].tobytes()
+    # one byte short: the exact need, nothing written
+    rv, got_need, dst, _, _, _ = encode_dev(enc, d, d_fields, need - 1)
+    assert rv == _lib.QH_ERR_NOMEM and got_need == need and (dst == PATTERN).all()
+    # and through host memory
+    h_dst, h_sec, h_mx, h_mn = enc.encode_fields(h["plain"], fields_of(h["strs"], h["never"]), h["fs"],
+                                                 views=tab["views"], section_view=h["sv"],
+                                                 ref_limit=h["rl"], entries=tab["entries"],
+                                                 keys=tab["keys"], dyn_bytes=tab["bytes"])
+    assert h_dst.tobytes() == want_dst.tobytes() and h_sec.tobytes() == want_sec.tobytes()
+    assert h_mx.tobytes() == h["plan"]["max_cnt"].tobytes()
+    assert h_mn.tobytes() == h["plan"]["min_cnt"].tobytes()
+
+
+@pytest.mark.parametrize("name", [n for n in CASES if dc.by_name(n).bad is None])
+def test_closure_on_the_device(enc, name):
+    """encode_fields_dev against the table -> decode_blocks_dev ->
+    emit_fields_dev against the same views, every hand-over a tensor in HBM."""
+    import torch
+    c, d = dc.by_name(name), Dev(name)
+    h, tab = d.h, d.tab
+    need = h["dst"].size
+    d_dst = torch.zeros(need + 64, dtype=torch.uint8, device="cuda")
+    d_sec = torch.zeros((max(d.nsec, 1), 2), dtype=torch.int64, device="cuda")
+    got_need, mx, mn = enc.encode_fields_dev(d.plain, _cuda(fields_of(h["strs"], h["never"])), d.n, d.fs,
+                                             d_dst, d_sec, **d.dyn)
+    assert got_need == need
+    # (an out-of-range view index plans as no table: it decodes against an
+    # empty table state appended to the views)
+    nv = tab["views"].size
+    views = _cuda(np.concatenate([tab["views"], np.zeros(1, qpack.VIEW_DTYPE)]))
+    bv = np.zeros(d.nsec, np.uint32) if h["sv"] is None else np.where(h["sv"] >= nv, nv, h["sv"])
+    fsd = qpack.FieldSectionDecoder(codec=enc.codec)
+    src = d_dst[:max(need, 1)]
+    res = fsd.decode_blocks_dev(src, d_sec[:d.nsec], packed=True, prefixes=True)
+    em = fsd.emit_fields_dev(res, src, d_sec[:d.nsec], views=views,
+                             block_view=_cuda(bv.astype(np.uint32)).view(torch.int32),
+                             entries=d.dyn["entries"], dyn_bytes=d.dyn["dyn_bytes"])
+    enc.codec.sync()
+    assert (em["status"].cpu().numpy()[:d.nsec] == 0).all()
+    assert em["ricnt"].cpu().numpy()[:d.nsec].astype(np.uint64).tolist() == h["plan"]["max_cnt"].tolist()
+    assert mx.cpu().numpy()[:d.nsec].astype(np.uint64).tolist() == h["plan"]["max_cnt"].tolist()
+    assert em["nfields"] == d.n
+    assert em["field_start"].cpu().numpy()[:d.nsec + 1].tolist() == list(c.field_start)
+    f = em["fields"].cpu().numpy()[:d.n * 32].view(qpack.FIELD_DTYPE)
+    out = em["out"].cpu().numpy()[:em["out_need"]].tobytes()
+    got = [(out[int(r["name_off"]):int(r["name_off"]) + int(r["name_len"])],
+            out[int(r["value_off"]):int(r["value_off"]) + int(r["value_len"])],
+            1 if r["flags"] & qpack.FL_NEVER else 0) for r in f]
+    assert got == [(n, v, 1 if nvr else 0) for n, v, nvr in c.fields]
+
+
+def test_without_a_table_the_static_planner_s_results(codec, enc):
+    import torch
+    fields = list(pc.cases())
+    never = pc.never_flags(fields, True)
+    plain, strs = pc.pack(fields)
+    n = len(fields)
+    fs = pc.field_start([n // 3, 0, n - n // 3])
+    d_plain, d_strs = _cuda(plain), _cuda(strs).view(torch.int64).reshape(-1, 2)
+    d_never, d_fs = _cuda(never), _cuda(fs).view(torch.int32)
+    want = _filled(n * 24)
+    qpack.plan_fields_dev(codec, d_plain, d_strs, d_never, want)
+    for views in (None, _cuda(np.zeros(1, qpack.VIEW_DTYPE))):
+        lines, pfx, mx, mn = _filled(n * 24), _filled(3 * 24), _filled(3 * 8), _filled(3 * 8)
+        qpack.plan_fields_dyn_dev(codec, d_plain, d_strs, d_never, d_fs, lines, pfx,
+                                  mx[:24].view(torch.int64), mn[:24].view(torch.int64), views=views)
+        codec.sync()
+        assert _host(lines, n * 24).tobytes() == _host(want, n * 24).tobytes() == \
+            qpack.plan_fields(plain, strs, never).tobytes()
+        assert _host(pfx, 72).tobytes() == bytes(72)
+        assert _host(mx, 24).tobytes() == bytes(24) and _host(mn, 24).tobytes() == b"\xff" * 24
+    # sections: qh_encode_fields_batch's
+    f = _cuda(fields_of(strs, never))
+    want_dst, want_sec = enc.encode_fields(plain, fields_of(strs, never), fs)
+    cap = want_dst.size + 32
+    dst, sec = _filled(cap), _filled(3 * 16)
+    need = ctypes.c_uint64(0)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    rv = qpack._load().qh_encode_fields_dyn_batch(codec._ctx, p(d_plain), p(f), n, p(d_fs), 3, None,
+                                                 p(dst), cap, p(sec), ctypes.byref(need), None, None,
+                                                 _lib.QH_WHERE_DEVICE)
+    codec.sync()
+    assert rv == 0 and need.value == want_dst.size
+    assert _host(dst, cap)[:need.value].tobytes() == want_dst.tobytes()
+    assert _host(sec, 48).tobytes() == want_sec.tobytes()
+
+
+def test_scratch_reuse_big_small_big(enc):
+    for name in ("fields-4097", "selection", "sections-4097", "prefix-wrap", "mixed-corpus"):
+        d = Dev(name)
+        h = d.h
+        rv, need, dst, sec, mx, _ = encode_dev(enc, d, _cuda(fields_of(h["strs"], h["never"])),
+                                               h["dst"].size)
+        assert rv == 0 and need == h["dst"].size
+        assert dst.tobytes() == h["dst"].tobytes() and sec.tobytes() == h["sections"].tobytes()
+        assert mx == h["plan"]["max_cnt"].tobytes()
