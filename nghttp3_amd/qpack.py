@@ -451,6 +451,8 @@ class FieldSectionDecoder:
         tokens, line_start, span_start, status, dst) plus the totals
         (nlines, nspans, nhuff, dst_need); `bufs` (a previous result)
         reuses its allocations.  Asynchronous after the framing sync.
+        The record arrays hold one line and one string per byte of src, and
+        grow to the call's totals when blocks overlap and hold more.
         ``packed`` (QH_SECTIONS_PACKED): the decoded Huffman strings back to
         back in dst (dst_need: their bytes) instead of the slot layout; the
         call then also waits for the decode.  ``prefixes``: also every
@@ -480,7 +482,8 @@ class FieldSectionDecoder:
             b["dst"] = torch.empty(cap * 8 // 5, dtype=torch.uint8, device=dev)
         lib = _load()
         p = lambda t: t.data_ptr()
-        for _ in range(2):  # a second try only when dst was too small
+        cap = b["cap"]
+        for _ in range(3):  # again only when the records or dst were too small
             st = qh_sections(p(b["lines"]), cap, p(b["spans"]), cap, p(b["strs"]), p(b["verdict"]),
                              p(b["tokens"]), p(b["line_start"]), p(b["span_start"]), p(b["status"]),
                              p(b["prefixes"]) if prefixes else None, p(b["dst"]),
@@ -488,6 +491,15 @@ class FieldSectionDecoder:
             rv = lib.qh_decode_sections_batch(self.codec._ctx, ctypes.c_void_p(src.data_ptr()),
                                               ctypes.c_void_p(blocks.data_ptr()), n, opts,
                                               ctypes.byref(st), _lib.QH_WHERE_DEVICE)
+            if rv == _lib.QH_ERR_NOMEM and max(st.nlines, st.nspans) > cap:
+                # (blocks that overlap hold more lines and strings than src has bytes)
+                cap = b["cap"] = int(max(st.nlines, st.nspans))
+                b["lines"] = torch.empty(cap * FIELD_LINE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                b["spans"] = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+                b["strs"] = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+                b["verdict"] = torch.empty(cap, dtype=torch.int8, device=dev)
+                b["tokens"] = torch.empty(cap, dtype=torch.int32, device=dev)
+                continue
             if rv == _lib.QH_ERR_NOMEM and st.dst_need > b["dst"].numel():
                 b["dst"] = torch.empty(int(st.dst_need), dtype=torch.uint8, device=dev)
                 continue

@@ -3,8 +3,9 @@
 // host.  Every block is placed in a stage buffer at an alignment from 0 to
 // 15 with random bytes around it (the kernel's LDS stage holds the wave's
 // other blocks there).  Prints: blocks, answered, mismatches, clean blocks
-// not answered.  Usage: frame_fast_check SRC BLOCKS (SRC: bytes; BLOCKS:
-// (u64 offset, u64 length) pairs).
+// not answered.  Usage: frame_fast_check SRC BLOCKS [OPTS] (SRC: bytes;
+// BLOCKS: (u64 offset, u64 length) pairs; OPTS: the QH_SECTIONS_* options
+// word both parsers get, QH_SECTIONS_DTABLE0 when absent).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,7 @@ int main(int argc, char **argv) {
   uint64_t *bl = (uint64_t *)slurp(argv[2], &bz);
   if (!src || !bl) return 2;
   const long n = bz / 16;
+  const uint32_t opts = argc > 3 ? (uint32_t)strtoul(argv[3], nullptr, 0) : QH_SECTIONS_DTABLE0;
   long fast = 0, mism = 0, clean_fallback = 0;
   uint8_t *stage = (uint8_t *)aligned_alloc(16, 1 << 20);
   srand(7);
@@ -48,11 +50,11 @@ int main(int argc, char **argv) {
     FrCounts c;
     qh_section_prefix pf{}, pf2{};
     uint16_t ls[kFrLines], ls2[kFrLines];
-    const bool ok = frame_count_fast(stage, at, len, QH_SECTIONS_DTABLE0, c, pf, ls);
+    const bool ok = frame_count_fast(stage, at, len, opts, c, pf, ls);
     scan_out o = {};
     o.lines_cap = (size_t)-1;
     o.spans_cap = (size_t)-1;
-    o.opts = QH_SECTIONS_DTABLE0;
+    o.opts = opts;
     o.lstarts = ls2;
     o.lstarts_cap = kFrLines;
     const int rv = scan_section(&o, src + off, len, off, &pf2);
@@ -68,5 +70,8 @@ int main(int argc, char **argv) {
     }
   }
   printf("%ld %ld %ld %ld\n", n, fast, mism, clean_fallback);
+  free(stage);
+  free(src);
+  free(bl);
   return 0;
 }
