@@ -689,6 +689,91 @@ QH_EXPORT int qh_dtable_get_view(const qh_dtable *dt, qh_dtable_view *view);
 QH_EXPORT const qh_dyn_entry *qh_dtable_entries(const qh_dtable *dt, size_t *n);
 QH_EXPORT const uint8_t *qh_dtable_bytes(const qh_dtable *dt, size_t *n);
 
+/* ---- Many dynamic tables in one log: encoder streams in batches ---------
+ * nghttp3_qpack_decoder_read_encoder (qpack.c:2815-3306) for a batch of
+ * connections.  A table is two records in caller-owned arrays, views[t] (as
+ * emission and the planners take it) and acct[t], over one shared log:
+ * entries[0, *nentries) and bytes[0, *nbytes), caller-owned, append-only.
+ * There is no library object.
+ *
+ * One call applies stream p = src[streams[p].off, +len) to table tsel[p]
+ * (tsel NULL: table p, nsel = ntables).  Per stream the instructions are
+ * applied in order; a trailing partial instruction is not consumed
+ * (consumed[p] = the bytes of complete, applied instructions: hand the rest
+ * in again with what follows).  The first failing instruction sets
+ * status[p], the ones before it stay applied and consumed[p] ends before it:
+ * QH_ERR_QPACK_ENCODER_STREAM_ERROR for a capacity above hard_max, an entry
+ * larger than the capacity, a relative index that is not live, a static
+ * index >= 99, a varint overflow, or a Huffman string that does not decode
+ * (EOS, padding: qpack.c:2737-2763); QH_ERR_QPACK_HEADER_TOO_LARGE exactly
+ * as qh_qpack_scan_encoder_stream reports it.
+ *
+ * Layout rule (the host function and the kernels follow it, so their logs
+ * are byte for byte equal).  Allocation follows the order of the call's
+ * table list.  A table moves iff at least one insert or duplicate of its
+ * stream is applied.  A moving table's records live on entry, [live_lo,
+ * insert_count) on entry, L of them, are copied verbatim (offsets
+ * unchanged) to the entry cursor, one record per applied insert follows in
+ * stream order, and ent_base becomes region_start - live_lo (on entry): entry
+ * a is still entries[ent_base + a] for every a live on entry and every new
+ * one.  Its bytes go to the byte cursor back to back, per applied insert the
+ * name bytes (a literal or static name; a dynamic name reference or a
+ * duplicate shares the old offsets) and then the value bytes (unless a
+ * duplicate).  A table that does not move (an empty stream, set-capacity
+ * only, a failure before the first insert) keeps ent_base; live_lo, cap and
+ * size still change as the instructions say.  Records and bytes written
+ * earlier are never modified, so a view copied before the call stays valid
+ * after it.
+ * Growth: a call appends, per moving table, 32 (L + inserts) bytes of records
+ * and the new strings' bytes; the records of the regions left behind stay.
+ * A table of capacity C holds at most C / 32 live records, so relocation
+ * costs at most C bytes per touched table per call.  Compacting the log
+ * (copying the live regions to a fresh log, views rebased) is the caller's
+ * and not done here.
+ *
+ * Returns 0; QH_ERR_INVALID_ARGUMENT (a table index >= ntables, a table
+ * listed twice in tsel: nothing is written); QH_ERR_NOMEM when entries_cap
+ * or bytes_cap is too small: *nentries and *nbytes are then the exact sizes
+ * the log would have, views, acct and the log are untouched (status and
+ * consumed may have been written), and the caller grows the arrays and calls
+ * again with its old counts.  A view whose live range leaves the log, or a
+ * referenced record whose strings leave [0, *nbytes), fails that table with
+ * QH_ERR_QPACK_ENCODER_STREAM_ERROR and nothing is read outside the log. */
+typedef struct qh_dtable_acct { /* 32 B: what an apply needs and a view does not */
+  uint64_t hard_max; /* the hard maximum capacity                           */
+  uint64_t cap;      /* the current capacity                                */
+  uint64_t size;     /* sum of name_len + value_len + 32 over live entries  */
+  uint64_t reserved;
+} qh_dtable_acct;
+
+/* A fresh table (nghttp3_qpack_decoder_init + set_max_dtable_capacity). */
+QH_EXPORT void qh_dtable_state_init(uint64_t hard_max, qh_dtable_view *view,
+                                    qh_dtable_acct *acct);
+
+QH_EXPORT int qh_qpack_dtables_apply(
+    const uint8_t *src, const qh_span_in *streams, const uint32_t *tsel, size_t nsel,
+    size_t ntables, qh_dtable_view *views, qh_dtable_acct *acct, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes,
+    uint64_t bytes_cap, int32_t *status, uint32_t *consumed);
+
+/* The same over arrays in HBM (where must be QH_WHERE_DEVICE; nentries and
+ * nbytes are host scalars).  Asynchronous on the context stream after one
+ * host wait, which reads the parser's totals and the size pass's totals
+ * (against the caps): the work is queued over scratch laid out from what the
+ * context's previous call parsed, scaled to this call's stream count plus an
+ * eighth, and a call that parses more than that (and the first one) waits
+ * twice.  A call much smaller per stream than the one before it pays for the
+ * unused layout once (a memset and empty strings for the decoder).  No
+ * fence is needed inside the apply kernel: one lane per table walks, and the
+ * only records of this call it reads back are the ones it stored itself; the
+ * bytes a call appends are not read by that call.  Sources are read in place:
+ * no padding is required around src.  Scratch comes from the context. */
+QH_EXPORT int qh_dtables_apply_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *streams, const uint32_t *tsel, size_t nsel,
+    size_t ntables, qh_dtable_view *views, qh_dtable_acct *acct, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes,
+    uint64_t bytes_cap, int32_t *status, uint32_t *consumed, int where);
+
 /* Where a field's name / value bytes are. */
 #define QH_IN_SRC 0    /* raw string in the block bytes (off into src)     */
 #define QH_IN_DST 1    /* decoded Huffman string (off into sections dst)   */

@@ -166,6 +166,10 @@ EXPORTED_FUNCTIONS = (
     "qh_dtable_bytes",
     "qh_qpack_emit_fields",
     "qh_emit_fields_batch",
+    # encoder streams of many connections, tables in one log (csrc/qh_dtset.c, csrc/qh_dtset.inc)
+    "qh_dtable_state_init",
+    "qh_qpack_dtables_apply",
+    "qh_dtables_apply_batch",
     # field representations on the GPU (csrc/qh_plan.inc)
     "qh_plan_fields_batch",
     "qh_encode_fields_batch",

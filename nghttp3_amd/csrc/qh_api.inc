@@ -35,6 +35,8 @@ enum BufId {
   kBufEmit,         // qh_emit_fields_batch: per-block counts, per-line records, long strings
   kBufEmitStatic,   // ... the static table: 99 records, their bytes, the planner's chains and token tables
   kBufPlan,         // qh_encode_fields_batch: the planned fields' spans and lines
+  kBufDtset,        // qh_dtables_apply_batch: per-stream counts, sizes and verdicts
+  kBufDtsetWork,    // ... instructions, spans, the Huffman strings' spans, results and slots
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage0,     // host-mode staging: src, spans in, dst, spans out
   kBufPinned0 = kBufStage0 + 4,  // from here on: pinned host memory
@@ -43,6 +45,7 @@ enum BufId {
   kBufEnds,        // host pipelines: a slice's dense end (64 words)
   kBufEncSecHost,  // the sections encoder's totals read back (8 words)
   kBufEmitHost,    // field emission's totals read back (8 words)
+  kBufDtsetHost,   // the table set's totals read back (8 words)
   kNumBuf
 };
 
@@ -116,6 +119,11 @@ struct qh_ctx {
   uint64_t es_nl_hint = 0;  // the most lines a call has seen (kBufEncSecLoff's capacity)
   hipEvent_t es_ev = nullptr;  // recorded after the copy into kBufEncSecHost
   uint32_t emit_long_min = 0;  // QH_OPT_EMIT_LONG_MIN (0: kEmitLongMin, qh_emit.inc)
+  // the instructions, spans, Huffman spans and decode-slot bytes the last
+  // qh_dtables_apply_batch call parsed, and its stream count (the next call's
+  // work buffer is laid out from them before its own totals are known)
+  uint64_t dt_hint[4] = {0, 0, 0, 0};
+  uint64_t dt_hint_nsel = 0;
   // fused encoder (qh_enc_fused.inc): the halves of kBufEw are used by
   // alternate calls
   int ew_par = 0;

@@ -1,0 +1,517 @@
+// Encoder streams of many connections applied to dynamic tables that share
+// one device-resident log (include/qhuff.h qh_dtables_apply_batch): the
+// device twin of qh_dtset.c.  The parser is qh_qpack_core.h and the walk
+// qh_dtable_core.h, the sources the host function compiles, and the layout
+// rule of the header fixes every record's and byte's place, so the two logs
+// are equal byte for byte.
+//
+//   count   qh_k_dts_count, a lane per stream: the table list checked (an
+//           index past ntables, a table named twice), the stream parsed in
+//           counting mode: its instructions, spans, Huffman spans and decode
+//           slot bytes, its verdict and the bytes of complete instructions;
+//   scan    qh_k_scan_seg over the four counts;
+//   write   qh_k_dts_write, a lane per stream: parsed again into place
+//           (instructions with batch-global span indices and their end
+//           offsets, spans, per span its Huffman index, the Huffman spans
+//           compacted);
+//   decode  the context's decoder over the compacted Huffman spans
+//           (decode_device, the entry the sections pipeline uses; strings of
+//           4 KiB and more take its long path);
+//   size    qh_k_dts_size, a lane per table: the walk in size-only mode over
+//           lengths and decode statuses: the first failing instruction, the
+//           applied count, the records and bytes the table appends;
+//   scan    qh_k_scan_seg over the records and the bytes: each table's
+//           region starts and the totals;
+//   (sync)  one: the parser's totals against the work buffer's layout (laid
+//           out for the most an earlier call parsed; see the host function),
+//           the size pass's against entries_cap / bytes_cap;
+//   apply   qh_k_dts_apply, 16 lanes per table: the live records relocated a
+//           record per lane per round, then the walk again by lane 0 (state
+//           in its registers; it evicts, looks up a literal name's token and
+//           writes the record) with the whole group copying each insert's
+//           name and value bytes; lane 0 writes the new view and acct.
+// No atomics in the apply: regions are disjoint and fixed by the scans.
+
+#include "qh_dtable_core.h"
+
+namespace qhk {
+
+constexpr uint32_t kDtLanes = 16;
+
+// The header words ahead of the scan's tile states (zeroed before each scan;
+// words 1-7 read back with one copy).
+enum : uint32_t {
+  kDtCtr = 0,       // scan tile counter
+  kDtTot = 1,       // the scan's totals: up to four words
+  kDtTimeouts = 5,  // scan look-backs that gave up
+  kDtErr = 6,       // a bad table list, a stream or a table past the 32-bit counts
+  kDtNLong = 7,     // Huffman strings of at least QH_LONG_MIN encoded bytes
+  kDtHdr = 8
+};
+
+// The work buffer's room, in records.  The chain from the write pass to the
+// second scan may be queued before the host has seen the parser's totals
+// (over a buffer sized by earlier calls): a stream whose records would pass
+// a cap writes none and is walked by nobody, and the host, which then finds
+// the totals above the caps, queues the chain again.
+struct DtCaps {
+  uint64_t ni, ns, nh;
+};
+// (The decode-slot bytes are not checked here: a string whose slot would pass
+// the layout's slot bytes is refused by the decoder itself -- status
+// QH_ERR_NOMEM, nothing written at or past dst_cap (qh_peek_dec.inc) -- and
+// the host's test of the slot total queues the chain again.)
+__device__ __forceinline__ bool dts_fits(const SpanOut *__restrict__ cnt, uint64_t nsel, uint64_t p,
+                                         const DtCaps &k) {
+  const SpanOut ci = cnt[p], cs = cnt[nsel + p], ch = cnt[2 * nsel + p];
+  return ci.off + ci.len <= k.ni && cs.off + cs.len <= k.ns && ch.off + ch.len <= k.nh;
+}
+
+struct DtRes {  // a table's verdict from the size pass
+  int32_t status;
+  uint32_t consumed, napplied, bad_view;
+};
+
+__global__ void __launch_bounds__(256) qh_k_dts_count(
+    const uint8_t *__restrict__ src, const SpanIn *__restrict__ streams,
+    const uint32_t *__restrict__ tsel, uint64_t nsel, uint64_t ntables,
+    uint32_t *__restrict__ owner, SpanOut *__restrict__ cnt, int32_t *__restrict__ sv,
+    uint32_t *__restrict__ done, uint64_t *__restrict__ hdr) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nsel) return;
+  const uint64_t t = tsel ? tsel[p] : p;
+  bool err = t >= ntables;
+  if (!err && tsel) err = atomicExch(&owner[t], (uint32_t)p) != 0xFFFFFFFFu;  // (named twice)
+  const SpanIn s = streams[p];
+  if (s.len > (1u << 30) || (s.len && !src)) err = true;
+  scan_out o;
+  frame_init(o, 0);
+  size_t dn = 0;
+  int v = 0;
+  if (!err) v = scan_encoder(&o, src + s.off, s.len, s.off, nullptr, &dn);
+  cnt[p].len = (uint32_t)o.nlines;
+  cnt[nsel + p].len = (uint32_t)o.nspans;
+  cnt[2 * nsel + p].len = (uint32_t)o.nhuff;
+  cnt[3 * nsel + p].len = (uint32_t)o.hslots;  // (at most 8/5 of 2^30 bytes + 80 per string)
+  sv[p] = v;
+  done[p] = (uint32_t)dn;
+  if (err) atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
+  if (o.nlong)
+    atomicAdd(reinterpret_cast<unsigned long long *>(hdr + kDtNLong), (unsigned long long)o.nlong);
+}
+
+// After the scan: cnt[k nsel + p].off = stream p's first instruction, span,
+// Huffman span (k = 0, 1, 2).
+__global__ void __launch_bounds__(256) qh_k_dts_write(
+    const uint8_t *__restrict__ src, const SpanIn *__restrict__ streams, uint64_t nsel,
+    const SpanOut *__restrict__ cnt, const uint32_t *__restrict__ done,
+    qh_field_line *__restrict__ insts, uint32_t *__restrict__ ends, SpanIn *__restrict__ spans,
+    uint64_t *__restrict__ aux, SpanIn *__restrict__ huff, DtCaps caps) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nsel) return;
+  const SpanOut ci = cnt[p], cs = cnt[nsel + p], ch = cnt[2 * nsel + p];
+  if (ci.len == 0 || !dts_fits(cnt, nsel, p, caps)) return;
+  const SpanIn s = streams[p];
+  scan_out o;
+  frame_init(o, 0);
+  o.lines = insts + ci.off;
+  o.lines_cap = ci.len;
+  o.spans = reinterpret_cast<qh_span_in *>(spans + cs.off);
+  o.spans_cap = cs.len;
+  o.aux = aux + cs.off;
+  o.huff = reinterpret_cast<qh_span_in *>(huff);
+  o.huff_base = ch.off;
+  o.span_base = cs.off;
+  o.block = p;
+  size_t dn = 0;
+  // (the bytes of complete instructions, parsed as in the count pass: the
+  // same records, which the caps above hold exactly)
+  (void)scan_encoder(&o, src + s.off, done[p], s.off, ends + ci.off, &dn);
+}
+
+// Instruction l with its strings' lengths and statuses (a Huffman string's
+// from the decoder's result).
+__device__ __forceinline__ void dts_inst(const qh_field_line &l, const SpanIn *__restrict__ spans,
+                                         const uint64_t *__restrict__ aux,
+                                         const SpanOut *__restrict__ hout, qh_dt_inst *in) {
+  const uint32_t hn = l.name >= 0 ? (uint32_t)aux[l.name] : 0xFFFFFFFFu;
+  const uint32_t hv = l.value >= 0 ? (uint32_t)aux[l.value] : 0xFFFFFFFFu;
+  qh_dt_inst_of(&l, reinterpret_cast<const qh_span_in *>(spans),
+                hn != 0xFFFFFFFFu ? reinterpret_cast<const qh_span_out *>(hout + hn) : nullptr,
+                hv != 0xFFFFFFFFu ? reinterpret_cast<const qh_span_out *>(hout + hv) : nullptr, in);
+}
+
+// cnt2[p].len = the records table p appends, cnt2[nsel + p].len its bytes.
+__global__ void __launch_bounds__(256) qh_k_dts_size(
+    const uint32_t *__restrict__ tsel, uint64_t nsel, uint64_t ntables,
+    const qh_dtable_view *__restrict__ views, const qh_dtable_acct *__restrict__ acct,
+    const qh_dyn_entry *__restrict__ entries, uint64_t nentries, uint64_t nbytes,
+    const qh_static_rec *__restrict__ stat, DtCaps caps,
+    const SpanOut *__restrict__ cnt, const int32_t *__restrict__ sv,
+    const uint32_t *__restrict__ done, const qh_field_line *__restrict__ insts,
+    const uint32_t *__restrict__ ends, const SpanIn *__restrict__ spans,
+    const uint64_t *__restrict__ aux, const SpanOut *__restrict__ hout, uint32_t *__restrict__ lens,
+    SpanOut *__restrict__ cnt2, DtRes *__restrict__ res, uint64_t *__restrict__ hdr) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nsel) return;
+  const uint64_t t = tsel ? tsel[p] : p;
+  DtRes r{QH_ERR_QPACK_ENCODER_STREAM_ERROR, 0u, 0u, 1u};
+  // (a bad table list or records past the caps: the host discards this pass)
+  if (t >= ntables || !dts_fits(cnt, nsel, p, caps)) {
+    res[p] = r;
+    cnt2[p].len = 0;
+    cnt2[nsel + p].len = 0;
+    return;
+  }
+  const qh_dtable_view v = views[t];
+  const qh_dtable_acct a = acct[t];
+  uint64_t nrec = 0, nbyte = 0;
+  if (qh_dt_view_check(&v, nentries) == 0) {
+    const SpanOut ci = cnt[p];
+    qh_dt_walk w;
+    qh_dt_begin(&w, &v, &a, entries, nbytes, stat);
+    w.lens = lens + 2 * ci.off;
+    uint32_t i = 0;
+    for (; i < ci.len; ++i) {  // (at most the stream's instructions, plus the evictions)
+      const qh_field_line l = insts[ci.off + i];
+      qh_dt_inst in;
+      qh_dt_add ad;
+      dts_inst(l, spans, aux, hout, &in);
+      if (qh_dt_step(&w, &in, &ad) != 0) break;
+    }
+    r.napplied = i;
+    r.bad_view = 0;
+    r.status = i < ci.len ? QH_ERR_QPACK_ENCODER_STREAM_ERROR : sv[p];
+    r.consumed = i < ci.len ? (i ? ends[ci.off + i - 1] : 0u) : done[p];
+    if (w.nnew) {
+      nrec = (w.count_in - w.live_lo_in) + w.nnew;
+      nbyte = w.byte_at;
+    }
+  }
+  if (nrec > 0xFFFFFFFFull || nbyte > 0xFFFFFFFFull) {
+    atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
+    nrec = nbyte = 0;
+  }
+  res[p] = r;
+  cnt2[p].len = (uint32_t)nrec;
+  cnt2[nsel + p].len = (uint32_t)nbyte;
+}
+
+// n bytes from -> to by a 16-lane group (any alignment): 16-byte pieces at
+// min(16 k, n - 16), the last overlapping the one before it, a lane each per
+// round; a string under 16 bytes a byte per lane.  Never touches a byte
+// outside [from, from + n) or [to, to + n).
+__device__ __forceinline__ void dts_group_copy(uint8_t *to, const uint8_t *from, uint32_t n,
+                                               uint32_t sl) {
+  if (n < 16) {
+    if (sl < n) to[sl] = from[sl];
+    return;
+  }
+  const uint32_t np = (n + 15) / 16;
+  for (uint32_t k = sl; k < np; k += kDtLanes) {
+    const uint32_t at = min(16 * k, n - 16);
+    const u32x4 w = *reinterpret_cast<const u32x4_ua *>(from + at);
+    *reinterpret_cast<u32x4_ua *>(to + at) = w;
+  }
+}
+
+// After the second scan: cnt2[p].off = the records appended before table p's
+// region, cnt2[nsel + p].off the bytes.
+// (8 waves per SIMD: the walk is serial per table and latency-bound, the
+// parallelism is across tables)
+#ifndef QH_DTS_MIN_WAVES
+#define QH_DTS_MIN_WAVES 8
+#endif
+__global__ void __launch_bounds__(256, QH_DTS_MIN_WAVES) qh_k_dts_apply(
+    const uint8_t *__restrict__ src, const uint32_t *__restrict__ tsel, uint64_t nsel,
+    qh_dtable_view *__restrict__ views, qh_dtable_acct *__restrict__ acct,
+    qh_dyn_entry *entries, uint64_t nentries, uint8_t *__restrict__ bytes, uint64_t nbytes,
+    const qh_static_rec *__restrict__ stat, const uint8_t *__restrict__ stat_bytes,
+    const SpanOut *__restrict__ cnt, const qh_field_line *__restrict__ insts,
+    const SpanIn *__restrict__ spans, const uint64_t *__restrict__ aux,
+    const SpanOut *__restrict__ hout, const uint8_t *__restrict__ slots,
+    uint32_t *__restrict__ lens, const SpanOut *__restrict__ cnt2, const DtRes *__restrict__ res,
+    int32_t *__restrict__ status, uint32_t *__restrict__ consumed) {
+  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kDtLanes;
+  const uint32_t sl = threadIdx.x % kDtLanes;
+  if (p >= nsel) return;  // (whole 16-lane groups)
+  const DtRes r = res[p];
+  if (sl == 0) {
+    status[p] = r.status;
+    consumed[p] = r.consumed;
+  }
+  if (r.bad_view) return;
+  const uint64_t t = tsel ? tsel[p] : p;
+  const qh_dtable_view v = views[t];
+  const qh_dtable_acct a = acct[t];
+  const SpanOut ci = cnt[p], cr = cnt2[p], cb = cnt2[nsel + p];
+  const uint64_t ent_at = nentries + cr.off;
+  qh_dt_walk w;
+  qh_dt_begin(&w, &v, &a, entries, nbytes, stat);
+  const uint64_t L = w.count_in - w.live_lo_in;
+  if (cr.len) {  // the table moves: its live records first, a record per lane per round
+    for (uint64_t j = sl; j < L; j += kDtLanes) entries[ent_at + j] = w.old[w.live_lo_in + j];
+    w.neu = entries + ent_at + L;
+    w.byte_at = nbytes + cb.off;
+  } else {
+    w.lens = lens + 2 * ci.off;  // (no insert is applied: nothing is stored)
+  }
+  for (uint32_t i = 0; i < r.napplied; ++i) {
+    const qh_field_line l = insts[ci.off + i];
+    qh_dt_add ad;
+    ad.added = 0;
+    ad.name_src = ad.value_src = QH_DT_SHARED;
+    ad.e.name_off = ad.e.value_off = 0;
+    ad.e.name_len = ad.e.value_len = 0;
+    if (sl == 0) {  // (the state lives in lane 0; it applied in the size pass: it succeeds)
+      qh_dt_inst in;
+      dts_inst(l, spans, aux, hout, &in);
+      (void)qh_dt_step(&w, &in, &ad);
+    }
+    if (!__shfl((int)ad.added, 0, kDtLanes)) continue;
+    const uint32_t name_src = __shfl((int)ad.name_src, 0, kDtLanes);
+    const uint32_t value_src = __shfl((int)ad.value_src, 0, kDtLanes);
+    const uint32_t name_len = __shfl(ad.e.name_len, 0, kDtLanes);
+    const uint32_t value_len = __shfl(ad.e.value_len, 0, kDtLanes);
+    const unsigned long long name_off = __shfl((unsigned long long)ad.e.name_off, 0, kDtLanes);
+    const unsigned long long value_off = __shfl((unsigned long long)ad.e.value_off, 0, kDtLanes);
+    if (name_src != QH_DT_SHARED) {
+      const uint8_t *from;
+      if (name_src == QH_DT_STATIC) {
+        from = stat_bytes + stat[l.index].name_off;
+      } else {
+        const uint32_t h = (uint32_t)aux[l.name];
+        from = h != 0xFFFFFFFFu ? slots + hout[h].off : src + spans[l.name].off;
+        if (sl == 0) ad.e.token = lookup_token(from, name_len);
+      }
+      dts_group_copy(bytes + name_off, from, name_len, sl);
+    }
+    if (value_src != QH_DT_SHARED) {
+      const uint32_t h = (uint32_t)aux[l.value];
+      const uint8_t *from = h != 0xFFFFFFFFu ? slots + hout[h].off : src + spans[l.value].off;
+      dts_group_copy(bytes + value_off, from, value_len, sl);
+    }
+    if (sl == 0) w.neu[w.nnew - 1] = ad.e;
+  }
+  if (sl == 0) {
+    qh_dtable_view nv = v;
+    qh_dtable_acct na = a;
+    if (cr.len) nv.ent_base = (int64_t)(ent_at - w.live_lo_in);
+    nv.live_lo = w.live_lo;
+    nv.insert_count = w.count;
+    na.cap = w.cap;
+    na.size = w.size;
+    views[t] = nv;
+    acct[t] = na;
+  }
+}
+
+}  // namespace qhk
+
+
+namespace {
+
+// The work buffer for up to ni instructions, ns spans, nh Huffman spans and
+// slots_b bytes of their decode slots (+64 per Huffman span: an unused entry
+// of the list is an empty string, which takes the smallest slot).
+struct DtWork {
+  qh_field_line *insts = nullptr;
+  uint32_t *ends = nullptr, *lens = nullptr;
+  qhk::SpanIn *spans = nullptr, *huff = nullptr;
+  uint64_t *aux = nullptr;
+  qhk::SpanOut *hout = nullptr;
+  uint8_t *slots = nullptr;
+  uint64_t slots_cap = 0;
+  qhk::DtCaps caps{0, 0, 0};
+};
+int dts_work(qh_ctx *c, uint64_t ni, uint64_t ns, uint64_t nh, uint64_t slots_b, DtWork &W) {
+  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+  W.slots_cap = slots_b + 64 * nh;
+  const uint64_t o_ends = al(ni * sizeof(qh_field_line)), o_lens = o_ends + al(ni * 4),
+                 o_spans = o_lens + al(ni * 8), o_aux = o_spans + al(ns * sizeof(qh_span_in)),
+                 o_huff = o_aux + al(ns * 8), o_hout = o_huff + al(nh * sizeof(qh_span_in)),
+                 o_slots = o_hout + al(nh * sizeof(qh_span_out)),
+                 total = o_slots + al(W.slots_cap + 16);
+  const int rv = reserve(c, kBufDtsetWork, total);
+  if (rv) return rv;
+  uint8_t *b = mem<uint8_t>(c, kBufDtsetWork);
+  W.insts = reinterpret_cast<qh_field_line *>(b);
+  W.ends = reinterpret_cast<uint32_t *>(b + o_ends);
+  W.lens = reinterpret_cast<uint32_t *>(b + o_lens);
+  W.spans = reinterpret_cast<qhk::SpanIn *>(b + o_spans);
+  W.aux = reinterpret_cast<uint64_t *>(b + o_aux);
+  W.huff = reinterpret_cast<qhk::SpanIn *>(b + o_huff);
+  W.hout = reinterpret_cast<qhk::SpanOut *>(b + o_hout);
+  W.slots = b + o_slots;
+  W.caps = qhk::DtCaps{ni, ns, nh};
+  return 0;
+}
+
+}  // namespace
+
+// Host waits: one, in the steady state.  The work buffer is laid out for what
+// the previous call parsed (qh_ctx::dt_hint: its four totals, scaled by this
+// call's stream count over that call's, plus an eighth), and the chain write
+// -> decode -> size -> scan is queued right behind the parser's count, so the
+// one wait reads both the parser's totals (did they fit the layout?) and the
+// size pass's (do they fit the caps?).  A call that parses more per stream
+// than the one before it (and the first one) waits for the parser's totals,
+// lays the buffer out for exactly them and queues the chain a second time: two
+// waits.  The layout follows the last call, not the largest: what a chain
+// costs over its call's own work is the layout's unused entries (a memset of
+// the Huffman list, an empty string each for the decoder), and a small call
+// after a big one pays that once, scaled down by its stream count, not
+// forever.
+QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_span_in *streams,
+                                     const uint32_t *tsel, size_t nsel, size_t ntables,
+                                     qh_dtable_view *views, qh_dtable_acct *acct,
+                                     qh_dyn_entry *entries, uint64_t *nentries,
+                                     uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes,
+                                     uint64_t bytes_cap, int32_t *status, uint32_t *consumed,
+                                     int where) {
+  int rv = check_ctx(c);
+  if (rv) return rv;
+  if (!tsel) nsel = ntables;
+  if (where != QH_WHERE_DEVICE || !nentries || !nbytes || *nentries > entries_cap ||
+      *nbytes > bytes_cap || (ntables && (!views || !acct)) ||
+      (nsel && (!streams || !status || !consumed)) || (!entries && entries_cap) ||
+      (!bytes && bytes_cap))
+    return QH_ERR_INVALID_ARGUMENT;
+  if (nsel == 0) return 0;
+  if (nsel > 0x7ffffffull || ntables > 0xFFFFFFFEull) return QH_ERR_INVALID_ARGUMENT;  // (grid)
+  if ((rv = emit_static(c))) return rv;
+  const uint8_t *simg = mem<const uint8_t>(c, kBufEmitStatic);
+  const qh_static_rec *stat = reinterpret_cast<const qh_static_rec *>(simg);
+  const uint8_t *stat_bytes = simg + qhk::kEmStatRecs;
+  const uint64_t ne0 = *nentries, nb0 = *nbytes;
+  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+
+  // per-stream scratch, sized by the table list alone: the four counts, the
+  // two sizes, verdicts, owners, and the two scans' headers and tile states
+  const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
+  const uint64_t hwords = qhk::kDtHdr + 4 * tps;
+  const uint64_t o_cnt2 = al(4 * (uint64_t)nsel * sizeof(qhk::SpanOut)),
+                 o_res = o_cnt2 + al(2 * (uint64_t)nsel * sizeof(qhk::SpanOut)),
+                 o_sv = o_res + al((uint64_t)nsel * sizeof(qhk::DtRes)),
+                 o_done = o_sv + al((uint64_t)nsel * 4), o_owner = o_done + al((uint64_t)nsel * 4),
+                 o_hdr = o_owner + al((uint64_t)ntables * 4),
+                 total1 = o_hdr + al(2 * hwords * sizeof(uint64_t));
+  if ((rv = reserve(c, kBufDtset, total1))) return rv;
+  uint8_t *b1 = mem<uint8_t>(c, kBufDtset);
+  qhk::SpanOut *cnt = reinterpret_cast<qhk::SpanOut *>(b1);
+  qhk::SpanOut *cnt2 = reinterpret_cast<qhk::SpanOut *>(b1 + o_cnt2);
+  qhk::DtRes *res = reinterpret_cast<qhk::DtRes *>(b1 + o_res);
+  int32_t *sv = reinterpret_cast<int32_t *>(b1 + o_sv);
+  uint32_t *done = reinterpret_cast<uint32_t *>(b1 + o_done);
+  uint32_t *owner = reinterpret_cast<uint32_t *>(b1 + o_owner);
+  uint64_t *hdr_a = reinterpret_cast<uint64_t *>(b1 + o_hdr), *hdr_b = hdr_a + hwords;
+  if ((rv = reserve(c, kBufDtsetHost, 16 * sizeof(uint64_t), qhs::kExact))) return rv;
+  uint64_t *h = mem<uint64_t>(c, kBufDtsetHost);  // [0, 7): the parser's words 1-7, [8, 15): the size pass's
+  DtWork W;
+  const bool spec = c->dt_hint_nsel != 0;
+  if (spec) {
+    uint64_t lay[4];
+    for (int k = 0; k < 4; ++k) {
+      lay[k] = (c->dt_hint[k] * (uint64_t)nsel + c->dt_hint_nsel - 1) / c->dt_hint_nsel;
+      lay[k] += lay[k] / 8 + 16;
+    }
+    if ((rv = dts_work(c, lay[0], lay[1], lay[2], lay[3], W))) return rv;
+  }
+
+  QH_HIP(hipMemsetAsync(hdr_a, 0, 2 * hwords * sizeof(uint64_t), c->stream));
+  if (tsel) QH_HIP(hipMemsetAsync(owner, 0xFF, ntables * 4, c->stream));
+  const unsigned grid1 = (unsigned)((nsel + 255) / 256);
+  {
+    Timed t(c, "qh_k_dts_count");
+    hipLaunchKernelGGL(qhk::qh_k_dts_count, dim3(grid1), dim3(256), 0, c->stream, src,
+                       (const qhk::SpanIn *)streams, tsel, (uint64_t)nsel, (uint64_t)ntables, owner,
+                       cnt, sv, done, hdr_a);
+    QH_HIP(hipGetLastError());
+  }
+  auto scan = [&](qhk::SpanOut *x, uint32_t nseg, uint64_t *hdr) -> int {
+    Timed t(c, "qh_k_scan_seg");
+    hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)(nseg * tps)), dim3(qhk::kBlock), 0,
+                       c->stream, x, (uint64_t)nsel, nseg, hdr + qhk::kDtHdr,
+                       reinterpret_cast<uint32_t *>(hdr),
+                       reinterpret_cast<unsigned long long *>(hdr + qhk::kDtTot),
+                       reinterpret_cast<unsigned long long *>(hdr + qhk::kDtTimeouts));
+    QH_HIP(hipGetLastError());
+    return 0;
+  };
+  // words 1-7 of both headers, one wait
+  auto totals = [&]() -> int {
+    QH_HIP(hipMemcpyAsync(h, hdr_a + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    QH_HIP(hipMemcpyAsync(h + 8, hdr_b + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    QH_HIP(hipStreamSynchronize(c->stream));
+    if (h[qhk::kDtTimeouts - 1] || h[8 + qhk::kDtTimeouts - 1]) {
+      fprintf(stderr, "qhuff: table-set scan look-back timed out\n");
+      return QH_ERR_FATAL;
+    }
+    return 0;
+  };
+  // write -> decode -> size -> scan over W's layout
+  auto chain = [&]() -> int {
+    int r = 0;
+    if (W.caps.nh)  // (an entry no stream writes is an empty string)
+      QH_HIP(hipMemsetAsync(W.huff, 0, W.caps.nh * sizeof(qh_span_in), c->stream));
+    if (W.caps.ni) {
+      Timed t(c, "qh_k_dts_write");
+      hipLaunchKernelGGL(qhk::qh_k_dts_write, dim3(grid1), dim3(256), 0, c->stream, src,
+                         (const qhk::SpanIn *)streams, (uint64_t)nsel, (const qhk::SpanOut *)cnt,
+                         (const uint32_t *)done, W.insts, W.ends, W.spans, W.aux, W.huff, W.caps);
+      QH_HIP(hipGetLastError());
+    }
+    if ((r = decode_device(c, src, W.huff, W.caps.nh, W.slots, W.slots_cap, W.hout, true, nullptr, 0)))
+      return r;
+    QH_HIP(hipMemsetAsync(hdr_b, 0, hwords * sizeof(uint64_t), c->stream));
+    {
+      Timed t(c, "qh_k_dts_size");
+      hipLaunchKernelGGL(qhk::qh_k_dts_size, dim3(grid1), dim3(256), 0, c->stream, tsel,
+                         (uint64_t)nsel, (uint64_t)ntables, (const qh_dtable_view *)views,
+                         (const qh_dtable_acct *)acct, (const qh_dyn_entry *)entries, ne0, nb0, stat,
+                         W.caps, (const qhk::SpanOut *)cnt, (const int32_t *)sv,
+                         (const uint32_t *)done, (const qh_field_line *)W.insts,
+                         (const uint32_t *)W.ends, (const qhk::SpanIn *)W.spans,
+                         (const uint64_t *)W.aux, (const qhk::SpanOut *)W.hout, W.lens, cnt2, res,
+                         hdr_b);
+      QH_HIP(hipGetLastError());
+    }
+    return scan(cnt2, 2, hdr_b);
+  };
+
+  if ((rv = scan(cnt, 4, hdr_a))) return rv;
+  if (spec && (rv = chain())) return rv;
+  if ((rv = totals())) return rv;  // the wait
+  if (h[qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  const uint64_t ni = h[0], ns = h[1], nh = h[2], slots_b = h[3];
+  if (ni > 0x7fffffffull || ns > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
+  if (!spec || ni > W.caps.ni || ns > W.caps.ns || nh > W.caps.nh ||
+      slots_b + 64 * (W.caps.nh - nh) > W.slots_cap) {
+    // more than the layout holds (or no layout yet): lay the buffer out for
+    // exactly this call and queue the chain (again); the second wait
+    if ((rv = dts_work(c, ni, ns, nh, slots_b, W))) return rv;
+    if ((rv = chain())) return rv;
+    if ((rv = totals())) return rv;
+  }
+  c->dt_hint[0] = ni;
+  c->dt_hint[1] = ns;
+  c->dt_hint[2] = nh;
+  c->dt_hint[3] = slots_b;
+  c->dt_hint_nsel = nsel;
+  if (h[8 + qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  *nentries = ne0 + h[8];
+  *nbytes = nb0 + h[9];
+  if (*nentries > entries_cap || *nbytes > bytes_cap) return QH_ERR_NOMEM;
+  {
+    Timed t(c, "qh_k_dts_apply");
+    const unsigned grid = (unsigned)(((uint64_t)nsel * qhk::kDtLanes + 255) / 256);
+    hipLaunchKernelGGL(qhk::qh_k_dts_apply, dim3(grid), dim3(256), 0, c->stream, src, tsel,
+                       (uint64_t)nsel, views, acct, entries, ne0, bytes, nb0, stat, stat_bytes,
+                       (const qhk::SpanOut *)cnt, (const qh_field_line *)W.insts,
+                       (const qhk::SpanIn *)W.spans, (const uint64_t *)W.aux,
+                       (const qhk::SpanOut *)W.hout, (const uint8_t *)W.slots, W.lens,
+                       (const qhk::SpanOut *)cnt2, (const qhk::DtRes *)res, status, consumed);
+    QH_HIP(hipGetLastError());
+  }
+  return 0;
+}

@@ -91,82 +91,20 @@ QH_EXPORT nghttp3_ssize qh_qpack_scan_encoder_stream(
   size_t insts_cap, size_t *ninsts, qh_span_in *spans, size_t spans_cap,
   size_t *nspans) {
   scan_out o = {.lines = insts, .lines_cap = insts_cap, .spans = spans, .spans_cap = spans_cap};
-  const uint8_t *p = src, *end = src + srclen, *done = src;
-  const int bad = QH_ERR_QPACK_ENCODER_STREAM_ERROR;
-  const int big = QH_ERR_QPACK_HEADER_TOO_LARGE; /* qpack.c:2962-2972 */
-  int rv = 0;
+  size_t done = 0;
+  int rv;
 
   if ((src == NULL && srclen) || ninsts == NULL || nspans == NULL ||
       (insts == NULL && insts_cap) || (spans == NULL && spans_cap)) {
     return QH_ERR_INVALID_ARGUMENT;
   }
-  /* qpack.c:2837-2875.  An instruction cut by the end of the input is left
-   * for the next call: the return value counts complete instructions. */
-  while (p != end) {
-    uint8_t b = *p;
-    size_t l0 = o.nlines, s0 = o.nspans;
-    qh_field_line *l;
-
-    if (b & 0x80u) {
-      l = new_line(&o, QH_ES_INSERT_INDEXED, (b & 0x40u) ? 0 : QH_FL_DYNAMIC);
-      if (l == NULL) {
-        rv = QH_ERR_NOMEM;
-        break;
-      }
-      rv = read_varint(&l->index, &p, end, 6);
-      /* rel2abs -> validate_index (qpack.c:3952-3969, :2796-2797): a
-       * static name reference must be < 99, whatever the table holds */
-      if (rv > 0 && !(l->flags & QH_FL_DYNAMIC) &&
-          l->index >= QH_QPACK_STATIC_ENTRIES) {
-        rv = bad;
-      }
-      if (rv > 0) {
-        rv = read_string(&o, &l->value, src, src_off, &p, end, 7,
-                         QH_QPACK_MAX_VALUELEN, 0, big, bad);
-      }
-    } else if (b & 0x40u) {
-      l = new_line(&o, QH_ES_INSERT, 0);
-      if (l == NULL) {
-        rv = QH_ERR_NOMEM;
-        break;
-      }
-      rv = read_string(&o, &l->name, src, src_off, &p, end, 5,
-                       QH_QPACK_MAX_NAMELEN, QH_SPAN_NAME, big, bad);
-      if (rv > 0) {
-        rv = read_string(&o, &l->value, src, src_off, &p, end, 7,
-                         QH_QPACK_MAX_VALUELEN, 0, big, bad);
-      }
-    } else {
-      l = new_line(&o, (b & 0x20u) ? QH_ES_SET_DTABLE_CAP : QH_ES_DUPLICATE,
-                   (b & 0x20u) ? 0 : QH_FL_DYNAMIC);
-      if (l == NULL) {
-        rv = QH_ERR_NOMEM;
-        break;
-      }
-      rv = read_varint(&l->index, &p, end, 5);
-    }
-    if (rv < 0) {
-      if (rv == QH_ERR_QPACK_FATAL) {
-        rv = bad;
-      }
-      o.nlines = l0;
-      o.nspans = s0;
-      break;
-    }
-    if (rv == 0) { /* truncated: roll back this instruction */
-      o.nlines = l0;
-      o.nspans = s0;
-      break;
-    }
-    done = p;
-    rv = 0;
-  }
+  rv = scan_encoder(&o, src, srclen, src_off, NULL, &done); /* qh_qpack_core.h */
   *ninsts = o.nlines;
   *nspans = o.nspans;
   if (rv < 0) {
     return rv;
   }
-  return (nghttp3_ssize)(done - src);
+  return (nghttp3_ssize)done;
 }
 
 /* ---- representation writers ---- */

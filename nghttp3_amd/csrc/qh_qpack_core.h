@@ -333,4 +333,83 @@ QH_HD static inline int scan_section(scan_out *o, const uint8_t *src, size_t src
   return 0;
 }
 
+/* The encoder stream's instruction loop, qpack.c:2837-2875 (the host entry
+ * point qh_qpack_scan_encoder_stream and the table-set kernels of
+ * qh_dtset.inc).  An instruction cut by the end of the input is left for the
+ * next call: *done counts the bytes of complete instructions.  ends (optional,
+ * one word per stored instruction): the offset in src just past it.  Returns
+ * 0, QH_ERR_NOMEM (a cap reached), or the failing instruction's error with
+ * the instructions before it kept. */
+QH_HD static inline int scan_encoder(scan_out *o, const uint8_t *src, size_t srclen,
+                                     uint64_t src_off, uint32_t *ends, size_t *done_out) {
+  const uint8_t *p = src, *end = src + srclen, *done = src;
+  const int bad = QH_ERR_QPACK_ENCODER_STREAM_ERROR;
+  const int big = QH_ERR_QPACK_HEADER_TOO_LARGE; /* qpack.c:2962-2972 */
+  int rv = 0;
+
+  while (p != end) {
+    uint8_t b = *p;
+    size_t l0 = o->nlines, s0 = o->nspans, h0 = o->nhuff;
+    uint64_t hs0 = o->hslots, nl0 = o->nlong;
+    qh_field_line *l;
+
+    if (b & 0x80u) {
+      l = new_line(o, QH_ES_INSERT_INDEXED, (b & 0x40u) ? 0 : QH_FL_DYNAMIC);
+      if (l == NULL) {
+        rv = QH_ERR_NOMEM;
+        break;
+      }
+      rv = read_varint(&l->index, &p, end, 6);
+      /* rel2abs -> validate_index (qpack.c:3952-3969, :2796-2797): a
+       * static name reference must be < 99, whatever the table holds */
+      if (rv > 0 && !(l->flags & QH_FL_DYNAMIC) &&
+          l->index >= QH_QPACK_STATIC_ENTRIES) {
+        rv = bad;
+      }
+      if (rv > 0) {
+        rv = read_string(o, &l->value, src, src_off, &p, end, 7,
+                         QH_QPACK_MAX_VALUELEN, 0, big, bad);
+      }
+    } else if (b & 0x40u) {
+      l = new_line(o, QH_ES_INSERT, 0);
+      if (l == NULL) {
+        rv = QH_ERR_NOMEM;
+        break;
+      }
+      rv = read_string(o, &l->name, src, src_off, &p, end, 5,
+                       QH_QPACK_MAX_NAMELEN, QH_SPAN_NAME, big, bad);
+      if (rv > 0) {
+        rv = read_string(o, &l->value, src, src_off, &p, end, 7,
+                         QH_QPACK_MAX_VALUELEN, 0, big, bad);
+      }
+    } else {
+      l = new_line(o, (b & 0x20u) ? QH_ES_SET_DTABLE_CAP : QH_ES_DUPLICATE,
+                   (b & 0x20u) ? 0 : QH_FL_DYNAMIC);
+      if (l == NULL) {
+        rv = QH_ERR_NOMEM;
+        break;
+      }
+      rv = read_varint(&l->index, &p, end, 5);
+    }
+    if (rv <= 0) { /* an error, or truncated (0): roll back this instruction */
+      if (rv == QH_ERR_QPACK_FATAL) {
+        rv = bad;
+      }
+      o->nlines = l0;
+      o->nspans = s0;
+      o->nhuff = h0;
+      o->hslots = hs0;
+      o->nlong = nl0;
+      break;
+    }
+    if (ends && o->lines) {
+      ends[l0] = (uint32_t)(p - src);
+    }
+    done = p;
+    rv = 0;
+  }
+  *done_out = (size_t)(done - src);
+  return rv;
+}
+
 #endif /* QH_QPACK_CORE_H */

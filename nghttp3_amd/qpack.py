@@ -49,6 +49,7 @@ FIELD_DTYPE = np.dtype([("name_off", "<u8"), ("value_off", "<u8"), ("name_len", 
                         ("value_where", "u1"), ("flags", "u1"), ("reserved", "u1")])
 DYN_ENTRY_DTYPE = np.dtype([("name_off", "<u8"), ("value_off", "<u8"), ("name_len", "<u4"),
                             ("value_len", "<u4"), ("token", "<i4"), ("reserved", "<u4")])
+ACCT_DTYPE = np.dtype([("hard_max", "<u8"), ("cap", "<u8"), ("size", "<u8"), ("reserved", "<u8")])
 VIEW_DTYPE = np.dtype([("ent_base", "<i8"), ("live_lo", "<u8"), ("insert_count", "<u8"),
                        ("max_entries", "<u8"), ("reserved", "<u8")])
 assert FIELD_DTYPE.itemsize == 32 and DYN_ENTRY_DTYPE.itemsize == 32 and VIEW_DTYPE.itemsize == 40
@@ -178,6 +179,14 @@ def _load():
         lib.qh_qpack_emit_fields.restype = i32
         lib.qh_emit_fields_batch.argtypes = [vp] + emit_args + [i32]
         lib.qh_emit_fields_batch.restype = i32
+        lib.qh_dtable_state_init.argtypes = [u64, vp, vp]
+        lib.qh_dtable_state_init.restype = None
+        dts_args = [vp, vp, vp, sz, sz, vp, vp, vp, c.POINTER(u64), u64, vp, c.POINTER(u64), u64,
+                    vp, vp]
+        lib.qh_qpack_dtables_apply.argtypes = dts_args
+        lib.qh_qpack_dtables_apply.restype = i32
+        lib.qh_dtables_apply_batch.argtypes = [vp] + dts_args + [i32]
+        lib.qh_dtables_apply_batch.restype = i32
         _L = lib
     return _L
 
@@ -849,6 +858,150 @@ class DynamicTable:
         views = torch.from_numpy(self.view().view(np.uint8).copy()).to(device)
         return {"views": views, "entries": d["entries"], "bytes": d["bytes"], "keys": d["keys"],
                 "nentries": int(ents.size), "nbytes": int(byts.size)}
+
+
+class DynamicTableSet:
+    """The dynamic tables of many connections over one log
+    (qh_dtables_apply_batch / qh_qpack_dtables_apply): `ntables` fresh tables
+    of hard maximum capacity `hard_max` (a scalar, or one value per table).
+
+    With a `codec` the views, acct records, the log and its keys are torch
+    tensors on the codec's device and ``read_encoder_dev`` applies encoder
+    streams there; ``views`` (uint8 [ntables * 40]), ``entries`` (uint8),
+    ``dyn_bytes`` (uint8), ``nentries`` and ``nbytes`` go straight into
+    ``emit_fields_dev(views=, entries=, dyn_bytes=, block_view=)`` and the
+    dynamic planners, ``keys()`` with them.  Without a codec the same state is
+    numpy arrays and ``read_encoder`` the host twin.  The log only grows: a
+    copy of ``views`` taken before a call stays valid after it."""
+
+    def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None):
+        self._lib = _load()
+        self.codec = codec
+        self.ntables = int(ntables)
+        hm = np.broadcast_to(np.asarray(hard_max, dtype=np.uint64), (self.ntables,))
+        views = np.zeros(max(self.ntables, 1), dtype=VIEW_DTYPE)[:self.ntables]
+        acct = np.zeros(max(self.ntables, 1), dtype=ACCT_DTYPE)[:self.ntables]
+        v1, a1 = np.zeros(1, dtype=VIEW_DTYPE), np.zeros(1, dtype=ACCT_DTYPE)
+        for t in range(self.ntables):
+            self._lib.qh_dtable_state_init(int(hm[t]), _vp(v1), _vp(a1))
+            views[t], acct[t] = v1[0], a1[0]
+        self.nentries = 0
+        self.nbytes = 0
+        self._nkeys = 0
+        if codec is None:
+            self.views, self.acct = views.view(np.uint8).copy(), acct.view(np.uint8).copy()
+            self.entries = np.zeros(0, dtype=np.uint8)
+            self.dyn_bytes = np.zeros(0, dtype=np.uint8)
+            self._keys = np.zeros(0, dtype=DYN_KEY_DTYPE)
+        else:
+            import torch
+            self._dev = torch.device("cuda", codec.device) if hasattr(codec, "device") else torch.device("cuda")
+            self.views = torch.from_numpy(views.view(np.uint8).copy()).to(self._dev)
+            self.acct = torch.from_numpy(acct.view(np.uint8).copy()).to(self._dev)
+            self.entries = torch.empty(0, dtype=torch.uint8, device=self._dev)
+            self.dyn_bytes = torch.empty(0, dtype=torch.uint8, device=self._dev)
+            self._keys = torch.empty(0, dtype=torch.uint8, device=self._dev)
+
+    # -- capacity: the arrays grow by doubling, the log's prefix kept
+
+    def _grow(self, name, have: int, need: int, minimum: int):
+        old = getattr(self, name)
+        size = old.size if isinstance(old, np.ndarray) else old.numel()
+        if need <= size:
+            return
+        cap = max(minimum, size)
+        while cap < need:
+            cap *= 2
+        if isinstance(old, np.ndarray):
+            new = np.zeros(cap, dtype=np.uint8)
+        else:
+            import torch
+            new = torch.empty(cap, dtype=torch.uint8, device=old.device)
+        new[:have] = old[:have]
+        setattr(self, name, new)
+
+    def _reserve(self, nentries: int, nbytes: int):
+        self._grow("entries", self.nentries * 32, nentries * 32, 4096)
+        self._grow("dyn_bytes", self.nbytes, nbytes, 4096)
+
+    def _apply(self, call, what: str):
+        # QH_ERR_NOMEM names the exact need: the arrays grow (by doubling, so
+        # that most calls find room) and the call is made once more
+        for _ in range(2):
+            ne, nb = ctypes.c_uint64(self.nentries), ctypes.c_uint64(self.nbytes)
+            rv = call(ne, nb)
+            if rv == _lib.QH_ERR_NOMEM:
+                self._reserve(int(ne.value), int(nb.value))
+                continue
+            break
+        _lib.check(rv, what)
+        self.nentries, self.nbytes = int(ne.value), int(nb.value)
+
+    def read_encoder_dev(self, src, streams, tsel=None):
+        """Applies encoder-stream bytes on the device: stream p is
+        src[streams[p, 0], + streams[p, 1] & 0xFFFFFFFF) (torch tensors in
+        HBM: src uint8, streams int64 [nsel, 2] as SPAN_IN_DTYPE records,
+        tsel int32 [nsel] or None for stream p -> table p).  -> (status int32
+        [nsel], consumed int32 [nsel]) tensors: per stream 0 or the first
+        failing instruction's error (-402, -109), and the bytes of complete,
+        applied instructions.  Asynchronous on the codec stream after the
+        call's host waits."""
+        import torch
+        nsel = self.ntables if tsel is None else int(tsel.shape[0])
+        status = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
+        consumed = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        # (an empty tensor has no address: an empty table list still has to
+        # be a list, not tsel = NULL's "stream p -> table p")
+        p_tsel = p(status) if tsel is not None and nsel == 0 else p(tsel)
+
+        def call(ne, nb):
+            return self._lib.qh_dtables_apply_batch(
+                self.codec._ctx, p(src), p(streams), p_tsel, nsel, self.ntables, p(self.views),
+                p(self.acct), p(self.entries), ctypes.byref(ne), self.entries.numel() // 32,
+                p(self.dyn_bytes), ctypes.byref(nb), self.dyn_bytes.numel(), p(status), p(consumed),
+                _lib.QH_WHERE_DEVICE)
+        self._apply(call, "qh_dtables_apply_batch")
+        return status[:nsel], consumed[:nsel]
+
+    def read_encoder(self, src, streams, tsel=None):
+        """The host twin (qh_qpack_dtables_apply) over numpy arrays: src
+        uint8, streams SPAN_IN_DTYPE, tsel uint32 or None.  -> (status int32,
+        consumed uint32)."""
+        src = _u8(src)
+        streams = np.ascontiguousarray(streams, dtype=SPAN_IN_DTYPE)
+        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
+        nsel = self.ntables if sel is None else sel.size
+        status = np.zeros(max(nsel, 1), dtype=np.int32)
+        consumed = np.zeros(max(nsel, 1), dtype=np.uint32)
+
+        def call(ne, nb):
+            return self._lib.qh_qpack_dtables_apply(
+                _vp(src), _vp(streams), None if sel is None else _vp(sel), nsel, self.ntables,
+                _vp(self.views), _vp(self.acct), _vp(self.entries), ctypes.byref(ne),
+                self.entries.size // 32, _vp(self.dyn_bytes), ctypes.byref(nb), self.dyn_bytes.size,
+                _vp(status), _vp(consumed))
+        self._apply(call, "qh_qpack_dtables_apply")
+        return status[:nsel], consumed[:nsel]
+
+    def keys(self):
+        """The log's keys (DYN_KEY_DTYPE records; a uint8 tensor of nentries *
+        16 bytes on the device), extended over the tail appended since the
+        last call (qh_dyn_keys_batch / qh_qpack_dyn_keys)."""
+        n = self.nentries
+        if self.codec is None:
+            if n > self._nkeys:
+                ents = self.entries[:n * 32].view(DYN_ENTRY_DTYPE)
+                self._keys = dyn_keys(ents, self.dyn_bytes[:self.nbytes], first=self._nkeys,
+                                      keys=self._keys)
+                self._nkeys = n
+            return self._keys
+        self._grow("_keys", self._nkeys * 16, n * 16, 4096)
+        if n > self._nkeys:
+            dyn_keys_dev(self.codec, self.entries, n, self.dyn_bytes, self.nbytes, self._nkeys,
+                         n - self._nkeys, self._keys)
+            self._nkeys = n
+        return self._keys[:n * 16]
 
 
 def dyn_keys(entries, dyn_bytes, first: int = 0, keys=None):
