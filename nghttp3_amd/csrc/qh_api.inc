@@ -38,8 +38,9 @@ enum BufId {
   kBufDtset,        // qh_dtables_apply_batch: per-stream counts, sizes and verdicts
   kBufDtsetWork,    // ... instructions, spans, the Huffman strings' spans, results and slots
   kBufEw,         // fused encoder: window records and ticket counters, two halves
-  kBufStage0,     // host-mode staging: src, spans in, dst, spans out
-  kBufPinned0 = kBufStage0 + 4,  // from here on: pinned host memory
+  kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
+  kBufStageDst,   // ... its dst, sized by dst_cap
+  kBufPinned0,    // from here on: pinned host memory
   kBufEhintHost = kBufPinned0,  // the hint's host copy
   kBufFrameHost,   // framing's totals read back (8 words)
   kBufEnds,        // host pipelines: a slice's dense end (64 words)
@@ -186,6 +187,19 @@ T *mem(const qh_ctx *c, int id) {
   return static_cast<T *>(c->buf[id].p);
 }
 
+// Buffer `id` cut into the pieces lay(l) takes (qhs::Layout): run over no
+// base for the total, the buffer reserved, then run over the buffer.
+template <class F>
+int reserve_layout(qh_ctx *c, int id, F &&lay, qhs::Policy pol = qhs::kPow2MiB) {
+  qhs::Layout sized, placed;
+  lay(sized);
+  const int rv = reserve(c, id, sized.total, pol);
+  if (rv) return rv;
+  placed.base = mem<uint8_t>(c, id);
+  lay(placed);
+  return 0;
+}
+
 // Events and streams owned by the context.
 int make_event(qh_ctx *c, hipEvent_t *e, unsigned flags = hipEventDisableTiming) {
   QH_HIP(hipEventCreateWithFlags(e, flags));
@@ -248,6 +262,27 @@ int launch_scan(qh_ctx *c, const SpanIn *in, SpanOut *out, uint64_t n) {
                      c->stream, in, out, n, states, ctr, c->d_stats);
   QH_HIP(hipGetLastError());
   return 0;
+}
+
+// qh_k_scan_seg over nseg segments of n entries each.  hdr (zeroed by the
+// caller): word 0 the tile counter, words `tot` on the segments' totals, word
+// `timeouts` the look-backs that gave up, from word `states` the tile states.
+int launch_scan_seg(qh_ctx *c, qhk::SpanOut *out, uint64_t n, uint32_t nseg, uint64_t *hdr,
+                    uint64_t states, uint64_t tot, uint64_t timeouts) {
+  const uint64_t tps = (n + qhk::kScanTile - 1) / qhk::kScanTile;
+  Timed t(c, "qh_k_scan_seg");
+  hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)(nseg * tps)), dim3(qhk::kBlock), 0,
+                     c->stream, out, n, nseg, hdr + states, reinterpret_cast<uint32_t *>(hdr),
+                     reinterpret_cast<unsigned long long *>(hdr + tot),
+                     reinterpret_cast<unsigned long long *>(hdr + timeouts));
+  QH_HIP(hipGetLastError());
+  return 0;
+}
+// The read-back `timeouts` word of such a scan: an error when not 0.
+int scan_seg_check(uint64_t timeouts, const char *what) {
+  if (!timeouts) return 0;
+  fprintf(stderr, "qhuff: %s scan look-back timed out\n", what);
+  return QH_ERR_FATAL;
 }
 
 int reset_stats(qh_ctx *c, uint64_t n) {
@@ -889,11 +924,14 @@ int decode_dense(qh_ctx *c, const uint8_t *src, const SpanIn *in, uint64_t n, ui
   if (rv || n == 0) return rv;
   // [0]: carry in, [1]: carry out, then the groups' decoded bytes
   const uint64_t words = 2 + (n + qhk::kDnGroup - 1) / qhk::kDnGroup;
-  const size_t st_b = (words * sizeof(uint64_t) + 255) & ~(size_t)255;
-  // (+16: qh_k_dense_pack loads 16 bytes at a short string's start)
-  if ((rv = reserve(c, kBufDense, st_b + dst_cap + 16))) return rv;
-  uint64_t *state = mem<uint64_t>(c, kBufDense);
-  uint8_t *slots = mem<uint8_t>(c, kBufDense) + st_b;
+  uint64_t *state;
+  uint8_t *slots;
+  rv = reserve_layout(c, kBufDense, [&](qhs::Layout &l) {
+    state = l.take<uint64_t>(words);
+    // (+16: qh_k_dense_pack loads 16 bytes at a short string's start)
+    slots = l.take<uint8_t>(dst_cap + 16);
+  });
+  if (rv) return rv;
   QH_HIP(hipMemsetAsync(state, 0, sizeof(uint64_t), c->stream));  // (the carry in)
   if ((rv = decode_device(c, src, in, n, slots, dst_cap, out, false))) return rv;
   return launch_dense_pack(c, slots, out, n, dst, dst_cap, (const unsigned long long *)state,
@@ -1062,19 +1100,23 @@ int decode_host_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *in, uint64
     extent = hi[k] > extent ? hi[k] : extent;
   }
   const uint64_t dcap = std::min<uint64_t>(dst_cap, sb[ns]);
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  // (the slots are followed by o_out: qh_k_dense_pack's 16-byte load at a
-  // short string's start stays inside the buffer)
-  const uint64_t o_in = al(extent), o_slots = o_in + al(n * 16), o_out = o_slots + al(sb[ns]);
-  const uint64_t o_tmp = o_out + al(n * 16), o_dense = o_tmp + al(n * 16);
-  const uint64_t o_carry = o_dense + al(dcap + 16), total = o_carry + 256;
-  if ((rv = reserve(c, kBufHostPipe, total))) return rv;
-  uint8_t *base = mem<uint8_t>(c, kBufHostPipe);
+  uint8_t *d_src, *d_slots, *d_dense;
+  SpanIn *d_in;
+  SpanOut *d_out, *d_tmp;
+  unsigned long long *d_carry;  // [0..ns]
+  rv = reserve_layout(c, kBufHostPipe, [&](qhs::Layout &l) {
+    d_src = l.take<uint8_t>(extent);
+    d_in = l.take<SpanIn>(n);
+    // (the slots are followed by d_out: qh_k_dense_pack's 16-byte load at a
+    // short string's start stays inside the buffer)
+    d_slots = l.take<uint8_t>(sb[ns]);
+    d_out = l.take<SpanOut>(n);
+    d_tmp = l.take<SpanOut>(n);
+    d_dense = l.take<uint8_t>(dcap + 16);
+    d_carry = l.take<unsigned long long>(kHostSlices + 1);
+  });
+  if (rv) return rv;
   unsigned long long *const h_ends = mem<unsigned long long>(c, kBufEnds);
-  uint8_t *d_src = base, *d_slots = base + o_slots, *d_dense = base + o_dense;
-  SpanIn *d_in = (SpanIn *)(base + o_in);
-  SpanOut *d_out = (SpanOut *)(base + o_out), *d_tmp = (SpanOut *)(base + o_tmp);
-  unsigned long long *d_carry = (unsigned long long *)(base + o_carry);  // [0..ns]
   QH_HIP(hipMemsetAsync(d_carry, 0, 8, c->stream));
   hipEvent_t *ev_h2d = c->hp_ev.data(), *ev_dec = c->hp_ev.data() + kHostSlices;
   // the copies may only start once the carry reset (and earlier work on
@@ -1199,12 +1241,27 @@ bool decoder_checks(const qh_ctx *c) {
   return variant(c).fn_check != nullptr;
 }
 
-// host-mode staging buffer k (0 = src, 1 = spans in, 2 = dst, 3 = spans out)
-int stage(qh_ctx *c, int k, size_t bytes, void **p) {
-  const int rv = reserve(c, kBufStage0 + k, bytes ? bytes : 16, qhs::kExact);
-  *p = mem(c, kBufStage0 + k);
+// Host-mode staging: a call's pieces (qhs::Staged) in kBufStage, its dst in
+// kBufStageDst (never null); the pieces' copies on the context's stream.
+int stage(qh_ctx *c, qhs::Staged &s) {
+  const int rv = reserve(c, kBufStage, s.sized.total ? s.sized.total : 16, qhs::kExact);
+  s.base = mem<uint8_t>(c, kBufStage);
   return rv;
 }
+int stage_dst(qh_ctx *c, uint64_t bytes, uint8_t **p) {
+  const int rv = reserve(c, kBufStageDst, bytes ? bytes : 16, qhs::kExact);
+  *p = mem<uint8_t>(c, kBufStageDst);
+  return rv;
+}
+int stage_copy(qh_ctx *c, const qhs::Staged &s, bool back) {
+  return s.copy(back, [&](void *to, const void *from, uint64_t bytes) -> int {
+    QH_HIP(hipMemcpyAsync(to, from, bytes, back ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice,
+                          c->stream));
+    return 0;
+  });
+}
+int stage_in(qh_ctx *c, const qhs::Staged &s) { return stage_copy(c, s, false); }
+int stage_out(qh_ctx *c, const qhs::Staged &s) { return stage_copy(c, s, true); }
 
 uint64_t src_extent(const qh_span_in *in, size_t n) {
   uint64_t e = 0;
@@ -1613,19 +1670,13 @@ QH_EXPORT int qh_encode_count_batch(qh_ctx *c, const uint8_t *src,
   }
   if (where != QH_WHERE_HOST) return QH_ERR_INVALID_ARGUMENT;
   const uint64_t extent = src_extent(in, n);
-  void *d_src, *d_in, *d_h;
-  if ((rv = stage(c, 0, extent, &d_src)) || (rv = stage(c, 1, n * 16, &d_in)) ||
-      (rv = stage(c, 3, n * 4, &d_h)))
+  qhs::Staged s;
+  const auto d_src = s.in(src, extent);
+  const auto d_in = s.in((const SpanIn *)in, n);
+  const auto d_h = s.out(hlen, n);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s)) || (rv = reset_stats(c, n))) return rv;
+  if (n && ((rv = count_device(c, s(d_src), s(d_in), n, s(d_h), nullptr)) || (rv = stage_out(c, s))))
     return rv;
-  QH_HIP(hipMemcpyAsync(d_src, src, extent, hipMemcpyHostToDevice, c->stream));
-  QH_HIP(hipMemcpyAsync(d_in, in, n * 16, hipMemcpyHostToDevice, c->stream));
-  if ((rv = reset_stats(c, n))) return rv;
-  if (n) {
-    rv = count_device(c, (const uint8_t *)d_src, (const SpanIn *)d_in, n,
-                      (uint32_t *)d_h, nullptr);
-    if (rv) return rv;
-    QH_HIP(hipMemcpyAsync(hlen, d_h, n * 4, hipMemcpyDeviceToHost, c->stream));
-  }
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1643,16 +1694,14 @@ QH_EXPORT int qh_encode_batch(qh_ctx *c, const uint8_t *src,
   const uint64_t extent = src_extent(in, n);
   const uint64_t bound = qh_encode_dst_bound(in, n);
   const uint64_t dcap = dst_cap < bound ? dst_cap : bound;
-  void *d_src, *d_in, *d_dst, *d_out;
-  if ((rv = stage(c, 0, extent, &d_src)) || (rv = stage(c, 1, n * 16, &d_in)) ||
-      (rv = stage(c, 2, dcap, &d_dst)) || (rv = stage(c, 3, n * 16, &d_out)))
+  uint8_t *d_dst;
+  qhs::Staged s;
+  const auto d_src = s.in(src, extent);
+  const auto d_in = s.in((const SpanIn *)in, n);
+  const auto d_out = s.out((SpanOut *)out, n);
+  if ((rv = stage(c, s)) || (rv = stage_dst(c, dcap, &d_dst)) || (rv = stage_in(c, s)) ||
+      (rv = encode_device(c, s(d_src), s(d_in), n, d_dst, dcap, s(d_out))) || (rv = stage_out(c, s)))
     return rv;
-  QH_HIP(hipMemcpyAsync(d_src, src, extent, hipMemcpyHostToDevice, c->stream));
-  QH_HIP(hipMemcpyAsync(d_in, in, n * 16, hipMemcpyHostToDevice, c->stream));
-  rv = encode_device(c, (const uint8_t *)d_src, (const SpanIn *)d_in, n,
-                     (uint8_t *)d_dst, dcap, (SpanOut *)d_out);
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(out, d_out, n * 16, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   // copy back only the bytes the dense layout occupies
   uint64_t used = 0;
@@ -1725,11 +1774,13 @@ QH_EXPORT int qh_synth_spans(qh_ctx *c, uint64_t seed, size_t n, uint32_t lo,
   hipLaunchKernelGGL(qh_k_synth_lens, dim3(blocks), dim3(kBlock), 0, c->stream,
                      seed, (uint64_t)n, lo, hi - lo + 1, in);
   QH_HIP(hipGetLastError());
-  void *tmp;
-  if ((rv = stage(c, 3, n * 16, &tmp))) return rv;
+  qhs::Staged s;
+  const auto d_tmp = s.take<SpanOut>(n);
+  if ((rv = stage(c, s))) return rv;
+  SpanOut *const tmp = s(d_tmp);
   hipLaunchKernelGGL(qh_k_copy_len, dim3(blocks), dim3(kBlock), 0, c->stream,
-                     in, (SpanOut *)tmp, (uint64_t)n);
-  if ((rv = launch_scan(c, in, (SpanOut *)tmp, n))) return rv;
+                     in, tmp, (uint64_t)n);
+  if ((rv = launch_scan(c, in, tmp, n))) return rv;
   hipLaunchKernelGGL(qh_k_set_off, dim3(blocks), dim3(kBlock), 0, c->stream,
                      in, (const SpanOut *)tmp, (uint64_t)n, total_dev);
   QH_HIP(hipGetLastError());
@@ -1744,15 +1795,14 @@ QH_EXPORT int qh_synth_fill(qh_ctx *c, uint64_t seed, uint64_t first, uint8_t *d
   if (!alphabet || alphabet_len == 0 || alphabet_len > 256 || (!dst_dev && nbytes))
     return QH_ERR_INVALID_ARGUMENT;
   if (nbytes == 0) return 0;
-  void *d_alph;
-  if ((rv = stage(c, 1, 256, &d_alph))) return rv;
-  QH_HIP(hipMemcpyAsync(d_alph, alphabet, alphabet_len, hipMemcpyHostToDevice,
-                        c->stream));
+  qhs::Staged s;
+  const auto d_alph = s.in(alphabet, alphabet_len);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s))) return rv;
   uint64_t blocks = (nbytes / 4 + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(qh_k_synth_fill, dim3((unsigned)blocks), dim3(kBlock), 0,
-                     c->stream, seed, first, dst_dev, nbytes, (const uint8_t *)d_alph,
+                     c->stream, seed, first, dst_dev, nbytes, s(d_alph),
                      alphabet_len);
   QH_HIP(hipGetLastError());
   // the alphabet staging buffer is reused by later host-mode calls: wait

@@ -325,26 +325,18 @@ struct DtWork {
   qhk::DtCaps caps{0, 0, 0};
 };
 int dts_work(qh_ctx *c, uint64_t ni, uint64_t ns, uint64_t nh, uint64_t slots_b, DtWork &W) {
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
   W.slots_cap = slots_b + 64 * nh;
-  const uint64_t o_ends = al(ni * sizeof(qh_field_line)), o_lens = o_ends + al(ni * 4),
-                 o_spans = o_lens + al(ni * 8), o_aux = o_spans + al(ns * sizeof(qh_span_in)),
-                 o_huff = o_aux + al(ns * 8), o_hout = o_huff + al(nh * sizeof(qh_span_in)),
-                 o_slots = o_hout + al(nh * sizeof(qh_span_out)),
-                 total = o_slots + al(W.slots_cap + 16);
-  const int rv = reserve(c, kBufDtsetWork, total);
-  if (rv) return rv;
-  uint8_t *b = mem<uint8_t>(c, kBufDtsetWork);
-  W.insts = reinterpret_cast<qh_field_line *>(b);
-  W.ends = reinterpret_cast<uint32_t *>(b + o_ends);
-  W.lens = reinterpret_cast<uint32_t *>(b + o_lens);
-  W.spans = reinterpret_cast<qhk::SpanIn *>(b + o_spans);
-  W.aux = reinterpret_cast<uint64_t *>(b + o_aux);
-  W.huff = reinterpret_cast<qhk::SpanIn *>(b + o_huff);
-  W.hout = reinterpret_cast<qhk::SpanOut *>(b + o_hout);
-  W.slots = b + o_slots;
   W.caps = qhk::DtCaps{ni, ns, nh};
-  return 0;
+  return reserve_layout(c, kBufDtsetWork, [&](qhs::Layout &l) {
+    W.insts = l.take<qh_field_line>(ni);
+    W.ends = l.take<uint32_t>(ni);
+    W.lens = l.take<uint32_t>(2 * ni);
+    W.spans = l.take<qhk::SpanIn>(ns);
+    W.aux = l.take<uint64_t>(ns);
+    W.huff = l.take<qhk::SpanIn>(nh);
+    W.hout = l.take<qhk::SpanOut>(nh);
+    W.slots = l.take<uint8_t>(W.slots_cap + 16);
+  });
 }
 
 }  // namespace
@@ -384,27 +376,27 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
   const qh_static_rec *stat = reinterpret_cast<const qh_static_rec *>(simg);
   const uint8_t *stat_bytes = simg + qhk::kEmStatRecs;
   const uint64_t ne0 = *nentries, nb0 = *nbytes;
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
 
   // per-stream scratch, sized by the table list alone: the four counts, the
   // two sizes, verdicts, owners, and the two scans' headers and tile states
   const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
   const uint64_t hwords = qhk::kDtHdr + 4 * tps;
-  const uint64_t o_cnt2 = al(4 * (uint64_t)nsel * sizeof(qhk::SpanOut)),
-                 o_res = o_cnt2 + al(2 * (uint64_t)nsel * sizeof(qhk::SpanOut)),
-                 o_sv = o_res + al((uint64_t)nsel * sizeof(qhk::DtRes)),
-                 o_done = o_sv + al((uint64_t)nsel * 4), o_owner = o_done + al((uint64_t)nsel * 4),
-                 o_hdr = o_owner + al((uint64_t)ntables * 4),
-                 total1 = o_hdr + al(2 * hwords * sizeof(uint64_t));
-  if ((rv = reserve(c, kBufDtset, total1))) return rv;
-  uint8_t *b1 = mem<uint8_t>(c, kBufDtset);
-  qhk::SpanOut *cnt = reinterpret_cast<qhk::SpanOut *>(b1);
-  qhk::SpanOut *cnt2 = reinterpret_cast<qhk::SpanOut *>(b1 + o_cnt2);
-  qhk::DtRes *res = reinterpret_cast<qhk::DtRes *>(b1 + o_res);
-  int32_t *sv = reinterpret_cast<int32_t *>(b1 + o_sv);
-  uint32_t *done = reinterpret_cast<uint32_t *>(b1 + o_done);
-  uint32_t *owner = reinterpret_cast<uint32_t *>(b1 + o_owner);
-  uint64_t *hdr_a = reinterpret_cast<uint64_t *>(b1 + o_hdr), *hdr_b = hdr_a + hwords;
+  qhk::SpanOut *cnt, *cnt2;
+  qhk::DtRes *res;
+  int32_t *sv;
+  uint32_t *done, *owner;
+  uint64_t *hdr_a;
+  rv = reserve_layout(c, kBufDtset, [&](qhs::Layout &l) {
+    cnt = l.take<qhk::SpanOut>(4 * (uint64_t)nsel);
+    cnt2 = l.take<qhk::SpanOut>(2 * (uint64_t)nsel);
+    res = l.take<qhk::DtRes>(nsel);
+    sv = l.take<int32_t>(nsel);
+    done = l.take<uint32_t>(nsel);
+    owner = l.take<uint32_t>(ntables);
+    hdr_a = l.take<uint64_t>(2 * hwords);
+  });
+  if (rv) return rv;
+  uint64_t *const hdr_b = hdr_a + hwords;
   if ((rv = reserve(c, kBufDtsetHost, 16 * sizeof(uint64_t), qhs::kExact))) return rv;
   uint64_t *h = mem<uint64_t>(c, kBufDtsetHost);  // [0, 7): the parser's words 1-7, [8, 15): the size pass's
   DtWork W;
@@ -429,25 +421,14 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
     QH_HIP(hipGetLastError());
   }
   auto scan = [&](qhk::SpanOut *x, uint32_t nseg, uint64_t *hdr) -> int {
-    Timed t(c, "qh_k_scan_seg");
-    hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)(nseg * tps)), dim3(qhk::kBlock), 0,
-                       c->stream, x, (uint64_t)nsel, nseg, hdr + qhk::kDtHdr,
-                       reinterpret_cast<uint32_t *>(hdr),
-                       reinterpret_cast<unsigned long long *>(hdr + qhk::kDtTot),
-                       reinterpret_cast<unsigned long long *>(hdr + qhk::kDtTimeouts));
-    QH_HIP(hipGetLastError());
-    return 0;
+    return launch_scan_seg(c, x, nsel, nseg, hdr, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts);
   };
   // words 1-7 of both headers, one wait
   auto totals = [&]() -> int {
     QH_HIP(hipMemcpyAsync(h, hdr_a + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     QH_HIP(hipMemcpyAsync(h + 8, hdr_b + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     QH_HIP(hipStreamSynchronize(c->stream));
-    if (h[qhk::kDtTimeouts - 1] || h[8 + qhk::kDtTimeouts - 1]) {
-      fprintf(stderr, "qhuff: table-set scan look-back timed out\n");
-      return QH_ERR_FATAL;
-    }
-    return 0;
+    return scan_seg_check(h[qhk::kDtTimeouts - 1] | h[8 + qhk::kDtTimeouts - 1], "table-set");
   };
   // write -> decode -> size -> scan over W's layout
   auto chain = [&]() -> int {

@@ -363,15 +363,15 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
   // the two counts per selected block, a field record per line, the long
   // strings' list (two per line at most)
   const uint64_t nl = s->nlines;
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const uint64_t o_tmp = al(2 * (uint64_t)nsel * sizeof(qhk::SpanOut)),
-                 o_list = o_tmp + al(nl * sizeof(qh_field)),
-                 total = o_list + al(2 * nl * sizeof(qhk::EmLong));
-  if ((rv = reserve(c, kBufEmit, total))) return rv;
-  uint8_t *base = mem<uint8_t>(c, kBufEmit);
-  qhk::SpanOut *cnt = reinterpret_cast<qhk::SpanOut *>(base);
-  qh_field *tmp = reinterpret_cast<qh_field *>(base + o_tmp);
-  qhk::EmLong *list = reinterpret_cast<qhk::EmLong *>(base + o_list);
+  qhk::SpanOut *cnt;
+  qh_field *tmp;
+  qhk::EmLong *list;
+  rv = reserve_layout(c, kBufEmit, [&](qhs::Layout &l) {
+    cnt = l.take<qhk::SpanOut>(2 * (uint64_t)nsel);
+    tmp = l.take<qh_field>(nl);
+    list = l.take<qhk::EmLong>(2 * nl);
+  });
+  if (rv) return rv;
   const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
   const uint64_t hwords = qhk::kEmHdr + 2 * tps;
   if ((rv = ensure_tile_state(c, hwords * qhk::kScanTile))) return rv;
@@ -386,15 +386,8 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
                        hdr);
     QH_HIP(hipGetLastError());
   }
-  {
-    Timed t(c, "qh_k_scan_seg");
-    hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)(2 * tps)), dim3(qhk::kBlock), 0,
-                       c->stream, cnt, (uint64_t)nsel, 2u, hdr + qhk::kEmHdr,
-                       reinterpret_cast<uint32_t *>(hdr),
-                       reinterpret_cast<unsigned long long *>(hdr + qhk::kEmFields),
-                       reinterpret_cast<unsigned long long *>(hdr + qhk::kEmTimeouts));
-    QH_HIP(hipGetLastError());
-  }
+  if ((rv = launch_scan_seg(c, cnt, nsel, 2, hdr, qhk::kEmHdr, qhk::kEmFields, qhk::kEmTimeouts)))
+    return rv;
   if ((rv = reserve(c, kBufEmitHost, 8 * sizeof(uint64_t), qhs::kExact))) return rv;
   uint64_t *h = mem<uint64_t>(c, kBufEmitHost);
   QH_HIP(hipMemcpyAsync(h, hdr + 1, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -402,10 +395,7 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
   e->nfields = h[0];
   e->out_need = h[1];
   e->nblocked = h[3];
-  if (h[2]) {
-    fprintf(stderr, "qhuff: field scan look-back timed out\n");
-    return QH_ERR_FATAL;
-  }
+  if ((rv = scan_seg_check(h[2], "field"))) return rv;
   if (h[4] || e->nfields > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;
   if (e->nfields > e->fields_cap || (e->out && e->out_need > e->out_cap)) return QH_ERR_NOMEM;
   if (e->nfields && !e->fields) return QH_ERR_INVALID_ARGUMENT;

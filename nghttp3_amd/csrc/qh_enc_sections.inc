@@ -329,15 +329,15 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   const uint64_t ns = e.nstrs, nb = e.nsec;
   uint64_t nl = e.nlines;
   // scratch: hlen, in2, eout (per string); the per-line offsets apart
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const uint64_t o_in2 = al(ns * 4), o_eout = o_in2 + al(ns * 16);
-  const uint64_t total = o_eout + al(ns * 16);
-  int rv = reserve(c, kBufEncSec, total);
+  uint32_t *hlen;
+  qhk::SpanIn *in2;
+  qhk::SpanOut *eout;
+  int rv = reserve_layout(c, kBufEncSec, [&](qhs::Layout &l) {
+    hlen = l.take<uint32_t>(ns);
+    in2 = l.take<qhk::SpanIn>(ns);
+    eout = l.take<qhk::SpanOut>(ns);
+  });
   if (rv) return rv;
-  uint8_t *base = mem<uint8_t>(c, kBufEncSec);
-  uint32_t *hlen = (uint32_t *)base;
-  qhk::SpanIn *in2 = (qhk::SpanIn *)(base + o_in2);
-  qhk::SpanOut *eout = (qhk::SpanOut *)(base + o_eout);
   const uint64_t lcap = nl != kLinesUnknown ? nl : c->es_nl_hint;
   if ((rv = reserve(c, kBufEncSecLoff, lcap * 8 + 64))) return rv;
   // the sections scan's tile states behind a header (word 0 the tile counter,
@@ -383,14 +383,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
     return 0;
   };
   if ((rv = size_pass(lcap))) return rv;
-  {
-    Timed t(c, "qh_k_scan_seg");
-    hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)tps), dim3(qhk::kBlock), 0, c->stream,
-                       sec, nb, 1u, hdr + kHdr, reinterpret_cast<uint32_t *>(hdr),
-                       reinterpret_cast<unsigned long long *>(hdr + 1),
-                       reinterpret_cast<unsigned long long *>(hdr + 4));
-    QH_HIP(hipGetLastError());
-  }
+  if ((rv = launch_scan_seg(c, sec, nb, 1, hdr, kHdr, 1, 4))) return rv;
   if (!c->es_ev && ((rv = reserve(c, kBufEncSecHost, 8 * sizeof(uint64_t), qhs::kExact)) ||
                     (rv = make_event(c, &c->es_ev))))
     return rv;
@@ -414,10 +407,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
   uint64_t h[5];
   memcpy(h, mem(c, kBufEncSecHost), sizeof(h));
   if ((int32_t)(h[2] & 0xFFFFFFFFu)) return QH_ERR_INVALID_ARGUMENT;
-  if (h[3]) {
-    fprintf(stderr, "qhuff: section scan look-back timed out\n");
-    return QH_ERR_FATAL;
-  }
+  if ((rv = scan_seg_check(h[3], "section"))) return rv;
   nl = h[4];
   e.nlines = nl;
   c->es_nl_hint = std::max<uint64_t>(c->es_nl_hint, nl);
@@ -490,36 +480,20 @@ QH_EXPORT int qh_encode_sections_batch(qh_ctx *c, const uint8_t *plain, const qh
   const size_t nl = line_start[nsections];
   if (nl && !lines) return QH_ERR_INVALID_ARGUMENT;
   const uint64_t extent = src_extent(strs, nstrs);
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const uint64_t o_strs = al(extent), o_lines = o_strs + al(nstrs * 16),
-                 o_ls = o_lines + al(nl * sizeof(qh_field_line)),
-                 o_pf = o_ls + al((nsections + 1) * 4),
-                 o_sec = o_pf + al(prefixes ? nsections * sizeof(qh_section_prefix) : 0),
-                 in_total = o_sec + al(nsections * 16);
-  void *din;
-  if ((rv = stage(c, 0, in_total, &din))) return rv;
-  uint8_t *d = (uint8_t *)din;
-  if (extent) QH_HIP(hipMemcpyAsync(d, plain, extent, hipMemcpyHostToDevice, c->stream));
-  if (nstrs) QH_HIP(hipMemcpyAsync(d + o_strs, strs, nstrs * 16, hipMemcpyHostToDevice, c->stream));
-  if (nl)
-    QH_HIP(hipMemcpyAsync(d + o_lines, lines, nl * sizeof(qh_field_line), hipMemcpyHostToDevice,
-                          c->stream));
-  QH_HIP(hipMemcpyAsync(d + o_ls, line_start, (nsections + 1) * 4, hipMemcpyHostToDevice,
-                        c->stream));
-  if (prefixes)
-    QH_HIP(hipMemcpyAsync(d + o_pf, prefixes, nsections * sizeof(qh_section_prefix),
-                          hipMemcpyHostToDevice, c->stream));
-  // dst staging is sized after the sizing pass: run it with cap 0 first
-  void *dout;
-  if ((rv = stage(c, 2, dst_cap ? dst_cap : 16, &dout))) return rv;
-  EncSec e{d, (const qh_span_in *)(d + o_strs), nstrs, (const qh_field_line *)(d + o_lines),
-           (const uint32_t *)(d + o_ls), nsections, nl,
-           prefixes ? (const qh_section_prefix *)(d + o_pf) : nullptr, (uint8_t *)dout, dst_cap,
-           (qh_span_in *)(d + o_sec), 0};
+  uint8_t *dout;
+  qhs::Staged s;
+  const auto d_src = s.in(plain, extent);
+  const auto d_strs = s.in(strs, nstrs);
+  const auto d_lines = s.in(lines, nl);
+  const auto d_ls = s.in(line_start, nsections + 1);
+  const auto d_pf = s.in(prefixes, prefixes ? nsections : 0);
+  const auto d_sec = s.out(sections, nsections);
+  if ((rv = stage(c, s)) || (rv = stage_dst(c, dst_cap, &dout)) || (rv = stage_in(c, s))) return rv;
+  EncSec e{s(d_src), s(d_strs), nstrs, s(d_lines), s(d_ls), nsections, nl,
+           prefixes ? s(d_pf) : nullptr, dout, dst_cap, s(d_sec), 0};
   rv = encsec_device(c, e);
   if (dst_need) *dst_need = e.need;
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(sections, d + o_sec, nsections * 16, hipMemcpyDeviceToHost, c->stream));
+  if (rv || (rv = stage_out(c, s))) return rv;
   if (e.need) QH_HIP(hipMemcpyAsync(dst, dout, e.need, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;

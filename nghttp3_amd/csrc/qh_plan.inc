@@ -209,12 +209,11 @@ struct PlanScratch {
   qh_field_line *lines;
 };
 int plan_scratch(qh_ctx *c, uint64_t n, PlanScratch *s) {
-  const uint64_t o_lines = (2 * n * sizeof(qh_span_in) + 255) & ~(uint64_t)255;
-  const int rv = reserve(c, kBufPlan, o_lines + n * sizeof(qh_field_line) + 256);
-  if (rv) return rv;
-  s->strs = mem<qh_span_in>(c, kBufPlan);
-  s->lines = reinterpret_cast<qh_field_line *>(mem<uint8_t>(c, kBufPlan) + o_lines);
-  return 0;
+  return reserve_layout(c, kBufPlan, [&](qhs::Layout &l) {
+    s->strs = l.take<qh_span_in>(2 * n);
+    s->lines = l.take<qh_field_line>(n);
+    l.take<uint8_t>(256);
+  });
 }
 
 // fields -> scratch -> sections; every pointer device-resident.
@@ -247,20 +246,16 @@ QH_EXPORT int qh_plan_fields_batch(qh_ctx *c, const uint8_t *plain, const qh_spa
   if (where != QH_WHERE_HOST) return QH_ERR_INVALID_ARGUMENT;
   if (nfields == 0) return 0;
   const uint64_t extent = src_extent(strs, 2 * nfields);
-  void *d_src, *d_in, *d_lines, *d_never;
-  if ((rv = stage(c, 0, extent, &d_src)) || (rv = stage(c, 1, 2 * nfields * sizeof(qh_span_in), &d_in)) ||
-      (rv = stage(c, 2, nfields * sizeof(qh_field_line), &d_lines)) ||
-      (rv = stage(c, 3, nfields, &d_never)))
+  qhs::Staged s;
+  const auto d_src = s.in(plain, extent);
+  const auto d_in = s.in(strs, 2 * nfields);
+  const auto d_never = s.in(never, never ? nfields : 0);
+  const auto d_lines = s.out(lines, nfields);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s)) ||
+      (rv = plan_device(c, s(d_src), s(d_in), nullptr, nfields, never ? s(d_never) : nullptr,
+                        s(d_lines), nullptr)) ||
+      (rv = stage_out(c, s)))
     return rv;
-  if (extent) QH_HIP(hipMemcpyAsync(d_src, plain, extent, hipMemcpyHostToDevice, c->stream));
-  QH_HIP(hipMemcpyAsync(d_in, strs, 2 * nfields * sizeof(qh_span_in), hipMemcpyHostToDevice,
-                        c->stream));
-  if (never) QH_HIP(hipMemcpyAsync(d_never, never, nfields, hipMemcpyHostToDevice, c->stream));
-  rv = plan_device(c, (const uint8_t *)d_src, (const qh_span_in *)d_in, nullptr, nfields,
-                   never ? (const uint8_t *)d_never : nullptr, (qh_field_line *)d_lines, nullptr);
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(lines, d_lines, nfields * sizeof(qh_field_line), hipMemcpyDeviceToHost,
-                        c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -290,25 +285,17 @@ QH_EXPORT int qh_encode_fields_batch(qh_ctx *c, const uint8_t *plain, const qh_f
   for (size_t i = 0; i < nfields; ++i)
     extent = std::max(extent, std::max(fields[i].name_off + fields[i].name_len,
                                        fields[i].value_off + fields[i].value_len));
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const uint64_t o_f = al(extent), o_fs = o_f + al(nfields * sizeof(qh_field)),
-                 o_sec = o_fs + al((nsections + 1) * 4), in_total = o_sec + al(nsections * 16);
-  void *din, *dout;
-  if ((rv = stage(c, 0, in_total, &din)) || (rv = stage(c, 2, dst_cap ? dst_cap : 16, &dout)))
-    return rv;
-  uint8_t *d = (uint8_t *)din;
-  if (extent) QH_HIP(hipMemcpyAsync(d, plain, extent, hipMemcpyHostToDevice, c->stream));
-  if (nfields)
-    QH_HIP(hipMemcpyAsync(d + o_f, fields, nfields * sizeof(qh_field), hipMemcpyHostToDevice,
-                          c->stream));
-  QH_HIP(hipMemcpyAsync(d + o_fs, field_start, (nsections + 1) * 4, hipMemcpyHostToDevice,
-                        c->stream));
-  rv = encode_fields_device(c, d, (const qh_field *)(d + o_f), nfields,
-                            (const uint32_t *)(d + o_fs), nsections, (uint8_t *)dout, dst_cap,
-                            (qh_span_in *)(d + o_sec), &need);
+  uint8_t *dout;
+  qhs::Staged s;
+  const auto d_src = s.in(plain, extent);
+  const auto d_f = s.in(fields, nfields);
+  const auto d_fs = s.in(field_start, nsections + 1);
+  const auto d_sec = s.out(sections, nsections);
+  if ((rv = stage(c, s)) || (rv = stage_dst(c, dst_cap, &dout)) || (rv = stage_in(c, s))) return rv;
+  rv = encode_fields_device(c, s(d_src), s(d_f), nfields, s(d_fs), nsections, dout, dst_cap,
+                            s(d_sec), &need);
   if (dst_need) *dst_need = need;
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(sections, d + o_sec, nsections * 16, hipMemcpyDeviceToHost, c->stream));
+  if (rv || (rv = stage_out(c, s))) return rv;
   if (need) QH_HIP(hipMemcpyAsync(dst, dout, need, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;

@@ -373,67 +373,39 @@ int dyn_keys_device(qh_ctx *c, const qh_dyn_entry *entries, const uint8_t *bytes
   return 0;
 }
 
-// A host call's pieces in one staging buffer: 256-byte aligned, copied in
-// by `in`, back by `out`.
-struct Staging {
-  struct Piece {
-    const void *src;
-    void *back;
-    uint64_t bytes, off;
-  };
-  std::vector<Piece> pieces;
-  uint64_t total = 0;
-  size_t add(const void *src, void *back, uint64_t bytes) {
-    pieces.push_back({src, back, bytes, total});
-    total += (bytes + 255) & ~(uint64_t)255;
-    return pieces.size() - 1;
-  }
-  template <class T>
-  T *at(uint8_t *base, size_t k) const {
-    return reinterpret_cast<T *>(base + pieces[k].off);
-  }
-  int in(qh_ctx *c, uint8_t *base) const {
-    for (const Piece &p : pieces)
-      if (p.src && p.bytes)
-        QH_HIP(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, c->stream));
-    return 0;
-  }
-  int out(qh_ctx *c, uint8_t *base) const {
-    for (const Piece &p : pieces)
-      if (p.back && p.bytes)
-        QH_HIP(hipMemcpyAsync(p.back, base + p.off, p.bytes, hipMemcpyDeviceToHost, c->stream));
-    return 0;
-  }
-};
-
-// The table states of a host call: their pieces, and the device's qh_plan_dyn.
+// The table states of a host call: their kPieces pieces, and (once the
+// staging buffer is reserved) the device's qh_plan_dyn.
 struct DynStaged {
-  size_t views, sv, rl, ents, keys, bytes;
-  bool any;
+  static constexpr int kPieces = 6;
+  const qh_plan_dyn *d = nullptr;  // null: no table state
+  qhs::Staged::Ref<qh_dtable_view> views;
+  qhs::Staged::Ref<uint32_t> sv;
+  qhs::Staged::Ref<uint64_t> rl;
+  qhs::Staged::Ref<qh_dyn_entry> ents;
+  qhs::Staged::Ref<qh_dyn_key> keys;
+  qhs::Staged::Ref<uint8_t> bytes;
+  DynStaged(qhs::Staged &s, const qh_plan_dyn *dyn, uint64_t nsec) {
+    if (!dyn || !dyn->nviews) return;
+    d = dyn;
+    views = s.in(d->views, d->nviews);
+    sv = s.in(d->section_view, d->section_view ? nsec : 0);
+    rl = s.in(d->ref_limit, d->ref_limit ? nsec : 0);
+    ents = s.in(d->dyn_entries, d->nentries);
+    keys = s.in(d->dyn_keys, d->nentries);
+    bytes = s.in(d->dyn_bytes, d->nbytes);
+  }
+  qh_plan_dyn on_device(const qhs::Staged &s) const {
+    if (!d) return kNoDyn;
+    qh_plan_dyn o = *d;
+    o.views = s(views);
+    o.section_view = d->section_view ? s(sv) : nullptr;
+    o.ref_limit = d->ref_limit ? s(rl) : nullptr;
+    o.dyn_entries = s(ents);
+    o.dyn_keys = s(keys);
+    o.dyn_bytes = s(bytes);
+    return o;
+  }
 };
-DynStaged stage_dyn(Staging &s, const qh_plan_dyn *d, uint64_t nsec) {
-  DynStaged k{};
-  k.any = d && d->nviews;
-  if (!k.any) return k;
-  k.views = s.add(d->views, nullptr, d->nviews * sizeof(qh_dtable_view));
-  k.sv = s.add(d->section_view, nullptr, d->section_view ? nsec * 4 : 0);
-  k.rl = s.add(d->ref_limit, nullptr, d->ref_limit ? nsec * 8 : 0);
-  k.ents = s.add(d->dyn_entries, nullptr, d->nentries * sizeof(qh_dyn_entry));
-  k.keys = s.add(d->dyn_keys, nullptr, d->nentries * sizeof(qh_dyn_key));
-  k.bytes = s.add(d->dyn_bytes, nullptr, d->nbytes);
-  return k;
-}
-qh_plan_dyn staged_dyn(const Staging &s, const DynStaged &k, uint8_t *base, const qh_plan_dyn *d) {
-  if (!k.any) return kNoDyn;
-  qh_plan_dyn o = *d;
-  o.views = s.at<const qh_dtable_view>(base, k.views);
-  o.section_view = d->section_view ? s.at<const uint32_t>(base, k.sv) : nullptr;
-  o.ref_limit = d->ref_limit ? s.at<const uint64_t>(base, k.rl) : nullptr;
-  o.dyn_entries = s.at<const qh_dyn_entry>(base, k.ents);
-  o.dyn_keys = s.at<const qh_dyn_key>(base, k.keys);
-  o.dyn_bytes = s.at<const uint8_t>(base, k.bytes);
-  return o;
-}
 
 // The spans, lines, prefixes and counts of a qh_encode_fields_dyn_batch call
 // in kBufPlan (the counts alone when n == 0 and pfx is not wanted).
@@ -444,19 +416,14 @@ struct PlanDynScratch {
   uint64_t *mx, *mn;
 };
 int plan_dyn_scratch(qh_ctx *c, uint64_t n, uint64_t nsec, PlanDynScratch *s) {
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const uint64_t o_lines = al(2 * n * sizeof(qh_span_in)),
-                 o_pfx = o_lines + al(n * sizeof(qh_field_line)),
-                 o_mx = o_pfx + al(nsec * sizeof(qh_section_prefix)), o_mn = o_mx + al(nsec * 8);
-  const int rv = reserve(c, kBufPlan, o_mn + al(nsec * 8) + 256);
-  if (rv) return rv;
-  uint8_t *const base = mem<uint8_t>(c, kBufPlan);
-  s->strs = reinterpret_cast<qh_span_in *>(base);
-  s->lines = reinterpret_cast<qh_field_line *>(base + o_lines);
-  s->pfx = reinterpret_cast<qh_section_prefix *>(base + o_pfx);
-  s->mx = reinterpret_cast<uint64_t *>(base + o_mx);
-  s->mn = reinterpret_cast<uint64_t *>(base + o_mn);
-  return 0;
+  return reserve_layout(c, kBufPlan, [&](qhs::Layout &l) {
+    s->strs = l.take<qh_span_in>(2 * n);
+    s->lines = l.take<qh_field_line>(n);
+    s->pfx = l.take<qh_section_prefix>(nsec);
+    s->mx = l.take<uint64_t>(nsec);
+    s->mn = l.take<uint64_t>(nsec);
+    l.take<uint8_t>(256);
+  });
 }
 
 // fields -> scratch -> sections; every pointer device-resident.
@@ -491,17 +458,12 @@ QH_EXPORT int qh_dyn_keys_batch(qh_ctx *c, const qh_dyn_entry *entries, size_t n
   if (where == QH_WHERE_DEVICE) return dyn_keys_device(c, entries, bytes, nbytes, first, n, keys);
   if (where != QH_WHERE_HOST) return QH_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
-  Staging s;
-  const size_t k_e = s.add(entries + first, nullptr, n * sizeof(qh_dyn_entry)),
-               k_b = s.add(bytes, nullptr, nbytes),
-               k_k = s.add(nullptr, keys + first, n * sizeof(qh_dyn_key));
-  void *din;
-  if ((rv = stage(c, 0, s.total, &din))) return rv;
-  uint8_t *const d = (uint8_t *)din;
-  if ((rv = s.in(c, d)) ||
-      (rv = dyn_keys_device(c, s.at<const qh_dyn_entry>(d, k_e), s.at<const uint8_t>(d, k_b), nbytes,
-                            0, n, s.at<qh_dyn_key>(d, k_k))) ||
-      (rv = s.out(c, d)))
+  qhs::Staged s;
+  const auto d_e = s.in(entries + first, n);
+  const auto d_b = s.in(bytes, nbytes);
+  const auto d_k = s.out(keys + first, n);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s)) ||
+      (rv = dyn_keys_device(c, s(d_e), s(d_b), nbytes, 0, n, s(d_k))) || (rv = stage_out(c, s)))
     return rv;
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
@@ -532,28 +494,25 @@ QH_EXPORT int qh_plan_fields_dyn_batch(qh_ctx *c, const uint8_t *plain, const qh
                            lines, nullptr, prefixes, max_cnt, min_cnt);
   }
   if (field_start[0] != 0 || field_start[nsections] != nfields) return QH_ERR_INVALID_ARGUMENT;
-  Staging s;
-  const size_t k_src = s.add(plain, nullptr, src_extent(strs, 2 * nfields)),
-               k_in = s.add(strs, nullptr, 2 * nfields * sizeof(qh_span_in)),
-               k_nv = s.add(never, nullptr, never ? nfields : 0),
-               k_fs = s.add(field_start, nullptr, (nsections + 1) * 4);
-  const DynStaged ks = stage_dyn(s, dyn, nsections);
-  const size_t k_lines = s.add(nullptr, lines, nfields * sizeof(qh_field_line)),
-               k_pfx = s.add(nullptr, prefixes, nsections * sizeof(qh_section_prefix)),
-               k_mx = s.add(nullptr, max_cnt, nsections * 8),
-               k_mn = s.add(nullptr, min_cnt, nsections * 8);
-  void *din;
-  if ((rv = stage(c, 0, s.total, &din))) return rv;
-  uint8_t *const d = (uint8_t *)din;
-  const qh_plan_dyn dd = staged_dyn(s, ks, d, dyn);
-  if ((rv = s.in(c, d)) ||
-      (rv = plan_dyn_device(c, s.at<const uint8_t>(d, k_src), s.at<const qh_span_in>(d, k_in),
-                            nullptr, nfields, never ? s.at<const uint8_t>(d, k_nv) : nullptr,
-                            s.at<const uint32_t>(d, k_fs), nsections, &dd,
-                            s.at<qh_field_line>(d, k_lines), nullptr,
-                            s.at<qh_section_prefix>(d, k_pfx), s.at<uint64_t>(d, k_mx),
-                            s.at<uint64_t>(d, k_mn))) ||
-      (rv = s.out(c, d)))
+  // (the most pieces of any host call)
+  static_assert(4 + DynStaged::kPieces + 4 <= qhs::kStagePieces, "qhs::Staged::piece");
+  qhs::Staged s;
+  const auto d_src = s.in(plain, src_extent(strs, 2 * nfields));
+  const auto d_in = s.in(strs, 2 * nfields);
+  const auto d_nv = s.in(never, never ? nfields : 0);
+  const auto d_fs = s.in(field_start, nsections + 1);
+  const DynStaged ks(s, dyn, nsections);
+  const auto d_lines = s.out(lines, nfields);
+  const auto d_pfx = s.out(prefixes, nsections);
+  const auto d_mx = s.out(max_cnt, nsections);
+  const auto d_mn = s.out(min_cnt, nsections);
+  if ((rv = stage(c, s))) return rv;
+  const qh_plan_dyn dd = ks.on_device(s);
+  if ((rv = stage_in(c, s)) ||
+      (rv = plan_dyn_device(c, s(d_src), s(d_in), nullptr, nfields, never ? s(d_nv) : nullptr,
+                            s(d_fs), nsections, &dd, s(d_lines), nullptr, s(d_pfx), s(d_mx),
+                            s(d_mn))) ||
+      (rv = stage_out(c, s)))
     return rv;
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
@@ -587,27 +546,22 @@ QH_EXPORT int qh_encode_fields_dyn_batch(qh_ctx *c, const uint8_t *plain, const 
   for (size_t i = 0; i < nfields; ++i)
     extent = std::max(extent, std::max(fields[i].name_off + fields[i].name_len,
                                        fields[i].value_off + fields[i].value_len));
-  Staging s;
-  const size_t k_src = s.add(plain, nullptr, extent),
-               k_f = s.add(fields, nullptr, nfields * sizeof(qh_field)),
-               k_fs = s.add(field_start, nullptr, (nsections + 1) * 4);
-  const DynStaged ks = stage_dyn(s, dyn, nsections);
-  const size_t k_sec = s.add(nullptr, sections, nsections * 16),
-               k_mx = s.add(nullptr, max_cnt, nsections * 8),
-               k_mn = s.add(nullptr, min_cnt, nsections * 8);
-  void *din, *dout;
-  if ((rv = stage(c, 0, s.total, &din)) || (rv = stage(c, 2, dst_cap ? dst_cap : 16, &dout)))
-    return rv;
-  uint8_t *const d = (uint8_t *)din;
-  const qh_plan_dyn dd = staged_dyn(s, ks, d, dyn);
-  if ((rv = s.in(c, d))) return rv;
-  rv = encode_fields_dyn_device(c, s.at<const uint8_t>(d, k_src), s.at<const qh_field>(d, k_f),
-                                nfields, s.at<const uint32_t>(d, k_fs), nsections, &dd,
-                                (uint8_t *)dout, dst_cap, s.at<qh_span_in>(d, k_sec), &need,
-                                s.at<uint64_t>(d, k_mx), s.at<uint64_t>(d, k_mn));
+  static_assert(3 + DynStaged::kPieces + 3 <= qhs::kStagePieces, "qhs::Staged::piece");
+  uint8_t *dout;
+  qhs::Staged s;
+  const auto d_src = s.in(plain, extent);
+  const auto d_f = s.in(fields, nfields);
+  const auto d_fs = s.in(field_start, nsections + 1);
+  const DynStaged ks(s, dyn, nsections);
+  const auto d_sec = s.out(sections, nsections);
+  const auto d_mx = s.out(max_cnt, nsections);
+  const auto d_mn = s.out(min_cnt, nsections);
+  if ((rv = stage(c, s)) || (rv = stage_dst(c, dst_cap, &dout)) || (rv = stage_in(c, s))) return rv;
+  const qh_plan_dyn dd = ks.on_device(s);
+  rv = encode_fields_dyn_device(c, s(d_src), s(d_f), nfields, s(d_fs), nsections, &dd, dout,
+                                dst_cap, s(d_sec), &need, s(d_mx), s(d_mn));
   if (dst_need) *dst_need = need;
-  if (rv) return rv;
-  if ((rv = s.out(c, d))) return rv;
+  if (rv || (rv = stage_out(c, s))) return rv;
   if (need) QH_HIP(hipMemcpyAsync(dst, dout, need, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;

@@ -1,12 +1,14 @@
 // qh_scratch.h -- a context's scratch buffers: a pointer, a capacity in bytes,
-// grow-only reservation and release.  The allocator is a template parameter,
-// so tests/c/scratch_lifecycle.cc drives this code over malloc under a
-// sanitizer; qh_api.inc gives it HIP's.
+// grow-only reservation and release; and how a buffer is cut into typed
+// pieces (Layout) and a host call staged through one (Staged).  The allocator
+// and the copy are template parameters, so tests/c/scratch_lifecycle.cc drives
+// this code over malloc and memcpy under a sanitizer; qh_api.inc gives it HIP's.
 #ifndef QH_SCRATCH_H
 #define QH_SCRATCH_H
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace qhs {
 
@@ -66,6 +68,77 @@ void release(A &a, Scratch &s) {
   s.p = nullptr;
   s.cap = 0;
 }
+
+// The round-up of every piece of a buffer: 256 bytes.
+constexpr uint64_t align_up(uint64_t bytes) { return (bytes + 255) & ~(uint64_t)255; }
+
+// A buffer cut into typed pieces, each 256-byte aligned from the base.  A
+// caller writes its takes once, as a function of a Layout &, and runs it over
+// no base for `total` (what to reserve; every pointer null), then over the
+// buffer: the same code, so the two cannot disagree.  A piece of no elements
+// takes no room; a pad (a kernel's over-read) is a take<uint8_t> of its own.
+struct Layout {
+  uint8_t *base = nullptr;
+  uint64_t total = 0;
+  template <class T>
+  T *take(uint64_t count) {
+    T *const p = base ? reinterpret_cast<T *>(base + total) : nullptr;
+    total += align_up(count * sizeof(T));
+    return p;
+  }
+};
+
+// The most pieces with a host side that a call stages (qh_plan_fields_dyn_batch;
+// the two calls of qh_plan_dyn.inc that stage a table state assert theirs).
+constexpr int kStagePieces = 14;
+
+// A host-memory call's pieces in one device buffer.  Each take is a Layout's
+// over no base, kept as a typed offset: once the buffer of `sized.total` bytes
+// is reserved and `base` set, s(ref) is the piece.  A piece may have a host
+// source (copied in), a host destination (copied back), both or neither; a
+// null host pointer or no bytes is no copy.  The copy is the caller's: int
+// cp(void *to, const void *from, uint64_t bytes), 0 or an error, which ends it.
+struct Staged {
+  template <class T>
+  struct Ref {
+    uint64_t off = 0;
+  };
+  struct Piece {
+    const void *src;
+    void *back;
+    uint64_t off, bytes;
+  };
+  Layout sized;
+  uint8_t *base = nullptr;
+  Piece piece[kStagePieces];
+  int npieces = 0;
+  template <class T>
+  Ref<T> take(uint64_t count, const T *src = nullptr, T *back = nullptr) {
+    const Ref<T> r{sized.total};
+    sized.take<T>(count);
+    if (src || back) {
+      if (npieces == kStagePieces) abort();  // (a call with more pieces: raise kStagePieces)
+      piece[npieces++] = Piece{src, back, r.off, count * sizeof(T)};
+    }
+    return r;
+  }
+  template <class T>
+  Ref<T> in(const T *src, uint64_t count) { return take<T>(count, src); }
+  template <class T>
+  Ref<T> out(T *back, uint64_t count) { return take<T>(count, nullptr, back); }
+  template <class T>
+  T *operator()(Ref<T> r) const { return reinterpret_cast<T *>(base + r.off); }
+  template <class Copy>
+  int copy(bool back, Copy &&cp) const {
+    for (const Piece *p = piece; p < piece + npieces; ++p) {
+      if (!p->bytes || !(back ? p->back != nullptr : p->src != nullptr)) continue;
+      const int rv = back ? cp(p->back, (const void *)(base + p->off), p->bytes)
+                          : cp((void *)(base + p->off), p->src, p->bytes);
+      if (rv) return rv;
+    }
+    return 0;
+  }
+};
 
 }  // namespace qhs
 

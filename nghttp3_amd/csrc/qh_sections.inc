@@ -202,15 +202,15 @@ struct SecLayout {
   uint64_t cap = 0;
 };
 int sec_layout(qh_ctx *c, uint64_t cap, bool verdicts, SecLayout &L) {
-  const int rv = reserve(c, kBufSec,
-                         cap * (sizeof(qh_span_in) + sizeof(qh_span_out) + sizeof(uint64_t) + 1) + 512);
-  if (rv) return rv;
-  L.huff = mem<qh_span_in>(c, kBufSec);
-  L.hout = reinterpret_cast<qh_span_out *>(L.huff + cap);
-  L.aux = reinterpret_cast<uint64_t *>(L.hout + cap);
-  L.hverdict = verdicts ? reinterpret_cast<int8_t *>(L.aux + cap) : nullptr;
   L.cap = cap;
-  return 0;
+  return reserve_layout(c, kBufSec, [&](qhs::Layout &l) {
+    L.huff = l.take<qh_span_in>(cap);
+    L.hout = l.take<qh_span_out>(cap);
+    L.aux = l.take<uint64_t>(cap);
+    int8_t *const hv = l.take<int8_t>(cap);
+    L.hverdict = verdicts ? hv : nullptr;
+    l.take<uint8_t>(512);
+  });
 }
 
 void frame_targets(FrameOut &f, const qh_sections *s, const SecLayout &L, uint64_t spans_cap) {
@@ -254,11 +254,13 @@ int sections_finish(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, siz
   if (pk) {
     // [0]: carry in, [1]: carry out, the groups' decoded bytes, then the
     // slots (+16: dense_tile_copy loads 16 bytes at a short string's start)
-    const size_t st_b = ((2 + groups) * sizeof(uint64_t) + 255) & ~(size_t)255;
-    if ((rv = reserve(c, kBufDense, st_b + f.slots + 16))) return rv;
-    unsigned long long *state = mem<unsigned long long>(c, kBufDense);
-    btot = mem<uint64_t>(c, kBufDense) + 2;
-    dec_dst = mem<uint8_t>(c, kBufDense) + st_b;
+    unsigned long long *state;
+    rv = reserve_layout(c, kBufDense, [&](qhs::Layout &l) {
+      state = l.take<unsigned long long>(2 + groups);
+      dec_dst = l.take<uint8_t>(f.slots + 16);
+    });
+    if (rv) return rv;
+    btot = reinterpret_cast<uint64_t *>(state + 2);
     dec_cap = f.slots;
     if (!pk->carry_in) {
       QH_HIP(hipMemsetAsync(state, 0, sizeof(uint64_t), c->stream));
@@ -372,17 +374,16 @@ int sections_host(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, size_
   int rv = 0;
   const bool packed = (opts & QH_SECTIONS_PACKED) != 0;
   const uint64_t extent = src_extent(blocks, n);
-  const size_t in_b = (extent + 255) & ~(size_t)255, bl_b = (n * 16 + 255) & ~(size_t)255;
-  const size_t st_b = (n * 4 + 4 + 255) & ~(size_t)255;
-  const size_t pf_b = s->prefixes ? (n * sizeof(qh_section_prefix) + 255) & ~(size_t)255 : 0;
-  void *din;
-  if ((rv = stage(c, 0, in_b + bl_b + st_b + pf_b, &din))) return rv;
-  uint8_t *d_src = (uint8_t *)din;
-  qh_span_in *d_blk = (qh_span_in *)(d_src + in_b);
-  int32_t *d_st = (int32_t *)((uint8_t *)d_blk + bl_b);
-  qh_section_prefix *d_pf = s->prefixes ? (qh_section_prefix *)((uint8_t *)d_st + st_b) : nullptr;
-  if (extent) QH_HIP(hipMemcpyAsync(d_src, src, extent, hipMemcpyHostToDevice, c->stream));
-  if (n) QH_HIP(hipMemcpyAsync(d_blk, blocks, n * 16, hipMemcpyHostToDevice, c->stream));
+  qhs::Staged in;
+  const auto r_src = in.in(src, extent);
+  const auto r_blk = in.in(blocks, n);
+  const auto r_st = in.take<int32_t>(n + 1);
+  const auto r_pf = in.take<qh_section_prefix>(s->prefixes ? n : 0);
+  if ((rv = stage(c, in)) || (rv = stage_in(c, in))) return rv;
+  const uint8_t *const d_src = in(r_src);
+  const qh_span_in *const d_blk = in(r_blk);
+  int32_t *const d_st = in(r_st);
+  qh_section_prefix *const d_pf = s->prefixes ? in(r_pf) : nullptr;
   FrameOut f{nullptr, 0, nullptr, 0, nullptr, nullptr, d_st, nullptr, 0, nullptr, d_pf,
              {0, 0, 0}, 0};
   if ((rv = frame_count(c, d_src, d_blk, n, opts, f))) return rv;
@@ -396,32 +397,20 @@ int sections_host(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, size_
     return QH_ERR_NOMEM;
   if (s->nspans && !s->strs) return QH_ERR_INVALID_ARGUMENT;
   const size_t nl = f.tot[0], ns = f.tot[1];
-  size_t off[9], total = 0;
-  auto take = [&](int k, size_t b) {
-    off[k] = total;
-    total += (b + 255) & ~(size_t)255;
-  };
-  take(0, nl * sizeof(qh_field_line));
-  take(1, ns * sizeof(qh_span_in));
-  take(2, ns * sizeof(qh_span_out));
-  take(3, s->verdict ? ns : 0);
-  take(4, s->token ? ns * sizeof(int32_t) : 0);
-  take(5, (n + 1) * sizeof(uint32_t));
-  take(6, (n + 1) * sizeof(uint32_t));
-  take(7, f.slots);  // (packed: the decoded bytes are no more than their slots)
-  void *dout;
-  if ((rv = stage(c, 2, total + 256, &dout))) return rv;
-  uint8_t *d = (uint8_t *)dout;
   qh_sections ds = *s;
-  ds.lines = (qh_field_line *)(d + off[0]);
-  ds.spans = (qh_span_in *)(d + off[1]);
-  ds.strs = (qh_span_out *)(d + off[2]);
-  ds.verdict = s->verdict ? (int8_t *)(d + off[3]) : nullptr;
-  ds.token = s->token ? (int32_t *)(d + off[4]) : nullptr;
-  ds.line_start = (uint32_t *)(d + off[5]);
-  ds.span_start = (uint32_t *)(d + off[6]);
+  rv = reserve_layout(c, kBufStageDst, [&](qhs::Layout &l) {
+    ds.lines = l.take<qh_field_line>(nl);
+    ds.spans = l.take<qh_span_in>(ns);
+    ds.strs = l.take<qh_span_out>(ns);
+    ds.verdict = s->verdict ? l.take<int8_t>(ns) : nullptr;
+    ds.token = s->token ? l.take<int32_t>(ns) : nullptr;
+    ds.line_start = l.take<uint32_t>(n + 1);
+    ds.span_start = l.take<uint32_t>(n + 1);
+    ds.dst = l.take<uint8_t>(f.slots);  // (packed: the decoded bytes are no more than their slots)
+    l.take<uint8_t>(256);
+  }, qhs::kExact);
+  if (rv) return rv;
   ds.status = d_st;
-  ds.dst = d + off[7];
   ds.prefixes = d_pf;  // (written by the framing's count pass)
   ds.dst_cap = f.slots;
   ds.lines_cap = nl;
@@ -490,7 +479,7 @@ constexpr uint64_t kSecSliceMin = 4u << 20;  // block bytes
 
 struct SecSlice {
   uint64_t l0, s0, nl, ns;
-  const uint8_t *lines, *spans, *strs, *verdict, *token;
+  const void *lines, *spans, *strs, *verdict, *token;
 };
 
 int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, size_t n,
@@ -537,19 +526,24 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
     hi[k] = h;
     extent = h > extent ? h : extent;
   }
-  auto al = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-  const size_t in_b = al(extent), bl_b = al(n * 16), st_b = al(n * 4 + 4);
-  const size_t pf_b = s->prefixes ? al(n * sizeof(qh_section_prefix)) : 0;
-  void *din;
-  if ((rv = stage(c, 0, in_b + bl_b + 3 * st_b + pf_b + al((nsl + 1) * 8), &din))) return rv;
-  uint8_t *d_src = (uint8_t *)din;
-  qh_span_in *d_blk = (qh_span_in *)(d_src + in_b);
-  // per block, for the whole call (copied back once, after the last slice):
-  // status, line_start, span_start, prefixes
-  int32_t *d_st = (int32_t *)((uint8_t *)d_blk + bl_b);
-  uint32_t *d_ls = (uint32_t *)((uint8_t *)d_st + st_b), *d_ss = (uint32_t *)((uint8_t *)d_st + 2 * st_b);
-  qh_section_prefix *d_pf = s->prefixes ? (qh_section_prefix *)((uint8_t *)d_st + 3 * st_b) : nullptr;
-  unsigned long long *d_carry = (unsigned long long *)((uint8_t *)d_st + 3 * st_b + pf_b);  // [0..nsl]
+  uint8_t *d_src;
+  qh_span_in *d_blk;
+  int32_t *d_st;
+  uint32_t *d_ls, *d_ss;
+  qh_section_prefix *d_pf;
+  unsigned long long *d_carry;  // [0..nsl]
+  rv = reserve_layout(c, kBufStage, [&](qhs::Layout &l) {
+    d_src = l.take<uint8_t>(extent);
+    d_blk = l.take<qh_span_in>(n);
+    // per block, for the whole call (copied back once, after the last slice):
+    // status, line_start, span_start, prefixes
+    d_st = l.take<int32_t>(n + 1);
+    d_ls = l.take<uint32_t>(n + 1);
+    d_ss = l.take<uint32_t>(n + 1);
+    d_pf = s->prefixes ? l.take<qh_section_prefix>(n) : nullptr;
+    d_carry = l.take<unsigned long long>(nsl + 1);
+  }, qhs::kExact);
+  if (rv) return rv;
   const uint64_t dcap = std::min<uint64_t>(s->dst_cap, block_bytes * 8 / 5);
   if ((rv = reserve(c, kBufSliceDense, dcap + 16))) return rv;
   if ((rv = reserve(c, kBufSlice, std::max<uint64_t>(c->sp_hint, 1u << 20)))) return rv;
@@ -649,16 +643,17 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
       break;
     }
     // the slice's staging
-    uint64_t off[5], need = 0;
-    auto take = [&](int j, uint64_t b) {
-      off[j] = need;
-      need += al(b);
+    qh_sections ds = *s;
+    auto slice_lay = [&](qhs::Layout &l) {
+      ds.lines = l.take<qh_field_line>(nl);
+      ds.spans = l.take<qh_span_in>(ns);
+      ds.strs = l.take<qh_span_out>(ns);
+      ds.verdict = s->verdict ? l.take<int8_t>(ns) : nullptr;
+      ds.token = s->token ? l.take<int32_t>(ns) : nullptr;
     };
-    take(0, nl * sizeof(qh_field_line));
-    take(1, ns * sizeof(qh_span_in));
-    take(2, ns * sizeof(qh_span_out));
-    take(3, s->verdict ? ns : 0);
-    take(4, s->token ? ns * sizeof(int32_t) : 0);
+    qhs::Layout sized;
+    slice_lay(sized);
+    const uint64_t need = sized.total;
     arena_all += need;
     if (arena + need > c->buf[kBufSlice].cap) {
       // wait until the earlier slices' copies out of the arena are done
@@ -674,14 +669,10 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
       if ((rv = reserve(c, kBufSlice, need))) break;
       arena = 0;
     }
-    uint8_t *d = mem<uint8_t>(c, kBufSlice) + arena;
+    qhs::Layout placed;
+    placed.base = mem<uint8_t>(c, kBufSlice) + arena;
+    slice_lay(placed);
     arena += need;
-    qh_sections ds = *s;
-    ds.lines = (qh_field_line *)(d + off[0]);
-    ds.spans = (qh_span_in *)(d + off[1]);
-    ds.strs = (qh_span_out *)(d + off[2]);
-    ds.verdict = s->verdict ? (int8_t *)(d + off[3]) : nullptr;
-    ds.token = s->token ? (int32_t *)(d + off[4]) : nullptr;
     // (the write pass also sets entry [nb]: the next slice's first entry,
     // which that slice writes again, or the call's last, set on the host)
     ds.line_start = d_ls + i0;
@@ -709,7 +700,7 @@ int sections_host_sliced_impl(qh_ctx *c, const uint8_t *src, const qh_span_in *b
       rv = QH_ERR_FATAL;
       break;
     }
-    sl[k] = SecSlice{l0, s0, nl, ns, d + off[0], d + off[1], d + off[2], d + off[3], d + off[4]};
+    sl[k] = SecSlice{l0, s0, nl, ns, ds.lines, ds.spans, ds.strs, ds.verdict, ds.token};
     {
       std::lock_guard<std::mutex> g(mu);
       queued = k + 1;

@@ -52,15 +52,13 @@ QH_EXPORT int qh_check_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span
   if (where != QH_WHERE_HOST) return QH_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
   const uint64_t extent = src_extent(in, n);
-  void *d_src, *d_in, *d_v;
-  if ((rv = stage(c, 0, extent, &d_src)) || (rv = stage(c, 1, n * 16, &d_in)) ||
-      (rv = stage(c, 3, n, &d_v)))
+  qhs::Staged s;
+  const auto d_src = s.in(src, extent);
+  const auto d_in = s.in((const SpanIn *)in, n);
+  const auto d_v = s.out(verdict, n);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s)) ||
+      (rv = check_fields_device(c, s(d_src), s(d_in), n, s(d_v))) || (rv = stage_out(c, s)))
     return rv;
-  QH_HIP(hipMemcpyAsync(d_src, src, extent, hipMemcpyHostToDevice, c->stream));
-  QH_HIP(hipMemcpyAsync(d_in, in, n * 16, hipMemcpyHostToDevice, c->stream));
-  rv = check_fields_device(c, (const uint8_t *)d_src, (const SpanIn *)d_in, n, (int8_t *)d_v);
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(verdict, d_v, n, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -126,15 +124,13 @@ QH_EXPORT int qh_lookup_tokens_batch(qh_ctx *c, const uint8_t *src, const qh_spa
   if (where != QH_WHERE_HOST) return QH_ERR_INVALID_ARGUMENT;
   if (n == 0) return 0;
   const uint64_t extent = src_extent(in, n);
-  void *d_src, *d_in, *d_t;
-  if ((rv = stage(c, 0, extent, &d_src)) || (rv = stage(c, 1, n * 16, &d_in)) ||
-      (rv = stage(c, 3, n * 4, &d_t)))
+  qhs::Staged s;
+  const auto d_src = s.in(src, extent);
+  const auto d_in = s.in((const SpanIn *)in, n);
+  const auto d_t = s.out(token, n);
+  if ((rv = stage(c, s)) || (rv = stage_in(c, s)) ||
+      (rv = lookup_tokens_device(c, s(d_src), s(d_in), n, s(d_t))) || (rv = stage_out(c, s)))
     return rv;
-  QH_HIP(hipMemcpyAsync(d_src, src, extent, hipMemcpyHostToDevice, c->stream));
-  QH_HIP(hipMemcpyAsync(d_in, in, n * 16, hipMemcpyHostToDevice, c->stream));
-  rv = lookup_tokens_device(c, (const uint8_t *)d_src, (const SpanIn *)d_in, n, (int32_t *)d_t);
-  if (rv) return rv;
-  QH_HIP(hipMemcpyAsync(token, d_t, n * 4, hipMemcpyDeviceToHost, c->stream));
   QH_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

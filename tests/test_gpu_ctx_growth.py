@@ -226,3 +226,56 @@ def test_contexts_give_their_memory_back(batches, sections):
     after = torch.cuda.mem_get_info()[0]
     print("free device memory before %d after %d: moved %d bytes" % (before, after, before - after))
     assert before - after <= LEAK_MARGIN
+
+
+# Every host-memory call stages through one arena of exactly the size asked
+# (kBufStage, qh_api.inc) and one dst buffer: a call with a larger total than
+# all before it reallocates them, a smaller one after it runs in the big one.
+STAGED = (1, 300, 1)
+
+
+def _staged_case(batches, n):
+    """n fields (their 2 n strings) in sections of up to three, n strings to
+    encode, and what the host twins and the oracle make of them."""
+    import plan_cases as pc
+    from test_gpu_plan import fields_of, want_sections
+    fields = pc.batch(n, start=n)
+    never = pc.never_flags(fields, True)
+    plain, strs = pc.pack(fields)
+    fs = pc.field_start([3] * (n // 3) + ([n % 3] if n % 3 else []))
+    chk = strs.copy()
+    chk["flags"][0::2] = qpack.SPAN_NAME
+    text = [plain[int(s["off"]):int(s["off"] + s["len"])].tobytes() for s in strs]
+    b = batches[n]
+    sp = np.zeros(n, dtype=SPAN_IN_DTYPE)
+    sp["off"], sp["len"] = b["off"], b["ln"]
+    return {"plain": plain, "strs": strs, "never": never, "fs": fs, "fields": fields_of(strs, never),
+            "lines": qpack.plan_fields(plain, strs, never).tobytes(),
+            "sections": want_sections(plain, strs, never, fs),
+            "chk": chk, "names": np.ascontiguousarray(strs[0::2]),
+            "verdict": np.array([qpack.check_header_value(x) if i % 2 else qpack.check_header_name(x)
+                                 for i, x in enumerate(text)], dtype=np.int8),
+            "token": np.array([qpack.lookup_token(x) for x in text[0::2]], dtype=np.int32),
+            "b": b, "sp": sp}
+
+
+def test_host_calls_share_one_staging_arena(batches):
+    cases = {n: _staged_case(batches, n) for n in sorted(set(STAGED))}
+    codec = HuffmanBatchCodec(0)
+    try:
+        enc = qpack.FieldSectionEncoder(codec=codec)
+        for n in STAGED:
+            k = cases[n]
+            b = k["b"]
+            assert qpack.plan_fields_host(codec, k["plain"], k["strs"], k["never"]).tobytes() == k["lines"]
+            dst, sec = enc.encode_fields(k["plain"], k["fields"], k["fs"])
+            assert dst.tobytes() == k["sections"][0].tobytes() and sec.tobytes() == k["sections"][1].tobytes()
+            assert np.array_equal(codec.encode_count_host(b["plain"], k["sp"])[:n], b["elen"].astype(np.uint32))
+            e, out = codec.encode_host(b["plain"], k["sp"])
+            assert (out["status"] == 0).all() and np.array_equal(out["len"], b["elen"].astype(np.uint32))
+            assert np.array_equal(out["off"].astype(np.uint64), b["eoff"].astype(np.uint64))
+            assert np.array_equal(e[:b["enc"].size], b["enc"])
+            assert np.array_equal(qpack.check_fields_host(codec, k["plain"], k["chk"])[:2 * n], k["verdict"])
+            assert np.array_equal(qpack.lookup_tokens_host(codec, k["plain"], k["names"])[:n], k["token"])
+    finally:
+        codec.close()

@@ -1,5 +1,6 @@
-"""The context's scratch-buffer type (nghttp3_amd/csrc/qh_scratch.h: reserve /
-release, the code qh_api.inc runs over hipMalloc) driven over malloc by a
+"""The context's scratch-buffer types (nghttp3_amd/csrc/qh_scratch.h: reserve /
+release, the code qh_api.inc runs over hipMalloc; the layout and staging
+types every batch entry point cuts its buffers with) driven over malloc by a
 stand-alone program built with AddressSanitizer and UBSan
 (tests/c/scratch_lifecycle.cc).  CPU only."""
 import os
@@ -16,4 +17,4 @@ def test_scratch_lifecycle_under_sanitizers(tmp_path):
                            os.path.join(ROOT, "tests", "c", "scratch_lifecycle.cc"), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "scratch lifecycle ok: 4 policies" in out.stdout
+    assert "scratch lifecycle ok: 4 policies, 8 layouts, staging" in out.stdout
