@@ -727,9 +727,10 @@ QH_EXPORT const uint8_t *qh_dtable_bytes(const qh_dtable *dt, size_t *n);
  * Growth: a call appends, per moving table, 32 (L + inserts) bytes of records
  * and the new strings' bytes; the records of the regions left behind stay.
  * A table of capacity C holds at most C / 32 live records, so relocation
- * costs at most C bytes per touched table per call.  Compacting the log
- * (copying the live regions to a fresh log, views rebased) is the caller's
- * and not done here.
+ * costs at most C bytes per touched table per call.  The regions left behind
+ * are given back by compacting the log (qh_qpack_dtables_compact /
+ * qh_dtables_compact_batch below: the live records copied to a fresh log,
+ * views rebased); when to do so is the caller's decision.
  *
  * Returns 0; QH_ERR_INVALID_ARGUMENT (a table index >= ntables, a table
  * listed twice in tsel: nothing is written); QH_ERR_NOMEM when entries_cap
@@ -773,6 +774,73 @@ QH_EXPORT int qh_dtables_apply_batch(
     size_t ntables, qh_dtable_view *views, qh_dtable_acct *acct, qh_dyn_entry *entries,
     uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes,
     uint64_t bytes_cap, int32_t *status, uint32_t *consumed, int where);
+
+/* Compaction of the shared log: the live records of the listed views copied
+ * to a fresh log (entries_out, bytes_out: caller-owned, not overlapping the
+ * source arrays), the views rewritten in place to point into it.  `views` is
+ * any list of views into the source log: normally the set's views array; a
+ * caller that still needs an older snapshot of a table (a view copied for a
+ * blocked section) appends it.  Every listed view gets its own region, so a
+ * snapshot costs a second copy of the records it shares with the current
+ * view (overlapping views are not merged).  acct is not an argument: nothing
+ * in it changes.  No policy is built in: the caller compares *nentries and
+ * *nbytes of its log with what its tables can hold and decides when to call.
+ *
+ * Layout rule of the compacted log (the host function and the kernels follow
+ * it, so their outputs are byte for byte equal).  Views are taken in list
+ * order.  View t has L_t = insert_count - live_lo live records; they go to
+ * entries_out[E_t, E_t + L_t) in absolute-index order, E_t the sum of L_u
+ * over u < t, and its ent_base becomes E_t - live_lo (an empty view's too);
+ * live_lo, insert_count, max_entries and reserved are unchanged.  Bytes are
+ * unshared: output record r (counted over the whole list, views in order,
+ * records in order) owns bytes_out[B_r, B_r + name_len + value_len), B_r the
+ * sum of name_len + value_len over the records before it; name_off = B_r,
+ * value_off = B_r + name_len (empty strings too); name_len, value_len, token
+ * and reserved are copied.  A duplicate or a dynamic name reference, which
+ * shared bytes with an older entry in the source log, gets its own copy.
+ * So *nbytes_out is the sum over the views of size_t - 32 L_t (size_t: the
+ * table's accounted size), and a compacted log of current views is never
+ * larger than the sum of the tables' capacities; no dedupe pass is needed;
+ * and the result does not depend on which entries happened to share bytes.
+ * The source arrays are only read: a view copied before the call stays valid
+ * against the old arrays, which the caller frees when it no longer needs
+ * them.
+ *
+ * Returns 0 with the views rewritten and *nentries_out / *nbytes_out the
+ * compacted log's lengths (nviews == 0 or every view empty: 0 and 0; null
+ * outputs are allowed then).  QH_ERR_NOMEM when entries_out_cap or
+ * bytes_out_cap is too small: *nentries_out and *nbytes_out are the exact
+ * needs, views and outputs are untouched (caps of 0 with null outputs is the
+ * sizing call).  QH_ERR_INVALID_ARGUMENT with nothing written to views,
+ * outputs or the two counts when a view fails against nentries (its live
+ * range leaves the log) or a live record's strings leave [0, nbytes) (or its
+ * two lengths sum to 2^32 or more, which no apply writes): status[t] is then
+ * QH_ERR_INVALID_ARGUMENT for each offending view and 0 for the others
+ * (status may be written on the error paths).  QH_ERR_INVALID_ARGUMENT also
+ * when the output arrays overlap the source arrays, a pointer is null where
+ * its count is not 0, or nviews is above 2^27 - 1 (the apply's grid limit).
+ * Nothing is read outside [0, nentries) or [0, nbytes), nothing is written at
+ * or past *nentries_out or *nbytes_out. */
+QH_EXPORT int qh_qpack_dtables_compact(
+    size_t nviews, qh_dtable_view *views, const qh_dyn_entry *entries, uint64_t nentries,
+    const uint8_t *bytes, uint64_t nbytes, qh_dyn_entry *entries_out, uint64_t *nentries_out,
+    uint64_t entries_out_cap, uint8_t *bytes_out, uint64_t *nbytes_out, uint64_t bytes_out_cap,
+    int32_t *status);
+
+/* The same over arrays in HBM (where must be QH_WHERE_DEVICE; nentries_out and
+ * nbytes_out are host scalars; at most 2^32 - 1 output records).  The work is
+ * flat over output records, not a lane per table.  Asynchronous on the context
+ * stream after one host wait, which reads the record total, the byte total
+ * and the error flags before anything is written to the outputs or the views.
+ * The per-record pass is sized from the context's previous call plus an
+ * eighth; the first call, and one with more output records than that, waits
+ * twice.  Scratch (16 bytes per view and per output record) comes from the
+ * context. */
+QH_EXPORT int qh_dtables_compact_batch(
+    qh_ctx *ctx, size_t nviews, qh_dtable_view *views, const qh_dyn_entry *entries,
+    uint64_t nentries, const uint8_t *bytes, uint64_t nbytes, qh_dyn_entry *entries_out,
+    uint64_t *nentries_out, uint64_t entries_out_cap, uint8_t *bytes_out, uint64_t *nbytes_out,
+    uint64_t bytes_out_cap, int32_t *status, int where);
 
 /* Where a field's name / value bytes are. */
 #define QH_IN_SRC 0    /* raw string in the block bytes (off into src)     */

@@ -170,6 +170,8 @@ EXPORTED_FUNCTIONS = (
     "qh_dtable_state_init",
     "qh_qpack_dtables_apply",
     "qh_dtables_apply_batch",
+    "qh_qpack_dtables_compact",
+    "qh_dtables_compact_batch",
     # field representations on the GPU (csrc/qh_plan.inc)
     "qh_plan_fields_batch",
     "qh_encode_fields_batch",

@@ -37,6 +37,8 @@ enum BufId {
   kBufPlan,         // qh_encode_fields_batch: the planned fields' spans and lines
   kBufDtset,        // qh_dtables_apply_batch: per-stream counts, sizes and verdicts
   kBufDtsetWork,    // ... instructions, spans, the Huffman strings' spans, results and slots
+  kBufDtc,          // qh_dtables_compact_batch: per-view record counts, the first scan's header
+  kBufDtcWork,      // ... per-output-record byte counts, the second scan's header
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap
@@ -47,6 +49,7 @@ enum BufId {
   kBufEncSecHost,  // the sections encoder's totals read back (8 words)
   kBufEmitHost,    // field emission's totals read back (8 words)
   kBufDtsetHost,   // the table set's totals read back (8 words)
+  kBufDtcHost,     // compaction's totals read back (16 words)
   kNumBuf
 };
 
@@ -125,6 +128,9 @@ struct qh_ctx {
   // work buffer is laid out from them before its own totals are known)
   uint64_t dt_hint[4] = {0, 0, 0, 0};
   uint64_t dt_hint_nsel = 0;
+  // the output records of the last qh_dtables_compact_batch call (the next
+  // call's per-record pass is sized from it before its own total is known)
+  uint64_t dtc_hint = 0;
   // fused encoder (qh_enc_fused.inc): the halves of kBufEw are used by
   // alternate calls
   int ew_par = 0;

@@ -19,6 +19,9 @@
  *              caller stores the record of every applied insert at
  *              neu[nnew - 1] before the next step.
  * See include/qhuff.h (qh_qpack_dtables_apply) for the layout rule.
+ *
+ * Compaction of the log (qh_qpack_dtables_compact) shares its checks and the
+ * forming of a compacted record and a rebased view in the same way.
  */
 #ifndef QH_DTABLE_CORE_H
 #define QH_DTABLE_CORE_H
@@ -76,6 +79,70 @@ QH_HD static inline int qh_dt_view_check(const qh_dtable_view *v, uint64_t nentr
     return -1;
   }
   return lo <= hi && hi <= nentries ? 0 : -1;
+}
+
+/* ---- compaction (qh_qpack_dtables_compact / qh_dtables_compact_batch) ---- */
+
+/* A live record against the byte log it points into: 0 when both strings lie
+ * inside [0, nbytes) and the two lengths sum to less than 2^32 (an entry the
+ * apply functions can have written; the sum is one scan item on the device). */
+QH_HD static inline int qh_dt_rec_check(const qh_dyn_entry *e, uint64_t nbytes) {
+  if (e->name_off > nbytes || e->name_len > nbytes - e->name_off) {
+    return -1;
+  }
+  if (e->value_off > nbytes || e->value_len > nbytes - e->value_off) {
+    return -1;
+  }
+  return (uint64_t)e->name_len + e->value_len > 0xFFFFFFFFull ? -1 : 0;
+}
+
+/* The record as the compacted log holds it: its strings back to back at byte
+ * `at` (the bytes of the output records before it), the rest copied. */
+QH_HD static inline qh_dyn_entry qh_dt_rec_compact(const qh_dyn_entry *e, uint64_t at) {
+  qh_dyn_entry n = *e;
+  n.name_off = at;
+  n.value_off = at + e->name_len;
+  return n;
+}
+
+/* The view over the compacted log: its live records start at record `at`. */
+QH_HD static inline qh_dtable_view qh_dt_view_compact(const qh_dtable_view *v, uint64_t at) {
+  qh_dtable_view n = *v;
+  n.ent_base = (int64_t)(at - v->live_lo); /* (mod 2^64: may be negative) */
+  return n;
+}
+
+/* [a, a + na) and [b, b + nb) share a byte. */
+QH_HD static inline int qh_dt_overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
+  const uint64_t x = (uint64_t)(uintptr_t)a, y = (uint64_t)(uintptr_t)b;
+  return na && nb && x < y + nb && y < x + na;
+}
+
+#define QH_DTC_MAX_VIEWS 0x7ffffffull /* the lane-per-item grid limit of the apply */
+
+/* The arguments both compaction entry points refuse before anything is read. */
+QH_HD static inline int qh_dtc_args_check(size_t nviews, const qh_dtable_view *views,
+                                          const qh_dyn_entry *entries, uint64_t nentries,
+                                          const uint8_t *bytes, uint64_t nbytes,
+                                          const qh_dyn_entry *entries_out, const uint64_t *nentries_out,
+                                          uint64_t entries_out_cap, const uint8_t *bytes_out,
+                                          const uint64_t *nbytes_out, uint64_t bytes_out_cap,
+                                          const int32_t *status) {
+  const uint64_t es = sizeof(qh_dyn_entry);
+  if (!nentries_out || !nbytes_out || (nviews && (!views || !status)) || (!entries && nentries) ||
+      (!bytes && nbytes) || (!entries_out && entries_out_cap) || (!bytes_out && bytes_out_cap)) {
+    return -1;
+  }
+  if (nviews > QH_DTC_MAX_VIEWS || nentries > (1ull << 58) || entries_out_cap > (1ull << 58)) {
+    return -1;
+  }
+  if (qh_dt_overlap(entries_out, entries_out_cap * es, entries, nentries * es) ||
+      qh_dt_overlap(entries_out, entries_out_cap * es, bytes, nbytes) ||
+      qh_dt_overlap(bytes_out, bytes_out_cap, entries, nentries * es) ||
+      qh_dt_overlap(bytes_out, bytes_out_cap, bytes, nbytes)) {
+    return -1;
+  }
+  return 0;
 }
 
 QH_HD static inline void qh_dt_lens(const qh_dt_walk *w, uint64_t a, uint32_t *nl, uint32_t *vl) {

@@ -10,6 +10,10 @@
  * its Huffman strings with the scalar drop-in and walks its table in
  * size-only mode (verdicts, consumed bytes, the records and bytes each table
  * appends); pass 1, once the caps hold, walks again and writes.
+ *
+ * qh_qpack_dtables_compact, at the end, copies the live records of a list of
+ * views to a fresh log (the header's second layout rule), again in two
+ * passes over the QH_HD functions the kernels compile.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -285,4 +289,72 @@ QH_EXPORT int qh_qpack_dtables_apply(const uint8_t *src, const qh_span_in *strea
 out:
   dts_free(st, nsel);
   return rv;
+}
+
+/* Compaction: two passes.  Pass 0 checks every view and every live record and
+ * sizes the result; pass 1, once the caps hold, writes the records, their
+ * bytes and the views.  The layout rule is the header's. */
+QH_EXPORT int qh_qpack_dtables_compact(size_t nviews, qh_dtable_view *views,
+                                       const qh_dyn_entry *entries, uint64_t nentries,
+                                       const uint8_t *bytes, uint64_t nbytes,
+                                       qh_dyn_entry *entries_out, uint64_t *nentries_out,
+                                       uint64_t entries_out_cap, uint8_t *bytes_out,
+                                       uint64_t *nbytes_out, uint64_t bytes_out_cap,
+                                       int32_t *status) {
+  uint64_t ent_at = 0, byte_at = 0, a;
+  size_t t;
+  int bad = 0;
+
+  if (qh_dtc_args_check(nviews, views, entries, nentries, bytes, nbytes, entries_out, nentries_out,
+                        entries_out_cap, bytes_out, nbytes_out, bytes_out_cap, status) != 0) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  /* pass 0: check and size */
+  for (t = 0; t < nviews; ++t) {
+    const qh_dtable_view *v = &views[t];
+    status[t] = 0;
+    if (qh_dt_view_check(v, nentries) != 0) {
+      status[t] = QH_ERR_INVALID_ARGUMENT;
+      bad = 1;
+      continue;
+    }
+    for (a = v->live_lo; a < v->insert_count; ++a) {
+      const qh_dyn_entry *e = &entries[(uint64_t)v->ent_base + a];
+      if (qh_dt_rec_check(e, nbytes) != 0) {
+        status[t] = QH_ERR_INVALID_ARGUMENT;
+        bad = 1;
+        continue;
+      }
+      byte_at += (uint64_t)e->name_len + e->value_len;
+    }
+    ent_at += v->insert_count - v->live_lo;
+  }
+  if (bad) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  *nentries_out = ent_at;
+  *nbytes_out = byte_at;
+  if (ent_at > entries_out_cap || byte_at > bytes_out_cap) {
+    return QH_ERR_NOMEM;
+  }
+  /* pass 1: write */
+  ent_at = byte_at = 0;
+  for (t = 0; t < nviews; ++t) {
+    const qh_dtable_view v = views[t];
+    for (a = v.live_lo; a < v.insert_count; ++a) {
+      const qh_dyn_entry *e = &entries[(uint64_t)v.ent_base + a];
+      const qh_dyn_entry n = qh_dt_rec_compact(e, byte_at);
+      if (e->name_len) {
+        memcpy(bytes_out + n.name_off, bytes + e->name_off, e->name_len);
+      }
+      if (e->value_len) {
+        memcpy(bytes_out + n.value_off, bytes + e->value_off, e->value_len);
+      }
+      entries_out[ent_at + (a - v.live_lo)] = n;
+      byte_at += (uint64_t)e->name_len + e->value_len;
+    }
+    views[t] = qh_dt_view_compact(&v, ent_at);
+    ent_at += v.insert_count - v.live_lo;
+  }
+  return 0;
 }

@@ -31,6 +31,8 @@
 //           writes the record) with the whole group copying each insert's
 //           name and value bytes; lane 0 writes the new view and acct.
 // No atomics in the apply: regions are disjoint and fixed by the scans.
+//
+// Compaction of that log (qh_dtables_compact_batch) is at the end of this file.
 
 #include "qh_dtable_core.h"
 
@@ -492,6 +494,215 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
                        (const qhk::SpanIn *)W.spans, (const uint64_t *)W.aux,
                        (const qhk::SpanOut *)W.hout, (const uint8_t *)W.slots, W.lens,
                        (const qhk::SpanOut *)cnt2, (const qhk::DtRes *)res, status, consumed);
+    QH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Compaction (include/qhuff.h qh_dtables_compact_batch): the live records of
+// every listed view copied to a fresh log, bytes unshared, views rebased; the
+// device twin of qh_qpack_dtables_compact.  The work is flat over output
+// records, so 64 tables of 2,048 entries fill the chip like 65,536 of 2.
+//
+//   views    qh_k_dtc_views, a lane per view: qh_dt_view_check, its live
+//            count L_t, status[t], the error flag;
+//   scan     qh_k_scan_seg over L: E_t and the record total R;
+//   records  qh_k_dtc_records, a lane per output record: its view by a binary
+//            search in E, the source record bounds-checked (on failure the
+//            error flag and its view's status), name_len + value_len;
+//   scan     qh_k_scan_seg over the lengths: B_r and the byte total;
+//   (sync)   one: both totals, both error flags, the scans' time-out words;
+//   write    qh_k_dtc_write, 16 lanes per output record: the two strings by
+//            dts_group_copy, the record by lane 0;
+//   rebase   qh_k_dtc_rebase, a lane per view: ent_base = E_t - live_lo (its
+//            own launch: the write kernel reads the views it replaces).
+// No atomics in the write: regions are disjoint and fixed by the scans.
+
+namespace qhk {
+
+__global__ void __launch_bounds__(256) qh_k_dtc_views(
+    const qh_dtable_view *__restrict__ views, uint64_t nviews, uint64_t nentries,
+    SpanOut *__restrict__ vcnt, int32_t *__restrict__ status, uint64_t *__restrict__ hdr) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nviews) return;
+  const qh_dtable_view v = views[t];
+  bool ok = qh_dt_view_check(&v, nentries) == 0;
+  uint64_t L = ok ? v.insert_count - v.live_lo : 0;
+  if (L > 0xFFFFFFFFull) {  // (one scan item; nentries is checked on the host)
+    ok = false;
+    L = 0;
+  }
+  vcnt[t].len = (uint32_t)L;
+  status[t] = ok ? 0 : QH_ERR_INVALID_ARGUMENT;
+  if (!ok) atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
+}
+
+// After the first scan: vcnt[t].off = E_t, hdr_a[kDtTot] = R.  Lanes r in
+// [R, cap) zero their scan item (cap: the room of rcnt, laid out before R was
+// known on the host).  rcnt[r].status = the record's view.
+__global__ void __launch_bounds__(256) qh_k_dtc_records(
+    const qh_dtable_view *__restrict__ views, uint64_t nviews,
+    const qh_dyn_entry *__restrict__ entries, uint64_t nbytes, const SpanOut *__restrict__ vcnt,
+    const uint64_t *__restrict__ hdr_a, SpanOut *__restrict__ rcnt, uint64_t cap,
+    int32_t *__restrict__ status, uint64_t *__restrict__ hdr_b) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= cap) return;
+  if (r >= hdr_a[kDtTot]) {
+    rcnt[r].len = 0;
+    return;
+  }
+  // the last view whose E is <= r: the views before it with the same E are empty
+  uint64_t lo = 0, hi = nviews;  // (E[lo] <= r < E[hi], E[nviews] = R)
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (vcnt[mid].off <= r) lo = mid;
+    else hi = mid;
+  }
+  const qh_dtable_view v = views[lo];
+  const qh_dyn_entry e = entries[(uint64_t)v.ent_base + v.live_lo + (r - vcnt[lo].off)];
+  uint32_t n = e.name_len + e.value_len;
+  if (qh_dt_rec_check(&e, nbytes) != 0) {
+    n = 0;
+    status[lo] = QH_ERR_INVALID_ARGUMENT;  // (every lane that stores here stores the same)
+    atomicExch(reinterpret_cast<unsigned long long *>(hdr_b + kDtErr), 1ull);
+  }
+  rcnt[r].len = n;
+  rcnt[r].status = (int32_t)lo;
+}
+
+// After the second scan: rcnt[r].off = B_r.  (4 waves per SIMD and more: a
+// group's work is two loads of the record, its strings' pieces and a store)
+__global__ void __launch_bounds__(256) qh_k_dtc_write(
+    const qh_dtable_view *__restrict__ views, const qh_dyn_entry *__restrict__ entries,
+    const uint8_t *__restrict__ bytes, const SpanOut *__restrict__ vcnt,
+    const SpanOut *__restrict__ rcnt, uint64_t nrec, qh_dyn_entry *__restrict__ entries_out,
+    uint8_t *__restrict__ bytes_out) {
+  const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kDtLanes;
+  const uint32_t sl = threadIdx.x % kDtLanes;
+  if (r >= nrec) return;  // (whole 16-lane groups)
+  const SpanOut rc = rcnt[r];
+  const uint32_t t = (uint32_t)rc.status;
+  const qh_dtable_view v = views[t];
+  const qh_dyn_entry e = entries[(uint64_t)v.ent_base + v.live_lo + (r - vcnt[t].off)];
+  const qh_dyn_entry n = qh_dt_rec_compact(&e, rc.off);
+  dts_group_copy(bytes_out + n.name_off, bytes + e.name_off, e.name_len, sl);
+  dts_group_copy(bytes_out + n.value_off, bytes + e.value_off, e.value_len, sl);
+  if (sl == 0) entries_out[r] = n;
+}
+
+__global__ void __launch_bounds__(256) qh_k_dtc_rebase(qh_dtable_view *__restrict__ views,
+                                                       uint64_t nviews,
+                                                       const SpanOut *__restrict__ vcnt) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nviews) return;
+  const qh_dtable_view v = views[t];
+  views[t] = qh_dt_view_compact(&v, vcnt[t].off);
+}
+
+}  // namespace qhk
+
+// Host waits: one, in the steady state.  The record total is only known on
+// the device when the per-record pass has to be sized, so that pass and its
+// scan are queued over room for the last call's total plus an eighth
+// (qh_ctx::dtc_hint), and the one wait reads both totals.  The first call, and
+// a call with more output records than that room, waits for the record total
+// and queues the pass (again) for exactly it: two waits.  The sizing call and
+// the real call of a caller make such a pair: the second finds the hint.
+QH_EXPORT int qh_dtables_compact_batch(qh_ctx *c, size_t nviews, qh_dtable_view *views,
+                                       const qh_dyn_entry *entries, uint64_t nentries,
+                                       const uint8_t *bytes, uint64_t nbytes,
+                                       qh_dyn_entry *entries_out, uint64_t *nentries_out,
+                                       uint64_t entries_out_cap, uint8_t *bytes_out,
+                                       uint64_t *nbytes_out, uint64_t bytes_out_cap,
+                                       int32_t *status, int where) {
+  int rv = check_ctx(c);
+  if (rv) return rv;
+  if (where != QH_WHERE_DEVICE ||
+      qh_dtc_args_check(nviews, views, entries, nentries, bytes, nbytes, entries_out, nentries_out,
+                        entries_out_cap, bytes_out, nbytes_out, bytes_out_cap, status) != 0)
+    return QH_ERR_INVALID_ARGUMENT;
+  if (nviews == 0) {
+    *nentries_out = *nbytes_out = 0;
+    return 0;
+  }
+  const uint64_t tps_v = (nviews + qhk::kScanTile - 1) / qhk::kScanTile;
+  qhk::SpanOut *vcnt, *rcnt = nullptr;
+  uint64_t *hdr_a, *hdr_b = nullptr;
+  rv = reserve_layout(c, kBufDtc, [&](qhs::Layout &l) {
+    vcnt = l.take<qhk::SpanOut>(nviews);
+    hdr_a = l.take<uint64_t>(qhk::kDtHdr + tps_v);
+  });
+  if (rv) return rv;
+  if ((rv = reserve(c, kBufDtcHost, 16 * sizeof(uint64_t), qhs::kExact))) return rv;
+  uint64_t *h = mem<uint64_t>(c, kBufDtcHost);  // [0, 7): the first scan's words 1-7, [8, 15): the second's
+  memset(h, 0, 16 * sizeof(uint64_t));
+  // the per-record pass and its scan over room for `cap` records
+  uint64_t cap = 0;
+  auto records = [&](uint64_t room) -> int {
+    cap = room;
+    const uint64_t tps_r = (cap + qhk::kScanTile - 1) / qhk::kScanTile;
+    const int r = reserve_layout(c, kBufDtcWork, [&](qhs::Layout &l) {
+      rcnt = l.take<qhk::SpanOut>(cap);
+      hdr_b = l.take<uint64_t>(qhk::kDtHdr + tps_r);
+    });
+    if (r) return r;
+    QH_HIP(hipMemsetAsync(hdr_b, 0, (qhk::kDtHdr + tps_r) * sizeof(uint64_t), c->stream));
+    {
+      Timed t(c, "qh_k_dtc_records");
+      hipLaunchKernelGGL(qhk::qh_k_dtc_records, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
+                         c->stream, (const qh_dtable_view *)views, (uint64_t)nviews, entries, nbytes,
+                         (const qhk::SpanOut *)vcnt, (const uint64_t *)hdr_a, rcnt, cap, status, hdr_b);
+      QH_HIP(hipGetLastError());
+    }
+    return launch_scan_seg(c, rcnt, cap, 1, hdr_b, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts);
+  };
+  auto totals = [&]() -> int {
+    QH_HIP(hipMemcpyAsync(h, hdr_a + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hdr_b)
+      QH_HIP(hipMemcpyAsync(h + 8, hdr_b + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    QH_HIP(hipStreamSynchronize(c->stream));
+    return scan_seg_check(h[qhk::kDtTimeouts - 1] | h[8 + qhk::kDtTimeouts - 1], "compaction");
+  };
+
+  QH_HIP(hipMemsetAsync(hdr_a, 0, (qhk::kDtHdr + tps_v) * sizeof(uint64_t), c->stream));
+  {
+    Timed t(c, "qh_k_dtc_views");
+    hipLaunchKernelGGL(qhk::qh_k_dtc_views, dim3((unsigned)((nviews + 255) / 256)), dim3(256), 0,
+                       c->stream, (const qh_dtable_view *)views, (uint64_t)nviews, nentries, vcnt, status,
+                       hdr_a);
+    QH_HIP(hipGetLastError());
+  }
+  if ((rv = launch_scan_seg(c, vcnt, nviews, 1, hdr_a, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts)))
+    return rv;
+  if (c->dtc_hint && (rv = records(c->dtc_hint + c->dtc_hint / 8 + 16))) return rv;
+  if ((rv = totals())) return rv;  // the wait
+  const uint64_t nrec = h[qhk::kDtTot - 1];
+  if (nrec > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;  // (grid)
+  if (nrec > cap) {
+    // more than the room (or no room yet): the pass again for exactly this
+    // total; the second wait
+    if ((rv = records(nrec))) return rv;
+    if ((rv = totals())) return rv;
+  }
+  c->dtc_hint = nrec;
+  if (h[qhk::kDtErr - 1] | h[8 + qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  const uint64_t nbyte = h[8 + qhk::kDtTot - 1];
+  *nentries_out = nrec;
+  *nbytes_out = nbyte;
+  if (nrec > entries_out_cap || nbyte > bytes_out_cap) return QH_ERR_NOMEM;
+  if (nrec) {
+    Timed t(c, "qh_k_dtc_write");
+    const unsigned grid = (unsigned)((nrec * qhk::kDtLanes + 255) / 256);
+    hipLaunchKernelGGL(qhk::qh_k_dtc_write, dim3(grid), dim3(256), 0, c->stream,
+                       (const qh_dtable_view *)views, entries, bytes, (const qhk::SpanOut *)vcnt,
+                       (const qhk::SpanOut *)rcnt, nrec, entries_out, bytes_out);
+    QH_HIP(hipGetLastError());
+  }
+  {
+    Timed t(c, "qh_k_dtc_rebase");
+    hipLaunchKernelGGL(qhk::qh_k_dtc_rebase, dim3((unsigned)((nviews + 255) / 256)), dim3(256), 0,
+                       c->stream, views, (uint64_t)nviews, (const qhk::SpanOut *)vcnt);
     QH_HIP(hipGetLastError());
   }
   return 0;

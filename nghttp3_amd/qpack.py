@@ -187,6 +187,11 @@ def _load():
         lib.qh_qpack_dtables_apply.restype = i32
         lib.qh_dtables_apply_batch.argtypes = [vp] + dts_args + [i32]
         lib.qh_dtables_apply_batch.restype = i32
+        dtc_args = [sz, vp, vp, u64, vp, u64, vp, c.POINTER(u64), u64, vp, c.POINTER(u64), u64, vp]
+        lib.qh_qpack_dtables_compact.argtypes = dtc_args
+        lib.qh_qpack_dtables_compact.restype = i32
+        lib.qh_dtables_compact_batch.argtypes = [vp] + dtc_args + [i32]
+        lib.qh_dtables_compact_batch.restype = i32
         _L = lib
     return _L
 
@@ -871,8 +876,9 @@ class DynamicTableSet:
     ``dyn_bytes`` (uint8), ``nentries`` and ``nbytes`` go straight into
     ``emit_fields_dev(views=, entries=, dyn_bytes=, block_view=)`` and the
     dynamic planners, ``keys()`` with them.  Without a codec the same state is
-    numpy arrays and ``read_encoder`` the host twin.  The log only grows: a
-    copy of ``views`` taken before a call stays valid after it."""
+    numpy arrays and ``read_encoder`` the host twin.  Applying only grows the
+    log: a copy of ``views`` taken before a call stays valid after it.
+    ``compact()`` replaces the log by one that holds the live records alone."""
 
     def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None):
         self._lib = _load()
@@ -983,6 +989,73 @@ class DynamicTableSet:
                 _vp(status), _vp(consumed))
         self._apply(call, "qh_qpack_dtables_apply")
         return status[:nsel], consumed[:nsel]
+
+    def compact(self, extra_views=None):
+        """Compacts the log (qh_dtables_compact_batch on the device form,
+        qh_qpack_dtables_compact on the numpy form): the live records of
+        every table copied to fresh ``entries`` / ``dyn_bytes`` arrays, bytes
+        unshared, ``views`` rewritten, ``nentries`` / ``nbytes`` the compacted
+        lengths; ``keys()`` recomputes over the new log.  `extra_views`
+        (VIEW_DTYPE records or their bytes; a uint8 tensor on the device
+        form): older snapshots of tables the caller still needs, each given a
+        region of its own after the set's views; -> their rewritten copies
+        (None without extra_views).  Copies of ``views`` and of the old
+        arrays taken before the call stay valid together.  When to call is the
+        caller's decision: compare ``nentries`` and ``nbytes`` with what the
+        tables can hold.  A failed call leaves the object as it was."""
+        nt = self.ntables
+        dev = self.codec is not None
+        if dev:
+            import torch
+            parts = [self.views] if extra_views is None else \
+                [self.views, extra_views.reshape(-1).view(torch.uint8)]
+            views = torch.cat(parts) if len(parts) > 1 else self.views.clone()
+            nv = views.numel() // VIEW_DTYPE.itemsize
+            status = torch.empty(max(nv, 1), dtype=torch.int32, device=self._dev)
+            new = lambda n: torch.empty(n, dtype=torch.uint8, device=self._dev)
+            size = lambda t: t.numel()
+            p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+            fn, what = self._lib.qh_dtables_compact_batch, "qh_dtables_compact_batch"
+            head, tail = (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,)
+        else:
+            extra = None if extra_views is None else \
+                np.ascontiguousarray(extra_views).view(np.uint8).reshape(-1)
+            views = self.views.copy() if extra is None else np.concatenate([self.views, extra])
+            nv = views.size // VIEW_DTYPE.itemsize
+            status = np.zeros(max(nv, 1), dtype=np.int32)
+            new = lambda n: np.zeros(n, dtype=np.uint8)
+            size = lambda a: a.size
+            p = lambda a: None if a is None or a.size == 0 else _vp(a)
+            fn, what = self._lib.qh_qpack_dtables_compact, "qh_qpack_dtables_compact"
+            head, tail = (), ()
+
+        def call(ents, byts):
+            ne, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rv = fn(*head, nv, p(views), p(self.entries), self.nentries, p(self.dyn_bytes), self.nbytes,
+                    p(ents), ctypes.byref(ne), 0 if ents is None else size(ents) // 32,
+                    p(byts), ctypes.byref(nb), 0 if byts is None else size(byts), p(status), *tail)
+            return rv, int(ne.value), int(nb.value)
+        rv, ne, nb = call(None, None)  # the sizing call
+        if rv != _lib.QH_ERR_NOMEM:
+            _lib.check(rv, what)  # (0: nothing is live; the arrays are still replaced)
+        # fresh arrays by the growth rule of _grow, so that the next
+        # read_encoder finds room
+        caps = []
+        for need in (ne * 32, nb):
+            cap = 4096
+            while cap < need:
+                cap *= 2
+            caps.append(cap)
+        ents, byts = new(caps[0]), new(caps[1])
+        rv, ne, nb = call(ents, byts)
+        _lib.check(rv, what)
+        own = lambda a: a.clone() if dev else a.copy()
+        self.views = views if extra_views is None else own(views[:nt * VIEW_DTYPE.itemsize])
+        self.entries, self.dyn_bytes, self.nentries, self.nbytes = ents, byts, ne, nb
+        self._nkeys = 0  # (keys depend on content alone: keys() computes them over the new log)
+        if not dev:
+            self._keys = np.zeros(0, dtype=DYN_KEY_DTYPE)
+        return None if extra_views is None else own(views[nt * VIEW_DTYPE.itemsize:])
 
     def keys(self):
         """The log's keys (DYN_KEY_DTYPE records; a uint8 tensor of nentries *
