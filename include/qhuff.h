@@ -1079,6 +1079,137 @@ QH_EXPORT int qh_encode_fields_dyn_batch(
     uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
     uint64_t *max_cnt, uint64_t *min_cnt, int where);
 
+/* ---- The encoder with dynamic-table inserts, for many connections --------
+ * nghttp3_qpack_encoder_encode (qpack.c:1139-1204) for a batch of
+ * connections, bit-exact: per connection its sections, and their fields, are
+ * walked in order; per section process_dtable_update (:1240-1270, with
+ * shrink_dtable :978-1009), base = insert_count (:1163), allow_blocking
+ * (:1166-1170), then per field encode_nv in full (:1455-1628:
+ * decide_indexing_mode :1307-1371 with both indexing strategies and
+ * NGHTTP3_NV_FLAG_TRY_INDEX, lookup_stable :1630-1660, encoder_qpack_map_find
+ * :799-835 with can_reference :791-795 and the post-base match that
+ * suppresses an insert :1513-1514, check_draining :1446-1453, can_index
+ * :1378-1413, the four dtable_*_add paths over context_dtable_add
+ * :2071-2127, the writers' index arithmetic :1824-1837, :1911-1930,
+ * :2019-2069), the section prefix with its sign (:2424-2460) and the
+ * acknowledgement scalars moved as add_stream_ref would move them
+ * (:1024-1074).  Connections are independent: the batch is parallel over
+ * connections and sequential inside one.
+ *
+ * A connection is three records in caller-owned arrays over the shared log
+ * of qh_qpack_dtables_apply: views[t], acct[t] (acct.cap is the encoder's
+ * ctx.max_dtable_capacity) and enc[t].  There is no library object.
+ * Acknowledgement bookkeeping stays the caller's (per-stream reference
+ * queues, ack_header, add_icnt, cancel_stream, the decoder-stream parser):
+ * between calls it updates krcnt, pin_min, nblocked and nstreams from the
+ * max_cnt / min_cnt a call returns, and per section it passes sec_flags.
+ * Inside one call a connection's sections must belong to distinct streams
+ * (otherwise split the call).  After a section with max_cnt > 0: pin_min =
+ * min(pin_min, min_cnt), nstreams += !KNOWN, nblocked += (max_cnt > krcnt &&
+ * !BLOCKED).  With QH_ENC_IMMEDIATE_ACK, after every section krcnt =
+ * insert_count, pin_min = UINT64_MAX, nblocked = nstreams = 0
+ * (ack_everything, :2385-2393). */
+#define QH_ENC_IMMEDIATE_ACK 0x1u /* enc.flags: acknowledge every section at once */
+#define QH_ENC_STRAT_NONE 0x2u    /* NGHTTP3_QPACK_INDEXING_STRAT_NONE (else EAGER) */
+#define QH_ENC_CAP_PENDING 0x4u   /* ..._FLAG_PENDING_SET_DTABLE_CAP */
+
+#define QH_ENC_SEC_STREAM_BLOCKED 0x1u /* sec_flags: its stream is blocked on entry */
+#define QH_ENC_SEC_STREAM_KNOWN 0x2u   /* its stream has unacknowledged sections */
+
+#define QH_NV_NEVER_INDEX 0x1u /* nvflags: NGHTTP3_NV_FLAG_NEVER_INDEX */
+#define QH_NV_TRY_INDEX 0x2u   /* NGHTTP3_NV_FLAG_TRY_INDEX */
+
+typedef struct qh_enc_state { /* 64 B */
+  uint64_t krcnt;       /* known received count                                 */
+  uint64_t pin_min;     /* smallest min_cnt over the unacknowledged sections,
+                           UINT64_MAX for none (encoder_get_min_cnt, :969-976)  */
+  uint64_t max_blocked; /* ctx.max_blocked_streams                              */
+  uint64_t nblocked;    /* distinct blocked streams                             */
+  uint64_t nstreams;    /* streams with unacknowledged sections (:1510: no
+                           lookup at 2,000)                                     */
+  uint64_t flags;       /* QH_ENC_*                                             */
+  uint64_t min_update, last_update; /* :941-957 */
+} qh_enc_state;
+
+/* nghttp3_qpack_encoder_new at hard_max: capacity 0 (:847-861, :899-923). */
+QH_EXPORT void qh_enc_state_init(uint64_t hard_max, uint64_t max_blocked, uint64_t flags,
+                                 qh_dtable_view *view, qh_dtable_acct *acct, qh_enc_state *enc);
+/* nghttp3_qpack_encoder_set_max_dtable_capacity (:941-957); the instruction
+ * is written by the next call that encodes a section of the connection. */
+QH_EXPORT void qh_enc_state_set_capacity(qh_enc_state *enc, qh_dtable_acct *acct, uint64_t cap);
+
+/* Inputs: field i is strs[2i] (name) and strs[2i + 1] (value), spans of
+ * plain, with nvflags[i] (QH_NV_*; NULL: 0); section b is fields
+ * [field_start[b], field_start[b + 1]) with sec_flags[b] (NULL: 0);
+ * connection c's sections are [conn_start[c], conn_start[c + 1]) (nconns + 1
+ * entries, conn_start[0] = 0, conn_start[nconns] = nsections) and its table
+ * is tsel[c] (NULL: table c, nconns = ntables).  A table named twice, or an
+ * index >= ntables, gives QH_ERR_INVALID_ARGUMENT and no state is written.
+ *
+ * In/out: views, acct, enc; the log (entries, *nentries, entries_cap, bytes,
+ * *nbytes, bytes_cap); keys, a qh_dyn_key per log entry, entries_cap of
+ * them: keys[0, *nentries) are valid on entry and the call appends the keys
+ * of what it appends.
+ *
+ * Out: lines[nfields] (field i's line: name / value = 2i / 2i + 1 where
+ * used; post-base forms are QH_FL_INDEXED_PB / QH_FL_INDEXED_NAME_PB),
+ * prefixes, max_cnt, min_cnt (per section); dst / sections: the field
+ * sections back to back, section b at sections[b]; edst / estreams: one
+ * encoder-stream span per listed connection (length 0 when it wrote
+ * nothing); status[nconns].
+ *
+ * Log layout rule: qh_qpack_dtables_apply's, word for word.  Allocation
+ * follows list order; a connection's table moves iff the call inserts or
+ * duplicates into it; its records live on entry are copied verbatim to the
+ * entry cursor (their keys too); one record per insert follows, in order;
+ * per insert the name bytes (a literal or static name; a dynamic name
+ * reference or a duplicate shares the old offsets), then the value bytes
+ * (omitted for a duplicate); token is lookup_token of the name; nothing
+ * written earlier is modified.  So, for a call with no pending capacity
+ * reduction, the log, views and acct.size equal byte for byte what
+ * qh_qpack_dtables_apply writes when given the emitted streams from the same
+ * entry state.
+ *
+ * QH_ERR_NOMEM when any of entries_cap, bytes_cap, dst_cap, edst_cap is too
+ * small: *nentries, *nbytes, *dst_need and *edst_need are the exact needs,
+ * and views, acct, enc, keys and the log are untouched (the walk's results
+ * live in scratch; caller-visible state is written by a final commit step).
+ * On success they are the new lengths and the bytes written.
+ * A view whose live range leaves the log, or a referenced record whose
+ * strings leave [0, *nbytes), fails that connection only: status[c] =
+ * QH_ERR_INVALID_ARGUMENT, its sections and its stream have length 0 (its
+ * lines have opcode 0), its state is unchanged, nothing is read outside the
+ * log.  A walk has at most fields + live entries eviction steps.
+ * qh_qpack_encode_conns is host C over host pointers. */
+QH_EXPORT int qh_qpack_encode_conns(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields, const uint8_t *nvflags,
+    const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
+    const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
+    qh_dtable_view *views, qh_dtable_acct *acct, qh_enc_state *enc, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
+    qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status);
+
+/* The same over arrays in HBM (where must be QH_WHERE_DEVICE; nentries,
+ * nbytes, dst_need and edst_need are host scalars): a connection per 16-lane
+ * group walks (same source, csrc/qh_enc_core.h), the bytes are written by the
+ * section writer of qh_encode_sections_batch, and a commit kernel writes the
+ * log and the state once the four caps hold.  Three host waits: the walk's
+ * record and byte totals, the section writer's sizes, the stream writer's
+ * sizes.  Scratch (64 bytes per field, 24 per possible instruction) comes
+ * from the context.  nfields at most 2^30, nconns at most 2^27 - 1. */
+QH_EXPORT int qh_encode_conns_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *nvflags, const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
+    const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
+    qh_dtable_view *views, qh_dtable_acct *acct, qh_enc_state *enc, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
+    qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
+    int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

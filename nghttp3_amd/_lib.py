@@ -181,6 +181,12 @@ EXPORTED_FUNCTIONS = (
     "qh_qpack_plan_fields_dyn",
     "qh_plan_fields_dyn_batch",
     "qh_encode_fields_dyn_batch",
+    # the encoder with dynamic-table inserts for many connections
+    # (csrc/qh_encconn.c, csrc/qh_encconn.inc)
+    "qh_enc_state_init",
+    "qh_enc_state_set_capacity",
+    "qh_qpack_encode_conns",
+    "qh_encode_conns_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

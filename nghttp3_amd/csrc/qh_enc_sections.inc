@@ -116,28 +116,41 @@ __global__ void __launch_bounds__(256) qh_k_encsec_pick(const SpanIn *__restrict
 // a 16-lane scan gives the lines' offsets, in rounds of 16 lines.
 // *err (0 on entry) gets QH_ERR_INVALID_ARGUMENT for an unknown opcode or a
 // missing string.
+// flags (internal callers only; qh_encode_sections_batch passes 0):
+//   kEsStream     the "sections" are encoder streams: no prefix, and the
+//                 QH_ES_* instructions are accepted (qpack.c:2019-2069, :1272-1276);
+//   kEsSkippable  a section whose prefix has reserved != 0 is absent: no bytes.
+// Under either flag a line of opcode 0 is no bytes.
 constexpr uint32_t kSecLanes = 16;
+constexpr uint32_t kEsStream = 1u, kEsSkippable = 2u;
 __global__ void __launch_bounds__(256) qh_k_encsec_size(
     const qh_field_line *__restrict__ lines, const uint32_t *__restrict__ line_start,
     uint64_t nsec, const qh_section_prefix *__restrict__ pfx, const SpanIn *__restrict__ strs,
     uint64_t nstrs, const uint32_t *__restrict__ hlen, uint64_t *__restrict__ loff,
     uint64_t loff_cap, SpanOut *__restrict__ sec, int32_t *__restrict__ err,
-    unsigned long long *__restrict__ nlines_out) {
+    unsigned long long *__restrict__ nlines_out, uint32_t flags) {
   const uint64_t b = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kSecLanes;
   const uint32_t sl = threadIdx.x % kSecLanes;
   if (b >= nsec) return;  // (whole 16-lane groups)
   if (b == nsec - 1 && sl == 0) *nlines_out = line_start[nsec];
   unsigned long long sz = 2;
-  if (pfx) {
+  bool absent = false;
+  if (flags & kEsStream) {
+    sz = 0;
+  } else if (pfx) {
     const qh_section_prefix p = pfx[b];
     sz = es_vlen(p.ricnt, 8) + es_vlen(p.delta_base, 7);
+    if ((flags & kEsSkippable) && p.reserved) {
+      absent = true;
+      sz = 0;
+    }
   }
   int bad = 0;
   const uint32_t l1 = line_start[b + 1];
   for (uint32_t c0 = line_start[b]; c0 < l1; c0 += kSecLanes) {
     const uint32_t i = c0 + sl;
     unsigned long long x = 0;
-    if (i < l1) {
+    if (i < l1 && !absent) {
       const qh_field_line l = lines[i];
       const bool has_v = l.value >= 0 && (uint64_t)l.value < nstrs;
       const bool has_n = l.name >= 0 && (uint64_t)l.name < nstrs;
@@ -153,6 +166,22 @@ __global__ void __launch_bounds__(256) qh_k_encsec_size(
         case QH_FL_LITERAL:
           if (!has_v || !has_n) { bad = 1; break; }
           x = es_str_bytes(strs, hlen, l.name, 3) + es_str_bytes(strs, hlen, l.value, 7);
+          break;
+        case QH_ES_INSERT_INDEXED:
+          if (!(flags & kEsStream) || !has_v) { bad = 1; break; }
+          x = es_vlen(l.index, 6) + es_str_bytes(strs, hlen, l.value, 7);
+          break;
+        case QH_ES_INSERT:
+          if (!(flags & kEsStream) || !has_v || !has_n) { bad = 1; break; }
+          x = es_str_bytes(strs, hlen, l.name, 5) + es_str_bytes(strs, hlen, l.value, 7);
+          break;
+        case QH_ES_SET_DTABLE_CAP:
+        case QH_ES_DUPLICATE:
+          if (!(flags & kEsStream)) { bad = 1; break; }
+          x = es_vlen(l.index, 5);
+          break;
+        case 0:
+          if (!flags) bad = 1;
           break;
         default: bad = 1;
       }
@@ -243,11 +272,13 @@ __global__ void __launch_bounds__(256) qh_k_encsec_write(
     const SpanOut *__restrict__ eout, const qh_field_line *__restrict__ lines,
     const uint32_t *__restrict__ line_start, uint64_t nsec, uint64_t nlines,
     const qh_section_prefix *__restrict__ pfx, const uint64_t *__restrict__ loff,
-    const SpanOut *__restrict__ sec, uint8_t *__restrict__ dst) {
+    const SpanOut *__restrict__ sec, uint8_t *__restrict__ dst, uint32_t flags) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < nsec) {
+    if (flags & kEsStream) return;
     uint8_t *p = dst + sec[t].off;
     const qh_section_prefix q = pfx ? pfx[t] : qh_section_prefix{0, 0, 0, 0};
+    if ((flags & kEsSkippable) && q.reserved) return;
     const uint32_t j = es_put(p, 0, q.ricnt, 8);
     es_put(p + j, q.sign ? 0x80 : 0, q.delta_base, 7);
     return;
@@ -281,6 +312,21 @@ __global__ void __launch_bounds__(256) qh_k_encsec_write(
       es_emit(p + j, 0, 7, v);
       break;
     }
+    case QH_ES_INSERT_INDEXED: {
+      const EsStr v = es_fetch(plain, strs, hlen, ebuf, eout, l.value);
+      const uint32_t j = es_put(p, dyn ? 0x80 : 0xc0, l.index, 6);
+      es_emit(p + j, 0, 7, v);
+      break;
+    }
+    case QH_ES_INSERT: {
+      const EsStr nm = es_fetch(plain, strs, hlen, ebuf, eout, l.name);
+      const EsStr v = es_fetch(plain, strs, hlen, ebuf, eout, l.value);
+      const uint32_t j = es_emit(p, 0x40, 5, nm);
+      es_emit(p + j, 0, 7, v);
+      break;
+    }
+    case QH_ES_SET_DTABLE_CAP: es_put(p, 0x20, l.index, 5); break;
+    case QH_ES_DUPLICATE: es_put(p, 0x00, l.index, 5); break;
     default: break;
   }
 }
@@ -302,6 +348,7 @@ struct EncSec {
   uint64_t dst_cap;
   qh_span_in *sections;
   uint64_t need;  // host: dst bytes of all sections
+  uint32_t flags = 0;  // kEsStream | kEsSkippable (qh_k_encsec_size)
 };
 
 // The picked strings through qh_k_enc_lanes, their lengths (eout) and block
@@ -378,7 +425,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
                        dim3((unsigned)((nb * qhk::kSecLanes + 255) / 256)), dim3(256), 0,
                        c->stream, e.lines, e.line_start, nb, e.pfx, (const qhk::SpanIn *)e.strs,
                        ns, (const uint32_t *)hlen, mem<uint64_t>(c, kBufEncSecLoff), cap, sec, err,
-                       reinterpret_cast<unsigned long long *>(hdr + 5));
+                       reinterpret_cast<unsigned long long *>(hdr + 5), e.flags);
     QH_HIP(hipGetLastError());
     return 0;
   };
@@ -439,7 +486,7 @@ int encsec_device(qh_ctx *c, EncSec &e) {
                      c->stream, e.plain, (const qhk::SpanIn *)e.strs, (const uint32_t *)hlen,
                      mem<const uint8_t>(c, kBufEncSecCodes), (const qhk::SpanOut *)eout, e.lines,
                      e.line_start, nb, nl, e.pfx, mem<const uint64_t>(c, kBufEncSecLoff),
-                     (const qhk::SpanOut *)sec, e.dst);
+                     (const qhk::SpanOut *)sec, e.dst, e.flags);
   QH_HIP(hipGetLastError());
   return 0;
 }

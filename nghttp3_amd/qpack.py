@@ -56,6 +56,13 @@ assert FIELD_DTYPE.itemsize == 32 and DYN_ENTRY_DTYPE.itemsize == 32 and VIEW_DT
 DYN_KEY_DTYPE = np.dtype([("name_id", "<u4"), ("name_len", "<u4"), ("value_len", "<u4"),
                           ("value_hash", "<u4")])
 assert DYN_KEY_DTYPE.itemsize == 16
+ENC_STATE_DTYPE = np.dtype([("krcnt", "<u8"), ("pin_min", "<u8"), ("max_blocked", "<u8"),
+                            ("nblocked", "<u8"), ("nstreams", "<u8"), ("flags", "<u8"),
+                            ("min_update", "<u8"), ("last_update", "<u8")])
+assert ENC_STATE_DTYPE.itemsize == 64
+ENC_IMMEDIATE_ACK, ENC_STRAT_NONE, ENC_CAP_PENDING = 0x1, 0x2, 0x4
+ENC_SEC_STREAM_BLOCKED, ENC_SEC_STREAM_KNOWN = 0x1, 0x2
+NV_NEVER_INDEX, NV_TRY_INDEX = 0x1, 0x2
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -192,6 +199,17 @@ def _load():
         lib.qh_qpack_dtables_compact.restype = i32
         lib.qh_dtables_compact_batch.argtypes = [vp] + dtc_args + [i32]
         lib.qh_dtables_compact_batch.restype = i32
+        lib.qh_enc_state_init.argtypes = [u64, u64, u64, vp, vp, vp]
+        lib.qh_enc_state_init.restype = None
+        lib.qh_enc_state_set_capacity.argtypes = [vp, vp, u64]
+        lib.qh_enc_state_set_capacity.restype = None
+        pu64 = c.POINTER(u64)
+        encc_args = [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, pu64, u64, vp, pu64,
+                     u64, vp, vp, vp, vp, vp, vp, u64, vp, pu64, vp, u64, vp, pu64, vp]
+        lib.qh_qpack_encode_conns.argtypes = encc_args
+        lib.qh_qpack_encode_conns.restype = i32
+        lib.qh_encode_conns_batch.argtypes = [vp] + encc_args + [i32]
+        lib.qh_encode_conns_batch.restype = i32
         _L = lib
     return _L
 
@@ -1075,6 +1093,232 @@ class DynamicTableSet:
                          n - self._nkeys, self._keys)
             self._nkeys = n
         return self._keys[:n * 16]
+
+
+class EncoderSet:
+    """The QPACK encoders of `n` connections with dynamic-table inserts over
+    one log (qh_qpack_encode_conns / qh_encode_conns_batch): `n` fresh
+    encoders of hard maximum capacity `hard_max` (a scalar, or one value per
+    connection) at capacity 0, as nghttp3_qpack_encoder_new leaves them.
+
+    The object owns the views, acct and enc records, the log and its keys,
+    grows them on QH_ERR_NOMEM and calls again, as DynamicTableSet does.
+    With ``device=None`` they are numpy arrays and ``encode`` is the host
+    twin; with a device index they are torch tensors there and
+    ``encode_dev(codec, ...)`` runs the walk on the GPU.  Acknowledgements
+    are the caller's: between calls it edits ``enc_records()`` (krcnt,
+    pin_min, nblocked, nstreams) and stores them back with
+    ``set_enc_records``."""
+
+    def __init__(self, hard_max, n: int, max_blocked=0, immediate_ack: bool = False, device=None,
+                 strat_none: bool = False):
+        self._lib = _load()
+        self.n = int(n)
+        hm = np.broadcast_to(np.asarray(hard_max, dtype=np.uint64), (self.n,))
+        mb = np.broadcast_to(np.asarray(max_blocked, dtype=np.uint64), (self.n,))
+        flags = (ENC_IMMEDIATE_ACK if immediate_ack else 0) | (ENC_STRAT_NONE if strat_none else 0)
+        views = np.zeros(max(self.n, 1), dtype=VIEW_DTYPE)[:self.n]
+        acct = np.zeros(max(self.n, 1), dtype=ACCT_DTYPE)[:self.n]
+        enc = np.zeros(max(self.n, 1), dtype=ENC_STATE_DTYPE)[:self.n]
+        v1, a1, e1 = (np.zeros(1, dtype=d) for d in (VIEW_DTYPE, ACCT_DTYPE, ENC_STATE_DTYPE))
+        for t in range(self.n):
+            self._lib.qh_enc_state_init(int(hm[t]), int(mb[t]), flags, _vp(v1), _vp(a1), _vp(e1))
+            views[t], acct[t], enc[t] = v1[0], a1[0], e1[0]
+        self.nentries = 0
+        self.nbytes = 0
+        self.device = device
+        arrays = {"views": views, "acct": acct, "enc": enc}
+        if device is None:
+            for k, a in arrays.items():
+                setattr(self, k, a.view(np.uint8).copy())
+            for k in ("entries", "dyn_bytes", "keys"):
+                setattr(self, k, np.zeros(0, dtype=np.uint8))
+        else:
+            import torch
+            self._dev = torch.device("cuda", int(device))
+            for k, a in arrays.items():
+                setattr(self, k, torch.from_numpy(a.view(np.uint8).copy()).to(self._dev))
+            for k in ("entries", "dyn_bytes", "keys"):
+                setattr(self, k, torch.empty(0, dtype=torch.uint8, device=self._dev))
+
+    # -- state access (numpy copies; the device form copies through the host)
+
+    def _host(self, name, dtype):
+        a = getattr(self, name)
+        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        return a.view(dtype).copy()
+
+    def _store(self, name, recs):
+        raw = np.ascontiguousarray(recs).view(np.uint8).reshape(-1).copy()
+        if self.device is None:
+            setattr(self, name, raw)
+        else:
+            import torch
+            setattr(self, name, torch.from_numpy(raw).to(self._dev))
+
+    def view_records(self):
+        return self._host("views", VIEW_DTYPE)
+
+    def acct_records(self):
+        return self._host("acct", ACCT_DTYPE)
+
+    def enc_records(self):
+        return self._host("enc", ENC_STATE_DTYPE)
+
+    def set_enc_records(self, recs):
+        self._store("enc", np.ascontiguousarray(recs, dtype=ENC_STATE_DTYPE))
+
+    def log(self):
+        """-> (entries DYN_ENTRY_DTYPE, bytes uint8, keys DYN_KEY_DTYPE), numpy copies."""
+        return (self._host("entries", np.uint8)[:self.nentries * 32].view(DYN_ENTRY_DTYPE),
+                self._host("dyn_bytes", np.uint8)[:self.nbytes],
+                self._host("keys", np.uint8)[:self.nentries * 16].view(DYN_KEY_DTYPE))
+
+    def set_capacity(self, caps):
+        """nghttp3_qpack_encoder_set_max_dtable_capacity per connection (a
+        scalar or one value each); the instruction is written by the next
+        call that encodes a section of the connection."""
+        caps = np.broadcast_to(np.asarray(caps, dtype=np.uint64), (self.n,))
+        acct, enc = self.acct_records(), self.enc_records()
+        a1, e1 = np.zeros(1, dtype=ACCT_DTYPE), np.zeros(1, dtype=ENC_STATE_DTYPE)
+        for t in range(self.n):
+            a1[0], e1[0] = acct[t], enc[t]
+            self._lib.qh_enc_state_set_capacity(_vp(e1), _vp(a1), int(caps[t]))
+            acct[t], enc[t] = a1[0], e1[0]
+        self._store("acct", acct)
+        self._store("enc", enc)
+
+    _grow = DynamicTableSet._grow
+
+    def _call(self, fn, head, tail, ptr, size, new, plain, strs, nfields, nvflags, field_start,
+              nsections, sec_flags, conn_start, nconns, tsel, caps=None):
+        """One call, grown and repeated on QH_ERR_NOMEM (`caps`: fixed
+        (entries, bytes, dst, edst) capacities instead, for tests; the call is
+        then made once and its return value and needs handed back)."""
+        lines = new(max(nfields, 1) * 24)
+        prefixes = new(max(nsections, 1) * 24)
+        mx, mn = new(max(nsections, 1) * 8), new(max(nsections, 1) * 8)
+        sections = new(max(nsections, 1) * 16)
+        estreams = new(max(nconns, 1) * 16)
+        status = new(max(nconns, 1) * 4)
+        # (the output buffers start at the sizes the last call needed)
+        dst_cap, edst_cap = getattr(self, "_out_caps", (4096, 4096))
+        pad = 0
+        if caps is not None:
+            # exactly the given room, with 64 sentinel bytes (0xA5) behind it
+            pad = 64
+            for name, have, cap in (("entries", self.nentries * 32, caps[0] * 32),
+                                    ("keys", self.nentries * 16, caps[0] * 16),
+                                    ("dyn_bytes", self.nbytes, caps[1])):
+                a = new(cap + pad)
+                a[:] = 0xA5
+                a[:have] = getattr(self, name)[:have]
+                setattr(self, name, a)
+            dst_cap, edst_cap = caps[2], caps[3]
+        for _ in range(3):
+            dst, edst = new(dst_cap + pad), new(edst_cap + pad)
+            if pad:
+                dst[:] = 0xA5
+                edst[:] = 0xA5
+            ne, nb = ctypes.c_uint64(self.nentries), ctypes.c_uint64(self.nbytes)
+            dn, en = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            ecap = min(size(self.entries) // 32, size(self.keys) // 16) if caps is None else caps[0]
+            bcap = size(self.dyn_bytes) if caps is None else caps[1]
+            rv = fn(*head, ptr(plain), ptr(strs), nfields, ptr(nvflags), ptr(field_start), nsections,
+                    ptr(sec_flags), ptr(conn_start), nconns, ptr(tsel), self.n, ptr(self.views),
+                    ptr(self.acct), ptr(self.enc), ptr(self.entries), ctypes.byref(ne), ecap,
+                    ptr(self.dyn_bytes), ctypes.byref(nb), bcap, ptr(self.keys), ptr(lines),
+                    ptr(prefixes), ptr(mx), ptr(mn), ptr(dst), dst_cap, ptr(sections),
+                    ctypes.byref(dn), ptr(edst), edst_cap, ptr(estreams), ctypes.byref(en),
+                    ptr(status), *tail)
+            needs = (int(ne.value), int(nb.value), int(dn.value), int(en.value))
+            if rv != _lib.QH_ERR_NOMEM or caps is not None:
+                break
+            self._grow("entries", self.nentries * 32, needs[0] * 32, 4096)
+            self._grow("keys", self.nentries * 16, needs[0] * 16, 2048)
+            self._grow("dyn_bytes", self.nbytes, needs[1], 4096)
+            while dst_cap < needs[2]:
+                dst_cap *= 2
+            while edst_cap < needs[3]:
+                edst_cap *= 2
+            self._out_caps = (dst_cap, edst_cap)
+        res = {"rv": rv, "needs": needs, "lines": lines, "prefixes": prefixes, "max_cnt": mx,
+               "min_cnt": mn, "dst": dst, "sections": sections, "edst": edst, "estreams": estreams,
+               "status": status, "nfields": nfields, "nsections": nsections, "nconns": nconns}
+        if caps is not None:
+            if rv == 0:
+                self.nentries, self.nbytes = needs[0], needs[1]
+            return res
+        _lib.check(rv, fn.__name__)
+        self.nentries, self.nbytes = needs[0], needs[1]
+        return res
+
+    def encode(self, plain, strs, field_start, conn_start, nvflags=None, sec_flags=None, tsel=None,
+               caps=None):
+        """The host twin (qh_qpack_encode_conns) over numpy arrays: plain
+        uint8, strs SPAN_IN_DTYPE (two per field), field_start / conn_start
+        uint32, nvflags / sec_flags uint8 or None, tsel uint32 or None.
+        -> dict of numpy arrays: lines (FIELD_LINE_DTYPE), prefixes
+        (PREFIX_DTYPE), max_cnt, min_cnt (uint64), dst (uint8, the sections'
+        bytes), sections (SPAN_IN_DTYPE), edst (uint8), estreams
+        (SPAN_IN_DTYPE, one per listed connection), status (int32)."""
+        assert self.device is None
+        plain = _u8(plain)
+        strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
+        fs = np.ascontiguousarray(field_start, dtype=np.uint32)
+        cs = np.ascontiguousarray(conn_start, dtype=np.uint32)
+        opt = lambda a, d: None if a is None else np.ascontiguousarray(a, dtype=d)
+        nv, sf, sel = opt(nvflags, np.uint8), opt(sec_flags, np.uint8), opt(tsel, np.uint32)
+        nfields, nsections = strs.size // 2, fs.size - 1
+        nconns = cs.size - 1
+        ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
+        if sel is not None and sel.size == 0:  # (an empty list is still a list)
+            ptr_sel = np.zeros(1, dtype=np.uint32)
+        else:
+            ptr_sel = sel
+        r = self._call(self._lib.qh_qpack_encode_conns, (), (), ptr, lambda a: a.size,
+                       lambda n: np.zeros(n, dtype=np.uint8), plain, strs, nfields, nv, fs,
+                       nsections, sf, cs, nconns, ptr_sel, caps)
+        return self._unpack(r, lambda a: a)
+
+    def encode_dev(self, codec: HuffmanBatchCodec, plain, strs, field_start, conn_start,
+                   nvflags=None, sec_flags=None, tsel=None, caps=None):
+        """qh_encode_conns_batch: the same over torch tensors in HBM (plain
+        uint8, strs int64 [2 nfields, 2] as SPAN_IN_DTYPE records,
+        field_start / conn_start / tsel int32, nvflags / sec_flags uint8).
+        -> the same dict, of tensors viewed as bytes (``to_host`` converts)."""
+        import torch
+        assert self.device is not None
+        nfields, nsections = int(strs.shape[0]) // 2, int(field_start.shape[0]) - 1
+        nconns = int(conn_start.shape[0]) - 1
+        ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+        if tsel is not None and tsel.numel() == 0:
+            tsel = torch.zeros(1, dtype=torch.int32, device=self._dev)
+        r = self._call(self._lib.qh_encode_conns_batch, (codec._ctx,), (_lib.QH_WHERE_DEVICE,), ptr,
+                       lambda t: t.numel(),
+                       lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev), plain, strs,
+                       nfields, nvflags, field_start, nsections, sec_flags, conn_start, nconns, tsel,
+                       caps)
+        return r
+
+    @staticmethod
+    def _unpack(r, host):
+        nf, ns, nc = r["nfields"], r["nsections"], r["nconns"]
+        out = dict(r)
+        out["lines"] = host(r["lines"])[:nf * 24].view(FIELD_LINE_DTYPE)
+        out["prefixes"] = host(r["prefixes"])[:ns * 24].view(PREFIX_DTYPE)
+        out["max_cnt"] = host(r["max_cnt"])[:ns * 8].view(np.uint64)
+        out["min_cnt"] = host(r["min_cnt"])[:ns * 8].view(np.uint64)
+        out["sections"] = host(r["sections"])[:ns * 16].view(SPAN_IN_DTYPE)
+        out["estreams"] = host(r["estreams"])[:nc * 16].view(SPAN_IN_DTYPE)
+        out["status"] = host(r["status"])[:nc * 4].view(np.int32)
+        out["dst"], out["edst"] = host(r["dst"]), host(r["edst"])  # (needs[2], needs[3] bytes)
+        return out
+
+    @classmethod
+    def to_host(cls, r):
+        """An ``encode_dev`` result as ``encode`` returns it (numpy)."""
+        return cls._unpack(r, lambda t: t.cpu().numpy())
 
 
 def dyn_keys(entries, dyn_bytes, first: int = 0, keys=None):
