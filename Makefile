@@ -97,6 +97,9 @@ $(DEV): $(CSRC)/qh_device.hip $(CSRC)/*.inc dev/csrc/*.inc $(CSRC)/qh_common.h $
 $(ORACLE): oracle/qh_oracle.c oracle/qh_oracle.h
 	$(CC) -std=c11 -O2 -mavx2 -fPIC -shared -pthread -Wall -o $@ $<
 
+# The replay driver on the reference library, when the reference tree is there.
+include oracle/ref.mk
+
 clean:
 	rm -f $(LIBDIR)/*.o $(DRIVER) $(LIB) $(ARCHIVE) $(STAMPS) $(DEV) $(ORACLE)
 

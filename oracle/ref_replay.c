@@ -1,0 +1,347 @@
+/* Replays a case file through the reference library's QPACK encoder and
+ * decoder and writes what it did as a transcript (oracle/README.md has both
+ * formats).  The program decides nothing: every stream id, flag,
+ * acknowledgement and capacity is in the case file, and every line of the
+ * transcript is read back from the library.  Built by oracle/ref.mk against
+ * the reference tree into oracle/_ref/; the tests read committed transcripts
+ * (tests/golden/ref_replay/), never this program's output directly.
+ *
+ *   ref_replay CASEFILE > TRANSCRIPT
+ *
+ * nghttp3/nghttp3.h is the public API; lib/nghttp3_qpack.h is included for
+ * the values the public API does not return (the encoder's scalars, the
+ * table's entries, a section's counts, Base). */
+#include <inttypes.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <nghttp3/nghttp3.h>
+
+#include "nghttp3_qpack.h"
+
+static FILE *in;
+static const nghttp3_mem *mem;
+
+static void die(const char *what) {
+  fprintf(stderr, "ref_replay: %s\n", what);
+  exit(2);
+}
+
+/* The next whitespace-separated token, or NULL at the end of the file. */
+static char *token(void) {
+  static char *buf;
+  static size_t cap;
+  size_t n = 0;
+  int c;
+  while ((c = fgetc(in)) != EOF && (c == ' ' || c == '\n' || c == '\t' || c == '\r')) {
+  }
+  if (c == EOF) {
+    return NULL;
+  }
+  for (; c != EOF && c != ' ' && c != '\n' && c != '\t' && c != '\r'; c = fgetc(in)) {
+    if (n + 2 > cap) {
+      cap = cap ? cap * 2 : 256;
+      buf = realloc(buf, cap);
+      if (!buf) {
+        die("out of memory");
+      }
+    }
+    buf[n++] = (char)c;
+  }
+  buf[n] = 0;
+  return buf;
+}
+
+static uint64_t number(void) {
+  char *t = token(), *end;
+  uint64_t v;
+  if (!t) {
+    die("number expected");
+  }
+  v = strtoull(t, &end, 10);
+  if (*end) {
+    die("bad number");
+  }
+  return v;
+}
+
+static int nibble(int c) {
+  if (c >= '0' && c <= '9') {
+    return c - '0';
+  }
+  if (c >= 'a' && c <= 'f') {
+    return c - 'a' + 10;
+  }
+  die("bad hex digit");
+  return 0;
+}
+
+/* A token of hex digits ("-": no bytes) -> malloc'ed bytes. */
+static uint8_t *hexbytes(size_t *plen) {
+  char *t = token();
+  size_t n, i;
+  uint8_t *p;
+  if (!t) {
+    die("hex string expected");
+  }
+  if (strcmp(t, "-") == 0) {
+    *plen = 0;
+    return malloc(1);
+  }
+  n = strlen(t);
+  if (n % 2) {
+    die("odd hex string");
+  }
+  p = malloc(n / 2 + 1);
+  if (!p) {
+    die("out of memory");
+  }
+  for (i = 0; i < n / 2; ++i) {
+    p[i] = (uint8_t)(nibble(t[2 * i]) << 4 | nibble(t[2 * i + 1]));
+  }
+  *plen = n / 2;
+  return p;
+}
+
+static void put_hex(const uint8_t *p, size_t n) {
+  size_t i;
+  putchar('"');
+  for (i = 0; i < n; ++i) {
+    printf("%02x", p[i]);
+  }
+  putchar('"');
+}
+
+static void put_table(nghttp3_qpack_context *ctx) {
+  size_t n = nghttp3_ringbuf_len(&ctx->dtable), i;
+  printf("\"tab\":[");
+  for (i = 0; i < n; ++i) { /* oldest first */
+    nghttp3_qpack_entry *ent = nghttp3_qpack_context_dtable_get(ctx, ctx->next_absidx - n + i);
+    nghttp3_vec name = nghttp3_rcbuf_get_buf(ent->nv.name);
+    nghttp3_vec value = nghttp3_rcbuf_get_buf(ent->nv.value);
+    printf("%s[", i ? "," : "");
+    put_hex(name.base, name.len);
+    putchar(',');
+    put_hex(value.base, value.len);
+    putchar(']');
+  }
+  putchar(']');
+}
+
+/* ---- encoder ---- */
+
+static nghttp3_qpack_encoder *enc;
+
+static void put_enc_state(void) {
+  printf("\"sc\":{\"insert_count\":%" PRIu64 ",\"nlive\":%zu,\"cap\":%zu,\"size\":%zu,\"krcnt\":%" PRIu64
+         ",\"nblocked\":%zu,\"nstreams\":%zu,\"pending\":%d,\"min_update\":%" PRIu64
+         ",\"last_update\":%zu,\"pin_min\":",
+         enc->ctx.next_absidx, nghttp3_ringbuf_len(&enc->ctx.dtable), enc->ctx.max_dtable_capacity,
+         enc->ctx.dtable_size, enc->krcnt, nghttp3_qpack_encoder_get_num_blocked_streams2(enc),
+         nghttp3_map_size(&enc->streams),
+         (enc->flags & NGHTTP3_QPACK_ENCODER_FLAG_PENDING_SET_DTABLE_CAP) ? 1 : 0,
+         (uint64_t)enc->min_dtable_update, enc->last_max_dtable_update);
+  if (nghttp3_pq_empty(&enc->min_cnts)) { /* no unacknowledged reference */
+    printf("null},");
+  } else {
+    printf("%" PRIu64 "},", nghttp3_qpack_encoder_get_min_cnt(enc));
+  }
+  put_table(&enc->ctx);
+}
+
+static size_t nrefs(int64_t sid) {
+  nghttp3_qpack_stream *s = nghttp3_qpack_encoder_find_stream(enc, sid);
+  return s ? nghttp3_ringbuf_len(&s->refs) : 0;
+}
+
+static void enc_encode(void) {
+  int64_t sid = (int64_t)number();
+  size_t nf = (size_t)number(), i, before;
+  nghttp3_nv *nva = calloc(nf + 1, sizeof(*nva));
+  nghttp3_buf pbuf, rbuf, ebuf;
+  int rv;
+  if (!nva) {
+    die("out of memory");
+  }
+  for (i = 0; i < nf; ++i) {
+    nva[i].flags = (uint8_t)number();
+    nva[i].name = hexbytes(&nva[i].namelen);
+    nva[i].value = hexbytes(&nva[i].valuelen);
+  }
+  nghttp3_buf_init(&pbuf);
+  nghttp3_buf_init(&rbuf);
+  nghttp3_buf_init(&ebuf);
+  before = nrefs(sid);
+  rv = nghttp3_qpack_encoder_encode(enc, &pbuf, &rbuf, &ebuf, sid, nva, nf);
+  printf("{\"op\":\"encode\",\"sid\":%" PRId64 ",\"rv\":%d,\"sec\":\"", sid, rv);
+  for (i = 0; i < nghttp3_buf_len(&pbuf); ++i) {
+    printf("%02x", pbuf.pos[i]);
+  }
+  for (i = 0; i < nghttp3_buf_len(&rbuf); ++i) {
+    printf("%02x", rbuf.pos[i]);
+  }
+  printf("\",\"es\":");
+  put_hex(ebuf.pos, nghttp3_buf_len(&ebuf));
+  if (nrefs(sid) > before) { /* the section's reference record, as the library keeps it */
+    nghttp3_qpack_stream *s = nghttp3_qpack_encoder_find_stream(enc, sid);
+    nghttp3_qpack_header_block_ref *ref =
+      *(nghttp3_qpack_header_block_ref **)nghttp3_ringbuf_get(&s->refs, nghttp3_ringbuf_len(&s->refs) - 1);
+    printf(",\"max_cnt\":%" PRIu64 ",\"min_cnt\":%" PRIu64 ",", ref->max_cnt, ref->min_cnt);
+  } else { /* no dynamic entry referred to: the library keeps no record */
+    printf(",\"max_cnt\":null,\"min_cnt\":null,");
+  }
+  put_enc_state();
+  printf("}\n");
+  nghttp3_buf_free(&pbuf, mem);
+  nghttp3_buf_free(&rbuf, mem);
+  nghttp3_buf_free(&ebuf, mem);
+  for (i = 0; i < nf; ++i) {
+    free((void *)nva[i].name);
+    free((void *)nva[i].value);
+  }
+  free(nva);
+}
+
+/* ---- decoder ---- */
+
+static nghttp3_qpack_decoder *dec;
+
+static void put_dec_state(void) {
+  printf("\"insert_count\":%" PRIu64 ",\"size\":%zu,\"cap\":%zu,", nghttp3_qpack_decoder_get_icnt(dec),
+         dec->ctx.dtable_size, dec->ctx.max_dtable_capacity);
+  put_table(&dec->ctx);
+}
+
+static void dec_section(void) {
+  int64_t sid = (int64_t)number();
+  size_t len, at = 0;
+  uint8_t *src = hexbytes(&len);
+  nghttp3_qpack_stream_context *sctx;
+  nghttp3_ssize total = 0;
+  int blocked = 0, first = 1;
+  if (nghttp3_qpack_stream_context_new(&sctx, sid, mem) != 0) {
+    die("out of memory");
+  }
+  printf("{\"op\":\"section\",\"sid\":%" PRId64 ",\"fields\":[", sid);
+  for (;;) {
+    nghttp3_qpack_nv nv;
+    uint8_t flags = 0;
+    nghttp3_ssize n = nghttp3_qpack_decoder_read_request(dec, sctx, &nv, &flags, src + at, len - at, 1);
+    if (n < 0) {
+      total = n;
+      break;
+    }
+    at += (size_t)n;
+    total += n;
+    if (flags & NGHTTP3_QPACK_DECODE_FLAG_BLOCKED) {
+      blocked = 1;
+      break;
+    }
+    if (flags & NGHTTP3_QPACK_DECODE_FLAG_EMIT) {
+      nghttp3_vec name = nghttp3_rcbuf_get_buf(nv.name), value = nghttp3_rcbuf_get_buf(nv.value);
+      printf("%s[", first ? "" : ",");
+      first = 0;
+      put_hex(name.base, name.len);
+      putchar(',');
+      put_hex(value.base, value.len);
+      printf(",%d,%d]", (int)nv.token, (nv.flags & NGHTTP3_NV_FLAG_NEVER_INDEX) ? 1 : 0);
+      nghttp3_rcbuf_decref(nv.name);
+      nghttp3_rcbuf_decref(nv.value);
+    }
+    if (flags & NGHTTP3_QPACK_DECODE_FLAG_FINAL) {
+      break;
+    }
+    if (n == 0 && !(flags & NGHTTP3_QPACK_DECODE_FLAG_EMIT)) {
+      die("the decoder neither read nor emitted");
+    }
+  }
+  printf("],\"rv\":%td,\"blocked\":%d,\"ricnt\":%" PRIu64 ",\"base\":%" PRIu64 ",", (ptrdiff_t)total, blocked,
+         nghttp3_qpack_stream_context_get_ricnt2(sctx), sctx->base);
+  put_dec_state();
+  printf("}\n");
+  nghttp3_qpack_stream_context_del(sctx);
+  free(src);
+}
+
+int main(int argc, char **argv) {
+  char *t;
+  if (argc != 2 || !(in = fopen(argv[1], "r"))) {
+    die("usage: ref_replay CASEFILE");
+  }
+  mem = nghttp3_mem_default();
+  while ((t = token()) != NULL) {
+    if (strcmp(t, "enc") == 0) { /* enc new hard_max max_blocked strat */
+      size_t hard_max, max_blocked;
+      uint64_t strat;
+      token();
+      hard_max = (size_t)number();
+      max_blocked = (size_t)number();
+      strat = number();
+      nghttp3_qpack_encoder_del(enc);
+      nghttp3_qpack_decoder_del(dec);
+      dec = NULL;
+      if (nghttp3_qpack_encoder_new(&enc, hard_max, mem) != 0) {
+        die("out of memory");
+      }
+      nghttp3_qpack_encoder_set_max_blocked_streams(enc, max_blocked);
+      nghttp3_qpack_encoder_set_indexing_strat(enc, (nghttp3_qpack_indexing_strat)strat);
+      printf("{\"op\":\"new\",");
+      put_enc_state();
+      printf("}\n");
+    } else if (strcmp(t, "dec") == 0) { /* dec new hard_max max_blocked */
+      size_t hard_max, max_blocked;
+      token();
+      hard_max = (size_t)number();
+      max_blocked = (size_t)number();
+      nghttp3_qpack_encoder_del(enc);
+      nghttp3_qpack_decoder_del(dec);
+      enc = NULL;
+      if (nghttp3_qpack_decoder_new(&dec, hard_max, max_blocked, mem) != 0) {
+        die("out of memory");
+      }
+      printf("{\"op\":\"new\",");
+      put_dec_state();
+      printf("}\n");
+    } else if (strcmp(t, "cap") == 0 && enc) {
+      nghttp3_qpack_encoder_set_max_dtable_capacity(enc, (size_t)number());
+      printf("{\"op\":\"cap\",");
+      put_enc_state();
+      printf("}\n");
+    } else if (strcmp(t, "cap") == 0 && dec) {
+      int rv = nghttp3_qpack_decoder_set_max_dtable_capacity(dec, (size_t)number());
+      printf("{\"op\":\"cap\",\"rv\":%d,", rv);
+      put_dec_state();
+      printf("}\n");
+    } else if (strcmp(t, "encode") == 0 && enc) {
+      enc_encode();
+    } else if (strcmp(t, "ack") == 0 && enc) {
+      int64_t sid = (int64_t)number();
+      int rv = nghttp3_qpack_encoder_ack_header(enc, sid);
+      printf("{\"op\":\"ack\",\"sid\":%" PRId64 ",\"rv\":%d,", sid, rv);
+      put_enc_state();
+      printf("}\n");
+    } else if (strcmp(t, "ackall") == 0 && enc) {
+      nghttp3_qpack_encoder_ack_everything(enc);
+      printf("{\"op\":\"ackall\",");
+      put_enc_state();
+      printf("}\n");
+    } else if (strcmp(t, "estream") == 0 && dec) {
+      size_t len;
+      uint8_t *src = hexbytes(&len);
+      nghttp3_ssize n = nghttp3_qpack_decoder_read_encoder(dec, src, len);
+      printf("{\"op\":\"estream\",\"rv\":%td,", (ptrdiff_t)n);
+      put_dec_state();
+      printf("}\n");
+      free(src);
+    } else if (strcmp(t, "section") == 0 && dec) {
+      dec_section();
+    } else {
+      die("unknown step");
+    }
+  }
+  nghttp3_qpack_encoder_del(enc);
+  nghttp3_qpack_decoder_del(dec);
+  fclose(in);
+  return 0;
+}

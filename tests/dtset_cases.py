@@ -14,6 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 import oracle
+import ref_cases as rc
 from emit_cases import es_cap, es_dup, es_insert, es_insert_ref
 from nghttp3_amd import qpack
 from nghttp3_amd.qpack_huffman import SPAN_IN_DTYPE
@@ -252,6 +253,20 @@ def check_table(got, hard_max, good: bytes):
         ref.close()
 
 
+def check_reference(case, t, pieces, fed, step, got):
+    """One call of one table against the reference library's transcript: its
+    first failing status is the Fail's (else it read every byte it was fed,
+    a Partial included, which it buffers), and the table after the call is
+    the one expected_of's prefix gives, in count, size, capacity and content."""
+    fails = [p for p in pieces if isinstance(p, Fail)]
+    assert step["rv"] == (fails[0].status if fails else len(fed)), (case.name, t, step["rv"])
+    if got is not None:
+        assert (got["insert_count"], got["size"], got["cap"]) == \
+            (step["insert_count"], step["size"], step["cap"]), (case.name, t, got, step)
+        d = rc.table_digest([(n, v) for n, v, _ in got["entries"]])
+        assert (d["n"], d["sha256"][:16]) == (step["n"], step["d"]), (case.name, t, got["entries"])
+
+
 # ---- running a case --------------------------------------------------------------
 
 def calls_of(case):
@@ -272,6 +287,12 @@ def run_case(case, runner, align=False, check=True):
     -> the per-call (src, spans, tsel, status, consumed) for further checks."""
     good = [b""] * len(case.tables)
     log = []
+    # what the reference library did with the same calls (a case this module
+    # lists has a transcript; one a test builds for itself has none)
+    ref = rc.dtset_ref_name(case)
+    cur = None if ref is None else rc.Cursor(ref, len(case.tables), prefix=True)
+    feeds = [rc.dtset_feeds(calls) for _, calls in case.tables]
+    ncall = 0
     for tsel, lists in calls_of(case):
         src, spans = pack_streams([stream_of(p) for p in lists], align=align)
         sel = None if tsel is None else np.array(tsel, np.uint32)
@@ -286,7 +307,16 @@ def run_case(case, runner, align=False, check=True):
             state = runner.state()
             for t, (hm, _) in enumerate(case.tables):
                 check_table(table_state(state, t), hm, good[t])
+        if cur is not None:
+            for p, t in enumerate(tabs):
+                if t >= cur.n:
+                    continue
+                check_reference(case, t, lists[p], feeds[t][ncall], cur.take(t, "estream"),
+                                table_state(state, t) if check else None)
+        ncall += 1
         log.append((src, spans, sel, np.array(status), np.array(consumed)))
+    if cur is not None:
+        cur.done()  # (every recorded call of the covered tables was read)
     return log
 
 

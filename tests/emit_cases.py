@@ -8,6 +8,7 @@ import os
 
 import numpy as np
 
+import ref_cases as rc
 from conftest import GOLDEN
 from nghttp3_amd import _lib, qpack
 from nghttp3_amd.qpack_huffman import SPAN_IN_DTYPE, SPAN_OUT_DTYPE
@@ -113,6 +114,7 @@ class Tables:
 
     def __init__(self, specs):
         """specs: [(hard_max, encoder stream bytes)]"""
+        self.specs = [(int(hm), bytes(stream)) for hm, stream in specs]
         self.oracle, views, ents, byts = [], [], [], []
         e0 = b0 = 0
         for hard_max, stream in specs:
@@ -279,15 +281,115 @@ def verdict_table():
 
 def expected_rows(tabs, rows):
     """-> [(status, ricnt, fields)] per row: the row's own expectation, else
-    the oracle's."""
+    the oracle's; either way it must be what the reference library did with
+    the same section against the same table (check_reference_row: the host
+    and the device tests both take their expectation from here)."""
     out = []
     for _, t, payload, want in rows:
         st, ric, fields = oracle_block(tabs.oracle[t], payload)
         if want is not None:  # (the oracle frames a HEADER_TOO_LARGE block no further)
             assert st in (want, BIG), (st, want)
             st, fields = want, []
+        check_reference_row(tabs.specs[t], payload, st, ric, fields)
         out.append((st, ric, fields))
     return out
+
+
+def check_reference_row(spec, payload, st, ric, fields):
+    """The expectation of one section against the reference library's
+    recorded answer (tests/golden/ref_replay/emit-*.json), in one of its
+    forms: the fields with token and never-index bit plus Required Insert
+    Count and Base, the blocked verdict with the count it waits for, or the
+    negative status.  A section without a recorded answer is an error."""
+    key = rc.emit_key(spec, payload)
+    assert key in rc.emit_index(), "no reference transcript holds this section (%s)" % payload.hex()
+    name, conn = rc.emit_index()[key]
+    steps = rc.load(name)["conns"][conn]
+    assert steps[2]["op"] == "estream" and steps[2]["rv"] == len(spec[1]), steps[2]
+    ref = steps[3]
+    if st == 0:
+        assert (ref["rv"], ref["blocked"], ref["ricnt"]) == (len(payload), 0, ric), (payload.hex(), ref)
+        enc, pos = qf.read_varint(payload, 0, 8)
+        delta, _ = qf.read_varint(payload, pos, 7)
+        assert ref["base"] == (ric - delta - 1 if payload[pos] & 0x80 else ric + delta), (payload.hex(), ref)
+        want = rc.fields_digest([(n, v, qpack.lookup_token(n), nv) for n, v, nv in fields])
+        assert (ref["n"], ref["d"]) == (want["n"], want["sha256"][:16]), (payload.hex(), ref, fields)
+    elif st == BLOCKED:
+        assert (ref["blocked"], ref["ricnt"]) == (1, ric) and ref["rv"] >= 0, (payload.hex(), ref)
+    else:
+        assert ref["rv"] == st, (payload.hex(), ref, st)
+
+
+# ---- the synthetic batches (tests/test_gpu_emit.py's shape sweep) --------------
+
+LENS = (0, 1, 15, 16, 17, 63, 64, 65)
+TEXT = b"abcdefghijklmnopqrstuvwxyz0123456789-_/.=; "
+BINARY = bytes(range(128, 256))  # (never Huffman-coded: longer that way)
+
+
+def rstr(rng, n, binary=False):
+    a = BINARY if binary else TEXT
+    return bytes(a[i] for i in rng.integers(0, len(a), n))
+
+
+def sweep_spec():
+    """Forty inserts into a 64 KiB table, the first ten evicted by a capacity
+    change: entries 10..39 live, names and values of every length of LENS."""
+    rng = np.random.default_rng(40)
+    ins = lambda k: es_insert(rstr(rng, LENS[k % 8]).replace(b" ", b"-") or b"",
+                              rstr(rng, LENS[(k // 8 + k) % 8], binary=k % 3 == 0))
+    stream = b"".join(ins(k) for k in range(10)) + es_cap(0) + es_cap(65536) + \
+        b"".join(ins(k) for k in range(10, 40))
+    return (65536, stream)
+
+
+def sweep_block(rng, nlines, bad=False):
+    """ricnt 40, base 35: base-relative lines reach entries 10..34, post-base
+    ones 35..39; `bad`: one reference to an evicted entry."""
+    out = [prefix(enc_ricnt(40, 2048), 1, 4)]
+    bad_at = int(rng.integers(0, nlines)) if bad and nlines else -1
+    for i in range(nlines):
+        op = int(rng.integers(0, 7))
+        vlen = LENS[int(rng.integers(0, 8))]
+        value = rstr(rng, vlen, binary=bool(rng.integers(0, 2)))
+        never = bool(rng.integers(0, 2))
+        if i == bad_at:
+            out.append(l_dyn(34 - int(rng.integers(0, 10))))  # abs 0..9
+        elif op == 0:
+            out.append(l_static(int(rng.integers(0, 99))))
+        elif op == 1:
+            out.append(l_dyn(int(rng.integers(0, 25))))
+        elif op == 2:
+            out.append(l_pb(int(rng.integers(0, 5))))
+        elif op == 3:
+            out.append(l_name_static(int(rng.integers(0, 99)), value, never))
+        elif op == 4:
+            out.append(l_name_dyn(int(rng.integers(0, 25)), value, never))
+        elif op == 5:
+            out.append(l_name_pb(int(rng.integers(0, 5)), value, never))
+        else:
+            out.append(l_literal(rstr(rng, LENS[int(rng.integers(0, 8))]).replace(b" ", b"-"),
+                                 value, never))
+    return b"".join(out)
+
+
+def sweep_want(tabs, pool):
+    """The expectation of every block of the pool against the sweep table,
+    each one checked against the reference's recorded answer on the way
+    (expected_rows); the pool holds failing blocks of 1, 16, 17 and 33 lines."""
+    want = expected_rows(tabs, [("", 0, payload, None) for payload in pool])
+    assert len(want) == 68 and sum(1 for st, _, _ in want if st == BAD) == 8
+    assert all(st in (0, BAD) for st, _, _ in want)
+    return want
+
+
+def sweep_pool():
+    rng = np.random.default_rng(41)
+    pool = []
+    for nlines in (0, 1, 16, 17, 33):
+        pool += [sweep_block(rng, nlines) for _ in range(12)]
+        pool += [sweep_block(rng, nlines, bad=True) for _ in range(2 if nlines else 0)]
+    return pool
 
 
 def fields_of(e, p, res, src, tabs_bytes=None):

@@ -15,8 +15,11 @@ A case is a list of steps over `n` connections:
                              name a stream that still has unacknowledged
                              sections
   ("ack", k)                 per connection, acknowledge the oldest section of
-                             its k oldest streams (the test applies it to the
-                             scalars between calls)
+                             its k oldest streams (a scalar or one value each;
+                             the test applies it to the scalars between calls)
+Every case has a transcript of the reference library (tests/ref_cases.py,
+tests/golden/ref_replay/<case.ref>.json), which run_case compares the host
+twin with after every step; a case without one is an error.
 Each generator asserts through the model's counters that its target branch
 is taken, so a case cannot silently miss it."""
 import random
@@ -24,6 +27,7 @@ import random
 import numpy as np
 
 import enc_model as em
+import ref_cases as rc
 from nghttp3_amd import qpack
 from oracle import qpack_qif as oq
 
@@ -37,8 +41,9 @@ VALUES = [b"", b"1", b"gzip", b"abc", b"/index.html", b"Mozilla/5.0 (X11)", b"01
 
 class Case:
     def __init__(self, name, n, hard_max, max_blocked=0, immediate=False, strat_none=False,
-                 steps=()):
+                 steps=(), ref=None):
         self.name, self.n, self.hard_max = name, n, hard_max
+        self.ref = ref or name  # the transcript's name
         self.max_blocked, self.immediate, self.strat_none = max_blocked, immediate, strat_none
         self.steps = list(steps)
 
@@ -120,9 +125,10 @@ class Model:
         self.flags_seen.update(flags)
         return np.array(flags, np.uint8)
 
-    def encode(self, call, tsel, sids):
+    def encode(self, call, tsel, sids, states=None):
         """-> per section (bytes, max_cnt, min_cnt), per listed connection the
-        encoder-stream bytes."""
+        encoder-stream bytes.  states: a list that receives the connection's
+        (scalars, table oldest first) after every section."""
         secs_out, streams = [], []
         for p, secs in enumerate(call):
             t = p if tsel is None else int(tsel[p])
@@ -133,13 +139,20 @@ class Model:
                 if self.case.immediate:
                     e.ack_everything()
                 secs_out.append((sec, mx, mn))
+                if states is not None:
+                    states.append((self.scalars(t), [(x[1], x[2]) for x in reversed(e.table)]))
                 es += eb
             streams.append(es)
         return secs_out, streams
 
+    def ack_ids(self, k):
+        """-> per connection the streams an ("ack", k) step acknowledges."""
+        return [sorted(e.streams)[:int(kk)]
+                for e, kk in zip(self.enc, np.broadcast_to(k, (self.case.n,)))]
+
     def ack(self, k):
-        for e in self.enc:
-            for sid in sorted(e.streams)[:k]:
+        for e, sids in zip(self.enc, self.ack_ids(k)):
+            for sid in sids:
                 e.ack_section(sid)
 
     def scalars(self, t):
@@ -186,6 +199,68 @@ def check_state(es, model):
         assert keys.tobytes() == want.tobytes()
 
 
+def check_state_digest(case, t, s, scalars, table):
+    """A transcript step's state digest against scalars (a dict: the model's
+    or, read back from the records, the host twin's) and the table's (name,
+    value) oldest first.  (An encode step before an immediate acknowledgement
+    and the inner steps of a connection of very many carry none.)"""
+    if "st" not in s:
+        return
+    sc = dict(scalars, nlive=scalars["insert_count"] - scalars["live_lo"])
+    got = rc.enc_state_digest([sc[k] for k in rc.SCALARS], table)
+    assert got == s["st"], (case, t, s, scalars, table)
+
+
+def model_state(model, t):
+    return model.scalars(t), [(e[1], e[2]) for e in reversed(model.enc[t].table)]
+
+
+def check_reference_call(case, cur, es, listed, ncalls_secs, sids, r, mstates):
+    """One encode call of the host twin against the reference's transcript:
+    per section the bytes, the counts and its share of the connection's
+    encoder stream (through the rolling digest), then the scalars and the
+    table as the library held them after the connection's last step of the
+    call.  The host twin's state can be read at the end of a call only;
+    mstates (the model's state after every section) is held against the
+    state digest of every section's step, so the sections inside a call are
+    judged too."""
+    views, acct, enc = es.view_records(), es.acct_records(), es.enc_records()
+    entries, dyn_bytes, _ = es.log()
+    b = 0
+    for p, t in enumerate(listed):
+        o, n = int(r["estreams"][p]["off"]), int(r["estreams"][p]["len"])
+        stream, at, last = bytes(r["edst"][o:o + n]), 0, None
+        for k in range(ncalls_secs[p]):
+            s = cur.take(t, "encode")
+            assert (s["sid"], s["rv"]) == (sids[p][k], 0), (case, t, s)
+            o, n = int(r["sections"][b]["off"]), int(r["sections"][b]["len"])
+            mx, mn = int(r["max_cnt"][b]), int(r["min_cnt"][b])
+            cur.chain[t] = rc.chain(cur.chain[t], s["sid"], bytes(r["dst"][o:o + n]),
+                                    stream[at:at + s["eslen"]], mx, mn)
+            if "out" in s:
+                assert cur.chain[t].hex()[:16] == s["out"], \
+                    (case, t, b, bytes(r["dst"][o:o + n]).hex(), stream[at:at + s["eslen"]].hex(), mx, mn)
+            at += s["eslen"]
+            last = cur.take(t, "ackall") if case.immediate else s
+            check_state_digest(case, t, last, *mstates[b])
+            b += 1
+        assert at == len(stream), (case, t)
+        if last is None:
+            continue
+        got = {"insert_count": int(views[t]["insert_count"]), "live_lo": int(views[t]["live_lo"]),
+               "cap": int(acct[t]["cap"]), "size": int(acct[t]["size"]),
+               "krcnt": int(enc[t]["krcnt"]), "pin_min": int(enc[t]["pin_min"]),
+               "nblocked": int(enc[t]["nblocked"]), "nstreams": int(enc[t]["nstreams"]),
+               "pending": int(bool(int(enc[t]["flags"]) & qpack.ENC_CAP_PENDING)),
+               "min_update": int(enc[t]["min_update"]), "last_update": int(enc[t]["last_update"])}
+        tab = []
+        for x in range(got["live_lo"], got["insert_count"]):
+            e = entries[int(views[t]["ent_base"]) + x]
+            tab.append((bytes(dyn_bytes[int(e["name_off"]):int(e["name_off"]) + int(e["name_len"])]),
+                        bytes(dyn_bytes[int(e["value_off"]):int(e["value_off"]) + int(e["value_len"])])))
+        check_state_digest(case, t, last, got, tab)
+
+
 STATE_KEYS = ("lines", "prefixes", "max_cnt", "min_cnt", "sections", "estreams", "status")
 
 
@@ -193,9 +268,15 @@ def run_case(case, dev=None, on_call=None):
     """Drives the model and the host twin (and, with dev = (codec, device),
     the device call) through the case's steps, asserting after every call that
     the host twin's bytes, counts and state are the model's and that the
-    device's outputs and state equal the host twin's byte for byte.
+    device's outputs and state equal the host twin's byte for byte; and
+    that what the reference library did with the same steps (the case's
+    transcript) is what the host twin did: sections, encoder streams, counts,
+    scalars and the table after every encode step, the model's scalars after
+    every other step.
     on_call(host_set, inputs, result): a hook per encode step.  -> the model."""
     model = Model(case)
+    cur = rc.Cursor(case.ref, case.n)
+    asked = [None] * case.n
     sets = [qpack.EncoderSet(case.hard_max, case.n, case.max_blocked, case.immediate,
                              strat_none=case.strat_none)]
     if dev is not None:
@@ -208,17 +289,30 @@ def run_case(case, dev=None, on_call=None):
             model.set_capacity(step[1])
             for s in sets:
                 s.set_capacity(step[1])
+            for t, cap in enumerate(np.broadcast_to(step[1], (case.n,))):
+                if asked[t] != int(cap):  # (a capacity asked for again is not in the transcript)
+                    asked[t] = int(cap)
+                    check_state_digest(case, t, cur.take(t, "cap"), *model_state(model, t))
         elif step[0] == "ack":
+            acked = model.ack_ids(step[1])
             model.ack(step[1])
             for s in sets:
                 set_scalars(s, model)
+            for t in range(case.n):
+                last = None
+                for sid in acked[t]:
+                    last = cur.take(t, "ack")
+                    assert (last["sid"], last["rv"]) == (sid, 0), (case, t, last)
+                if last is not None:
+                    check_state_digest(case, t, last, *model_state(model, t))
         else:
             call = step[1]
             tsel = None if len(step) < 3 or step[2] is None else np.asarray(step[2], np.uint32)
             plain, strs, fs, cs, nv = pack(call)
             sids = model.stream_ids(call, tsel, step[3] if len(step) > 3 else None)
             sf = model.sec_flags(call, tsel, sids)
-            want_secs, want_streams = model.encode(call, tsel, sids)
+            mstates = []
+            want_secs, want_streams = model.encode(call, tsel, sids, mstates)
             r = sets[0].encode(plain, strs, fs, cs, nvflags=nv, sec_flags=sf, tsel=tsel)
             assert (r["status"] == 0).all()
             for b, (sec, mx, mn) in enumerate(want_secs):
@@ -231,6 +325,8 @@ def run_case(case, dev=None, on_call=None):
             assert r["needs"][2] == sum(len(s[0]) for s in want_secs)
             assert r["needs"][3] == sum(len(s) for s in want_streams)
             check_state(sets[0], model)
+            check_reference_call(case, cur, sets[0], range(case.n) if tsel is None else [int(x) for x in tsel],
+                                 [len(secs) for secs in call], sids, r, mstates)
             if on_call is not None:
                 on_call(sets[0], (plain, strs, fs, cs, nv, sf, tsel), r)
             if dev is not None:
@@ -246,6 +342,7 @@ def run_case(case, dev=None, on_call=None):
                 assert d["dst"][:d["needs"][2]].tobytes() == r["dst"][:r["needs"][2]].tobytes()
                 assert d["edst"][:d["needs"][3]].tobytes() == r["edst"][:r["needs"][3]].tobytes()
                 same_state(sets[0], sets[1])
+    cur.done()
     return model
 
 
@@ -328,7 +425,8 @@ def corpus_case(copies=1, per_call=None):
     steps = [("cap", 256)]
     for k in range(0, len(blocks), per_call):
         steps.append(("encode", [blocks[k:k + per_call]] * copies))
-    return Case("corpus-x%d" % copies, copies, 256, 100, True, strat_none=True, steps=steps)
+    return Case("corpus-x%d" % copies, copies, 256, 100, True, strat_none=True, steps=steps,
+                ref="corpus")  # (one connection recorded, every copy compared with it)
 
 
 def dedicated_cases():
@@ -437,3 +535,112 @@ def collision_case():
     first = [[(n0, v0, 0)], [(n1, v0, 0)], [(n0, v1, 0)], [(n1, v1, 0)]]
     return Case("collisions", 1, 4096, 100, True,
                 steps=[("cap", 4096), ("encode", [first + first])])
+
+
+def tsel_case():
+    """Five connections listed in descending order, then two subsets."""
+    conns = pool_sections(7, nconns=5, nsec=4)
+    steps = [("cap", 256), ("encode", conns[::-1], [4, 3, 2, 1, 0]),
+             ("encode", [conns[1], conns[3]], [3, 1]), ("encode", [conns[0]], [2])]
+    return Case("tsel", 5, 256, 4, True, steps=steps)
+
+
+# ---- the walk: cases only the reference can answer ---------------------------
+
+WALK_SEEDS = (0x3A01, 0x3A02, 0x3A03, 0x3A04, 0x3A05, 0x3A06, 0x3A07, 0x3A08)
+WALK_HARD_MAX = (0, 64, 128, 256, 4096)
+WALK_NAMES = NAMES + [b"te", b":protocol", b"priority", b"connection", b"upgrade"]  # ("host" is in NAMES)
+WALK_CONNS, WALK_ROUNDS, WALK_FIELDS = 17, 12, 8
+# what the eight groups together must reach (asserted through the model's
+# counters by check_walk_coverage, so the walk cannot quietly go shallow)
+WALK_REQUIRED = ("insert_literal", "insert_dynamic_name", "insert_static_name", "duplicate", "add_evict",
+                 "can_index_pinned_oldest", "can_index_no_room", "pb_suppressed", "never_name_only",
+                 "three_quarters", "shrink_evict", "set_cap", "dynamic_name_ref", "prefix_sign")
+WALK_CLOSURE = 3  # the group whose recorded bytes also go through the decoding kernels
+
+
+def walk_group(g):
+    """-> (max_blocked, immediate, strat_none) of group g: the per-set
+    settings; every max_blocked with and without immediate acknowledgement,
+    each strategy under both."""
+    return (0, 1, 2, 100)[g % 4], bool(g >> 2), bool((g + (g >> 2)) & 1)
+
+
+def walk_case(g):
+    """A seeded walk of WALK_CONNS connections (more than a 16-lane group),
+    their hard maxima swept over WALK_HARD_MAX, each of at most WALK_ROUNDS
+    sections of at most WALK_FIELDS fields.  Nothing here consults the model:
+    the expected bytes exist only in the reference's transcript.  Before a
+    section the capacity may change (to 0, to a fraction of the hard maximum,
+    which may lie below the current size, or back to the hard maximum); a
+    third of the fields are drawn from three of the connection's own; the
+    section goes on a fresh stream or on the previous section's, which may
+    still be open; after it the oldest open stream may be acknowledged."""
+    seed = WALK_SEEDS[g]
+    max_blocked, immediate, strat_none = walk_group(g)
+    hard_max = [WALK_HARD_MAX[t % len(WALK_HARD_MAX)] for t in range(WALK_CONNS)]
+    plans = []
+    for t in range(WALK_CONNS):
+        rng = random.Random(seed * 1000 + t)
+        names = WALK_NAMES + [b"x-long-" + b"n" * (rng.choice((127, 128, 129)) - 7)]
+        values = VALUES + [b"w" * rng.choice((255, 256, 257))]
+        # three fields of the connection's own that come back (a repeated
+        # field is what finds an entry again, near the table's old end too)
+        own = [(rng.choice(names[:-1]), rng.choice(values[:-1])) for _ in range(3)]
+        cap, sid, rounds = hard_max[t], 0, []
+        for r in range(rng.randint(WALK_ROUNDS // 2, WALK_ROUNDS)):
+            u = rng.random()
+            if r and u < 0.4:
+                cap = rng.choice((0, hard_max[t] // 4, hard_max[t] // 2, hard_max[t]))
+            if not (r and rng.random() < 0.25):
+                sid += 1
+            fields = []
+            for _ in range(rng.randint(1, WALK_FIELDS)):
+                u = rng.random()
+                fl = em.NV_NEVER if u < 0.15 else em.NV_TRY if u < 0.45 else 0
+                name, value = rng.choice(own) if rng.random() < 0.35 else (rng.choice(names), rng.choice(values))
+                fields.append((name, value, fl))
+            rounds.append((cap, sid, fields, int(rng.random() < 0.5)))
+        plans.append(rounds)
+    steps = []
+    for r in range(WALK_ROUNDS):
+        live = [p[r] if r < len(p) else None for p in plans]
+        steps.append(("cap", [x[0] if x else plans[t][-1][0] for t, x in enumerate(live)]))
+        steps.append(("encode", [[x[2]] if x else [] for x in live], None,
+                      [[x[1]] if x else [] for x in live]))
+        steps.append(("ack", [x[3] if x else 0 for x in live]))
+    return Case("walk-%d" % g, WALK_CONNS, hard_max, max_blocked, immediate, strat_none, steps=steps)
+
+
+def check_walk_coverage(models):
+    c = em.Counter()
+    for m in models:
+        c.update(m.counts())
+    for k in WALK_REQUIRED:
+        assert c[k] > 0, (k, dict(c))
+
+
+def recorded_rounds(case):
+    """The reference-recorded bytes of a walk case, a round at a time: ->
+    [(encoder stream per connection (b"" where it has no section), listed
+    connections, their recorded sections, their input fields)].  The case's
+    transcript keeps every byte."""
+    tr = rc.load(case.ref)
+    enc_steps = [[s for s in tr["conns"][c] if s["op"] == "encode"] for c in tr["conn_of"]]
+    at = [0] * case.n
+    out = []
+    for step in case.steps:
+        if step[0] != "encode":
+            continue
+        streams, listed, secs, fields = [b""] * case.n, [], [], []
+        for t, sections in enumerate(step[1]):
+            for f in sections:  # (a walk has at most one)
+                s = enc_steps[t][at[t]]
+                at[t] += 1
+                streams[t] += bytes.fromhex(s["es"])
+                listed.append(t)
+                secs.append(bytes.fromhex(s["sec"]))
+                fields.append([(n, v) for n, v, _ in f])
+        out.append((streams, listed, secs, fields))
+    assert at == [len(s) for s in enc_steps]
+    return out

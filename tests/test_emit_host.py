@@ -153,6 +153,19 @@ def test_a_view_stays_valid_after_later_inserts():
     assert [f[:2] for f in ec.fields_of(e, 0, None, None)] == [(b"k2", b"v2"), (b"k0", b"v0")]
 
 
+def test_sweep_pool_against_the_reference():
+    """Every block of the synthetic pool (tests/test_gpu_emit.py's shape
+    sweep) through the host twin: status, Required Insert Count and fields
+    are the expectation's, which expected_rows holds against the reference
+    library's recorded answer for each of the 68 sections."""
+    pool, t = ec.sweep_pool(), ec.Tables([ec.sweep_spec()])
+    want = ec.sweep_want(t, pool)
+    src, blocks = ec.pack_blocks(pool, pad=5)
+    e = host_emit(ec.host_sections(src, blocks), src, blocks, views=t.views, entries=t.entries,
+                  dyn_bytes=t.bytes)
+    ec.check_against_expected(e, want)
+
+
 @pytest.fixture(scope="module")
 def table_case():
     tabs, rows = ec.verdict_table()

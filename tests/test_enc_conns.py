@@ -2,7 +2,9 @@
 tests/enc_model.py against the reference's corpus file, the host twin
 qh_qpack_encode_conns against the model on every case of tests/enc_cases.py
 (bytes, counts, state, the log's content and keys; multi-call sequences with
-the acknowledgements applied between calls), the log-equality property
+the acknowledgements applied between calls; every case also against the
+reference library's transcript, tests/ref_cases.py, and the seeded walks
+against nothing else), the log-equality property
 against qh_qpack_dtables_apply, the round trip through the model decoder,
 QH_ERR_NOMEM at each of the four caps, bad arguments, and the host function
 under AddressSanitizer and UBSan in a process of its own
@@ -119,10 +121,58 @@ def test_name_collisions():
 
 
 def test_tsel_descending_and_subset():
-    conns = ec.pool_sections(7, nconns=5, nsec=4)
-    steps = [("cap", 256), ("encode", conns[::-1], [4, 3, 2, 1, 0]),
-             ("encode", [conns[1], conns[3]], [3, 1]), ("encode", [conns[0]], [2])]
-    ec.run_case(ec.Case("tsel", 5, 256, 4, True, steps=steps))
+    ec.run_case(ec.tsel_case())
+
+
+_walk_models = {}
+
+
+@pytest.mark.parametrize("g", range(len(ec.WALK_SEEDS)))
+def test_walk_against_the_reference(g):
+    """A seeded walk whose expected bytes exist only in the reference
+    library's transcript: the host twin equals it step by step (and the model
+    equals the host twin)."""
+    _walk_models[g] = ec.run_case(ec.walk_case(g))
+
+
+def test_walk_coverage():
+    """The eight groups together reach every branch of WALK_REQUIRED, and
+    sections on known and on blocked streams."""
+    models = [_walk_models.get(g) or ec.run_case(ec.walk_case(g)) for g in range(len(ec.WALK_SEEDS))]
+    ec.check_walk_coverage(models)
+    seen = set().union(*(m.flags_seen for m in models))
+    known, blocked = qpack.ENC_SEC_STREAM_KNOWN, qpack.ENC_SEC_STREAM_BLOCKED
+    assert {0, known, known | blocked} <= seen
+
+
+def test_closure_over_reference_recorded_bytes():
+    """Encoder output this project did not write: the reference library's
+    recorded encoder streams through qh_qpack_dtables_apply and its recorded
+    sections through qh_qpack_emit_fields, round by round, give back the
+    input fields."""
+    import dtset_cases as dc
+    import emit_cases as mc
+    case = ec.walk_case(ec.WALK_CLOSURE)
+    ts = DynamicTableSet(list(case.hard_max), case.n)
+    nsec = 0
+    for streams, listed, secs, fields in ec.recorded_rounds(case):
+        src, spans = dc.pack_streams(streams)
+        st, co = ts.read_encoder(src, spans)
+        assert not st.any() and list(co) == [len(x) for x in streams]
+        if not listed:
+            continue
+        data, blocks = mc.pack_blocks(secs)
+        res = mc.host_sections(data, blocks)
+        assert not res["status"].any()
+        e = qpack.FieldSectionDecoder.emit_fields(
+            res, data, blocks, views=ts.views.view(qpack.VIEW_DTYPE), block_view=np.array(listed, np.uint32),
+            entries=ts.entries[:ts.nentries * 32].view(qpack.DYN_ENTRY_DTYPE),
+            dyn_bytes=ts.dyn_bytes[:ts.nbytes], materialise=True)
+        assert not e["status"].any() and e["nblocked"] == 0
+        assert e["field_start"].tolist() == np.cumsum([0] + [len(f) for f in fields]).tolist()
+        assert e["out"].tobytes() == b"".join(n + v for f in fields for n, v in f)
+        nsec += len(listed)
+    assert nsec > 8 * case.n
 
 
 def _copy_into_table_set(es):

@@ -139,73 +139,30 @@ def test_verdict_table_on_the_device(fsd, packed):
 
 # ---- synthetic batches ------------------------------------------------------
 
-LENS = (0, 1, 15, 16, 17, 63, 64, 65)
-TEXT = b"abcdefghijklmnopqrstuvwxyz0123456789-_/.=; "
-BINARY = bytes(range(128, 256))  # (never Huffman-coded: longer that way)
-
-
-def rstr(rng, n, binary=False):
-    a = BINARY if binary else TEXT
-    return bytes(a[i] for i in rng.integers(0, len(a), n))
+rstr = ec.rstr  # (the builders live in emit_cases, where the reference's replay reaches them)
 
 
 @pytest.fixture(scope="module")
 def sweep_table():
-    """Forty inserts into a 64 KiB table, the first ten evicted by a capacity
-    change: entries 10..39 live, names and values of every length of LENS."""
-    rng = np.random.default_rng(40)
-    ins = lambda k: ec.es_insert(rstr(rng, LENS[k % 8]).replace(b" ", b"-") or b"",
-                                 rstr(rng, LENS[(k // 8 + k) % 8], binary=k % 3 == 0))
-    stream = b"".join(ins(k) for k in range(10)) + ec.es_cap(0) + ec.es_cap(65536) + \
-        b"".join(ins(k) for k in range(10, 40))
-    tabs = ec.Tables([(65536, stream)])
+    tabs = ec.Tables([ec.sweep_spec()])
     v = tabs.views[0]
     assert (int(v["insert_count"]), int(v["live_lo"]), int(v["max_entries"])) == (40, 10, 2048)
     return tabs
 
 
-def sweep_block(rng, nlines, bad=False):
-    """ricnt 40, base 35: base-relative lines reach entries 10..34, post-base
-    ones 35..39; `bad`: one reference to an evicted entry."""
-    out = [ec.prefix(ec.enc_ricnt(40, 2048), 1, 4)]
-    bad_at = int(rng.integers(0, nlines)) if bad and nlines else -1
-    for i in range(nlines):
-        op = int(rng.integers(0, 7))
-        vlen = LENS[int(rng.integers(0, 8))]
-        value = rstr(rng, vlen, binary=bool(rng.integers(0, 2)))
-        never = bool(rng.integers(0, 2))
-        if i == bad_at:
-            out.append(ec.l_dyn(34 - int(rng.integers(0, 10))))  # abs 0..9
-        elif op == 0:
-            out.append(ec.l_static(int(rng.integers(0, 99))))
-        elif op == 1:
-            out.append(ec.l_dyn(int(rng.integers(0, 25))))
-        elif op == 2:
-            out.append(ec.l_pb(int(rng.integers(0, 5))))
-        elif op == 3:
-            out.append(ec.l_name_static(int(rng.integers(0, 99)), value, never))
-        elif op == 4:
-            out.append(ec.l_name_dyn(int(rng.integers(0, 25)), value, never))
-        elif op == 5:
-            out.append(ec.l_name_pb(int(rng.integers(0, 5)), value, never))
-        else:
-            out.append(ec.l_literal(rstr(rng, LENS[int(rng.integers(0, 8))]).replace(b" ", b"-"),
-                                    value, never))
-    return b"".join(out)
+@pytest.fixture(scope="module")
+def sweep_pool():
+    return ec.sweep_pool()
 
 
 @pytest.fixture(scope="module")
-def sweep_pool():
-    rng = np.random.default_rng(41)
-    pool = []
-    for nlines in (0, 1, 16, 17, 33):
-        pool += [sweep_block(rng, nlines) for _ in range(12)]
-        pool += [sweep_block(rng, nlines, bad=True) for _ in range(2 if nlines else 0)]
-    return pool
+def sweep_want(sweep_table, sweep_pool):
+    """Per pool block the expectation, held against the reference's recorded answer."""
+    return ec.sweep_want(sweep_table, sweep_pool)
 
 
 @pytest.mark.parametrize("nblocks", [0, 1, 15, 16, 17, 2049, 4097])
-def test_shape_sweep(fsd, sweep_table, sweep_pool, nblocks):
+def test_shape_sweep(fsd, sweep_table, sweep_pool, sweep_want, nblocks):
     rng = np.random.default_rng(nblocks)
     t = sweep_table
     kw = dict(views=t.views, entries=t.entries, dyn_bytes=t.bytes)
@@ -227,9 +184,10 @@ def test_shape_sweep(fsd, sweep_table, sweep_pool, nblocks):
         same(dev_emit(fsd, res, src, blocks, qif=True, **kw), h)
     if nblocks >= len(sweep_pool):
         assert set(int(x) for x in h["status"]) == {0, ec.BAD} and h["nfields"] > 0
-    if nblocks == 1:  # the oracle's answer, once
-        want = ec.expected_rows(t, [("", 0, sweep_pool[int(pick[0])], None)])
-        ec.check_against_expected(host_emit(fsd, res, src, blocks, **kw), want)
+    if nblocks <= 17:  # the reference's answer for every block of the batch, on both paths
+        want = [sweep_want[int(k)] for k in pick]
+        ec.check_against_expected(h, want)
+        ec.check_against_expected(dev_emit(fsd, res, src, blocks, **kw), want)
 
 
 def test_every_source_against_every_destination_alignment(fsd, codec):
@@ -290,7 +248,7 @@ def test_wave_copy_path(fsd, codec, long_min):
     assert len(f2) == 65 and all(x[:2] == (b"x-big", big_entry) for x in f2[:64])
 
 
-def test_bytes_past_the_totals_stay_unwritten(fsd, sweep_table, sweep_pool):
+def test_bytes_past_the_totals_stay_unwritten(fsd, sweep_table, sweep_pool, sweep_want):
     import torch
     src, blocks = ec.pack_blocks(sweep_pool, pad=2)
     res = sections_dev(fsd, src, blocks)
@@ -305,6 +263,8 @@ def test_bytes_past_the_totals_stay_unwritten(fsd, sweep_table, sweep_pool):
         b["fields"].fill_(PATTERN)
         d = dev_emit(fsd, res, src, blocks, qif=qif, bufs=b, **kw)
         same(d, h)
+        if not qif:  # the whole pool, in order: the reference's answer for each of its sections
+            ec.check_against_expected(d, sweep_want)
         out = d["_bufs"]["out"].cpu().numpy()
         fields = d["_bufs"]["fields"].cpu().numpy()
         assert out.size == h["out_need"] + 100 and (out[h["out_need"]:] == PATTERN).all()

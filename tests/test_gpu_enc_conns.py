@@ -79,10 +79,15 @@ def test_corpus_three_calls_relocate(codec):
 
 
 def test_tsel_descending_and_subset(codec):
-    conns = ec.pool_sections(7, nconns=5, nsec=4)
-    steps = [("cap", 256), ("encode", conns[::-1], [4, 3, 2, 1, 0]),
-             ("encode", [conns[1], conns[3]], [3, 1]), ("encode", [conns[0]], [2])]
-    ec.run_case(ec.Case("tsel", 5, 256, 4, True, steps=steps), dev=(codec, 0))
+    ec.run_case(ec.tsel_case(), dev=(codec, 0))
+
+
+@pytest.mark.parametrize("g", range(len(ec.WALK_SEEDS)))
+def test_walk_against_the_reference(codec, g):
+    """The seeded walk (17 connections, at most 12 sections each): the device
+    equals the host twin byte for byte, and the host twin the reference
+    library's transcript."""
+    ec.run_case(ec.walk_case(g), dev=(codec, 0))
 
 
 def test_no_connections(codec):
@@ -225,3 +230,40 @@ def test_closure_on_the_device(codec):
     assert e["field_start"].cpu().numpy()[:nb + 1].view(np.uint32).tolist() == fs.tolist()
     want = b"".join(n + v for secs in conns for fields in secs for n, v, _ in fields)
     assert e["out"].cpu().numpy()[:e["out_need"]].tobytes() == want
+
+
+def test_closure_over_reference_recorded_bytes(codec):
+    """Encoder output this project did not write: the reference library's
+    recorded encoder streams (tests/golden/ref_replay/) through
+    qh_dtables_apply_batch and its recorded sections through
+    qh_decode_sections_batch + qh_emit_fields_batch, round by round, give
+    back the input fields."""
+    import torch
+    import dtset_cases as dc
+    import emit_cases as mc
+    case = ec.walk_case(ec.WALK_CLOSURE)
+    tset = DynamicTableSet(list(case.hard_max), case.n, codec)
+    fsd = qpack.FieldSectionDecoder(codec=codec)
+    nsec = 0
+    for streams, listed, secs, fields in ec.recorded_rounds(case):
+        src, spans = dc.pack_streams(streams)
+        st, co = tset.read_encoder_dev(_t(src), _t(spans, torch.int64).reshape(-1, 2))
+        codec.sync()
+        assert not st.cpu().numpy().any()
+        assert list(co.cpu().numpy()) == [len(x) for x in streams]
+        if not listed:
+            continue
+        data, blocks = mc.pack_blocks(secs)
+        d_src, d_blocks = _t(np.frombuffer(data, np.uint8)), _t(blocks, torch.int64).reshape(-1, 2)
+        res = fsd.decode_blocks_dev(d_src, d_blocks, packed=True, prefixes=True)
+        e = fsd.emit_fields_dev(res, d_src, d_blocks, views=tset.views,
+                                block_view=_t(np.array(listed, np.uint32), torch.int32),
+                                entries=tset.entries, dyn_bytes=tset.dyn_bytes, materialise=True)
+        codec.sync()
+        nb = len(listed)
+        assert not e["status"].cpu().numpy()[:nb].any() and e["nblocked"] == 0
+        assert e["field_start"].cpu().numpy()[:nb + 1].view(np.uint32).tolist() == \
+            np.cumsum([0] + [len(f) for f in fields]).tolist()
+        assert e["out"].cpu().numpy()[:e["out_need"]].tobytes() == b"".join(n + v for f in fields for n, v in f)
+        nsec += nb
+    assert nsec > 8 * case.n
