@@ -1099,10 +1099,13 @@ QH_EXPORT int qh_encode_fields_dyn_batch(
  * A connection is three records in caller-owned arrays over the shared log
  * of qh_qpack_dtables_apply: views[t], acct[t] (acct.cap is the encoder's
  * ctx.max_dtable_capacity) and enc[t].  There is no library object.
- * Acknowledgement bookkeeping stays the caller's (per-stream reference
+ * Acknowledgement bookkeeping is outside this call (per-stream reference
  * queues, ack_header, add_icnt, cancel_stream, the decoder-stream parser):
- * between calls it updates krcnt, pin_min, nblocked and nstreams from the
- * max_cnt / min_cnt a call returns, and per section it passes sec_flags.
+ * qh_enc_sec_flags_batch, qh_enc_refs_record_batch and
+ * qh_enc_read_decoder_batch (below) do it over a reference log in HBM.  A
+ * caller that keeps its own queues instead updates, between calls, krcnt,
+ * pin_min, nblocked and nstreams from the max_cnt / min_cnt a call returns,
+ * and per section it passes sec_flags.
  * Inside one call a connection's sections must belong to distinct streams
  * (otherwise split the call).  After a section with max_cnt > 0: pin_min =
  * min(pin_min, min_cnt), nstreams += !KNOWN, nblocked += (max_cnt > krcnt &&
@@ -1209,6 +1212,160 @@ QH_EXPORT int qh_encode_conns_batch(
     uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
     uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
     int where);
+
+/* ---- Acknowledgements: the decoder stream read and written per batch -----
+ * The encoder's side of nghttp3_qpack_encoder_read_decoder (qpack.c:2545-2641)
+ * with ack_header (:2329-2372), add_icnt (:2374-2383), cancel_stream
+ * (:2395-2412) and unblock (:2314-2327), the reference list of
+ * qpack_encoder_add_stream_ref (:1024-1074) as the tail of encoder_encode
+ * keeps it (:1183-1199), and the decoder's side:
+ * nghttp3_qpack_decoder_write_section_ack (:3813-3839), write_decoder
+ * (:3859-3887), decoder_cancel_stream (:3889-3913) and the acknowledgement at
+ * the end of read_request (:3790-3795).
+ *
+ * State: connection t's unacknowledged sections are refs[rv[t].base, +
+ * rv[t].n), oldest first, in one caller-owned log refs[0, *nrefs) of capacity
+ * refs_cap; rv[] is a caller-owned array beside views, acct and enc.  dlen is
+ * uninterrupted_decoderlen.  A fresh connection is all zeros.  There is no
+ * library object.  Layout rules, the same on host and device:
+ *   - a connection that gains references in a call moves: its references are
+ *     copied in order to the cursor (*nrefs on entry, then past each moved
+ *     connection in list order) and the new ones follow;
+ *   - removal never moves a connection: its region is compacted in place,
+ *     order kept, and n shrinks;
+ *   - QH_ERR_NOMEM when refs_cap is too small: *nrefs is then the exact need
+ *     and nothing is written;
+ *   - qh_qpack_enc_refs_compact copies every listed connection's references
+ *     back to back, in list order, into a fresh log (rv rebased), so the
+ *     regions left behind are given back.  When to compact is the caller's
+ *     decision, as for the dynamic-table log.
+ * The derived scalars of qh_enc_state: pin_min is the smallest min_cnt left
+ * (UINT64_MAX for none), nstreams the distinct stream ids left, nblocked the
+ * distinct streams whose largest max_cnt exceeds krcnt. */
+#define QH_ERR_QPACK_DECODER_STREAM_ERROR (-403) /* nghttp3.h:266 */
+typedef struct qh_enc_ref { uint64_t stream_id, max_cnt, min_cnt, reserved; } qh_enc_ref;   /* 32 B */
+typedef struct qh_enc_refs { uint64_t base, n, dlen, flags; } qh_enc_refs;                   /* 32 B */
+#define QH_ENC_REFS_BAD 0x1u /* ctx.bad after a decoder-stream error */
+
+QH_EXPORT void qh_enc_refs_init(qh_enc_refs *rv);
+
+/* Before an encode: sec_flags[b] of section b on stream sec_sid[b], from the
+ * state on entry (conn_start, nconns, tsel, ntables as qh_qpack_encode_conns
+ * takes them): QH_ENC_SEC_STREAM_KNOWN iff a reference of the connection has
+ * that stream id, QH_ENC_SEC_STREAM_BLOCKED iff moreover the largest max_cnt
+ * of those references exceeds krcnt (:1165-1167).  status[c]: 0, or
+ * QH_ERR_INVALID_ARGUMENT (and flags 0) for a connection that lists one
+ * stream twice or whose rv region leaves refs[0, nrefs).  A table named
+ * twice, or an index >= ntables: the call returns QH_ERR_INVALID_ARGUMENT.
+ * The device call is asynchronous on the context stream, no host wait (the
+ * table list is in HBM: a connection whose index is out of range, or whose
+ * table another listed connection has claimed, gets status
+ * QH_ERR_INVALID_ARGUMENT and flags 0 there instead). */
+QH_EXPORT int qh_qpack_enc_sec_flags(
+    const uint64_t *sec_sid, size_t nsections, const uint32_t *conn_start, size_t nconns,
+    const uint32_t *tsel, size_t ntables, const qh_enc_state *enc, const qh_enc_refs *rv,
+    const qh_enc_ref *refs, uint64_t nrefs, uint8_t *sec_flags, int32_t *status);
+QH_EXPORT int qh_enc_sec_flags_batch(
+    qh_ctx *ctx, const uint64_t *sec_sid, size_t nsections, const uint32_t *conn_start,
+    size_t nconns, const uint32_t *tsel, size_t ntables, const qh_enc_state *enc,
+    const qh_enc_refs *rv, const qh_enc_ref *refs, uint64_t nrefs, uint8_t *sec_flags,
+    int32_t *status, int where);
+
+/* After an encode, with its max_cnt, min_cnt and status: a listed connection
+ * whose encode status is 0 gets dlen = 0 when it has at least one section
+ * (:1186) and, unless enc has QH_ENC_IMMEDIATE_ACK, one reference {sid,
+ * max_cnt, min_cnt, 0} per section with max_cnt > 0, in section order
+ * (:1188-1194); it then moves as the layout rule says.  enc is only read
+ * (the encode call has moved its scalars).  A table list error or an rv
+ * region outside refs[0, *nrefs): QH_ERR_INVALID_ARGUMENT, nothing written.
+ * The device call: a count pass, a scan, a flat copy over output records, one
+ * host wait (the total against refs_cap). */
+QH_EXPORT int qh_qpack_enc_refs_record(
+    const uint64_t *sec_sid, size_t nsections, const uint32_t *conn_start, size_t nconns,
+    const uint32_t *tsel, size_t ntables, const uint64_t *max_cnt, const uint64_t *min_cnt,
+    const int32_t *enc_status, const qh_enc_state *enc, qh_enc_refs *rv, qh_enc_ref *refs,
+    uint64_t *nrefs, uint64_t refs_cap);
+QH_EXPORT int qh_enc_refs_record_batch(
+    qh_ctx *ctx, const uint64_t *sec_sid, size_t nsections, const uint32_t *conn_start,
+    size_t nconns, const uint32_t *tsel, size_t ntables, const uint64_t *max_cnt,
+    const uint64_t *min_cnt, const int32_t *enc_status, const qh_enc_state *enc, qh_enc_refs *rv,
+    qh_enc_ref *refs, uint64_t *nrefs, uint64_t refs_cap, int where);
+
+/* The references of the listed connections (tsel NULL: all ntables, in
+ * order) copied to refs_out[0, *nrefs_out), rv[].base rewritten.  On
+ * QH_ERR_NOMEM *nrefs_out is the need and rv is untouched. */
+QH_EXPORT int qh_qpack_enc_refs_compact(
+    const uint32_t *tsel, size_t nconns, size_t ntables, qh_enc_refs *rv, const qh_enc_ref *refs,
+    uint64_t nrefs, qh_enc_ref *refs_out, uint64_t *nrefs_out, uint64_t refs_out_cap);
+QH_EXPORT int qh_enc_refs_compact_batch(
+    qh_ctx *ctx, const uint32_t *tsel, size_t nconns, size_t ntables, qh_enc_refs *rv,
+    const qh_enc_ref *refs, uint64_t nrefs, qh_enc_ref *refs_out, uint64_t *nrefs_out,
+    uint64_t refs_out_cap, int where);
+
+/* Decoder streams read: stream p is src[streams[p].off, + len) for
+ * connection tsel[p] (NULL: p), the conventions those of
+ * qh_qpack_dtables_apply: instructions applied in order, a trailing partial
+ * instruction not consumed (hand the rest in again with what follows), the
+ * first failing instruction sets status[p], the ones before it stay applied
+ * and consumed[p] ends before it.  views is read for insert_count.
+ * Per stream: QH_ENC_REFS_BAD set gives QH_ERR_QPACK_FATAL, nothing consumed
+ * (:2553); length 0 gives 0; dlen + len > 4096 gives -403, nothing consumed,
+ * dlen += len and BAD not set (:2561-2564 returns without marking the
+ * context: the condition lasts until the next encode resets dlen); else dlen
+ * += consumed.  Opcodes (:2571-2589): 1xxxxxxx Section Acknowledgment, 7-bit
+ * prefix; 01xxxxxx Stream Cancellation, 6-bit; 00xxxxxx Insert Count
+ * Increment, 6-bit; an integer overflow gives -403 and BAD.
+ * Increment n: -403 and BAD when n == 0 or insert_count - krcnt < n, else
+ * krcnt += n.  Acknowledgment sid: -403 and BAD when the connection has no
+ * reference of that stream, else its oldest one is removed and krcnt =
+ * max(krcnt, its max_cnt).  Cancellation sid: every reference of the stream
+ * is removed; an unknown stream is no error.  Then pin_min, nstreams and
+ * nblocked are recomputed.  A stream whose rv region leaves refs[0, nrefs)
+ * gets QH_ERR_INVALID_ARGUMENT and is not touched.  A table named twice, or
+ * an index >= ntables: the host call returns QH_ERR_INVALID_ARGUMENT and
+ * nothing is written.  The device call (a 16-lane group per stream) is
+ * asynchronous, no host wait: nothing grows; its table list is in HBM, so a
+ * stream whose index is out of range, or whose table another listed stream
+ * has claimed, gets status QH_ERR_INVALID_ARGUMENT there and is not applied. */
+QH_EXPORT int qh_qpack_enc_read_decoder(
+    const uint8_t *src, const qh_span_in *streams, const uint32_t *tsel, size_t nsel,
+    size_t ntables, const qh_dtable_view *views, qh_enc_state *enc, qh_enc_refs *rv,
+    qh_enc_ref *refs, uint64_t nrefs, int32_t *status, uint32_t *consumed);
+QH_EXPORT int qh_enc_read_decoder_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *streams, const uint32_t *tsel, size_t nsel,
+    size_t ntables, const qh_dtable_view *views, qh_enc_state *enc, qh_enc_refs *rv,
+    qh_enc_ref *refs, uint64_t nrefs, int32_t *status, uint32_t *consumed, int where);
+
+/* Decoder streams written, from a finished qh_emit_fields_batch: per emitted
+ * block its stream id block_sid[], its table block_view[] and status[] /
+ * ricnt[] as emit wrote them; cancel_sid[] / cancel_view[]: cancelled
+ * streams; views for insert_count; written_icnt[ntables] in/out.  The blocks
+ * of one table must be consecutive in the list, and so its cancellations
+ * (else QH_ERR_INVALID_ARGUMENT, as for a table index >= ntables).
+ * dstreams[t] is table t's span of dst (tables in index order, back to back,
+ * length 0 when nothing is written), in this order:
+ *   1. a Section Acknowledgment (0x80, 7-bit prefix) per block with status 0
+ *      and ricnt > 0, in list order, written_icnt = max(written_icnt, ricnt);
+ *   2. a Stream Cancellation (0x40, 6-bit prefix) per listed stream;
+ *   3. if written_icnt < insert_count an Insert Count Increment (0x00, 6-bit)
+ *      of the difference, written_icnt = insert_count.
+ * The reference writes acknowledgements and cancellations in call order and
+ * the increment last; this fixed order is the batch's definition (a caller
+ * that needs another splits the call).  QH_ERR_NOMEM with *dst_need exact
+ * when dst_cap is short; written_icnt is then untouched.  The reference's
+ * limit on its internal buffer (qpack_decoder_dbuf_overflow) is not
+ * restated: the caller owns dst.  The device call: a size pass, scans, a
+ * write pass, one host wait for the total. */
+QH_EXPORT int qh_qpack_dec_write_decoder(
+    const uint64_t *block_sid, const uint32_t *block_view, const int32_t *status,
+    const uint64_t *ricnt, size_t nblocks, const uint64_t *cancel_sid, const uint32_t *cancel_view,
+    size_t ncancel, const qh_dtable_view *views, size_t ntables, uint64_t *written_icnt,
+    uint8_t *dst, uint64_t dst_cap, qh_span_in *dstreams, uint64_t *dst_need);
+QH_EXPORT int qh_dec_write_decoder_batch(
+    qh_ctx *ctx, const uint64_t *block_sid, const uint32_t *block_view, const int32_t *status,
+    const uint64_t *ricnt, size_t nblocks, const uint64_t *cancel_sid, const uint32_t *cancel_view,
+    size_t ncancel, const qh_dtable_view *views, size_t ntables, uint64_t *written_icnt,
+    uint8_t *dst, uint64_t dst_cap, qh_span_in *dstreams, uint64_t *dst_need, int where);
 
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);

@@ -187,6 +187,19 @@ EXPORTED_FUNCTIONS = (
     "qh_enc_state_set_capacity",
     "qh_qpack_encode_conns",
     "qh_encode_conns_batch",
+    # acknowledgements: the reference log and the decoder stream's two ends
+    # (csrc/qh_ack.c, csrc/qh_ack.inc)
+    "qh_enc_refs_init",
+    "qh_qpack_enc_sec_flags",
+    "qh_enc_sec_flags_batch",
+    "qh_qpack_enc_refs_record",
+    "qh_enc_refs_record_batch",
+    "qh_qpack_enc_refs_compact",
+    "qh_enc_refs_compact_batch",
+    "qh_qpack_enc_read_decoder",
+    "qh_enc_read_decoder_batch",
+    "qh_qpack_dec_write_decoder",
+    "qh_dec_write_decoder_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

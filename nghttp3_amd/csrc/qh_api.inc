@@ -40,6 +40,7 @@ enum BufId {
   kBufDtc,          // qh_dtables_compact_batch: per-view record counts, the first scan's header
   kBufDtcWork,      // ... per-output-record byte counts, the second scan's header
   kBufEncConn,      // qh_encode_conns_batch: the walk's inserts, keys, instructions and results
+  kBufAck,          // the acknowledgement calls (qh_ack.inc): owner words, counts, scan headers
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap
@@ -52,6 +53,7 @@ enum BufId {
   kBufDtsetHost,   // the table set's totals read back (8 words)
   kBufDtcHost,     // compaction's totals read back (16 words)
   kBufEncConnHost,  // the connection encoder's totals read back (8 words)
+  kBufAckHost,      // the acknowledgement calls' totals read back (8 words)
   kNumBuf
 };
 

@@ -27,6 +27,7 @@ from .qpack_huffman import SPAN_IN_DTYPE, SPAN_OUT_DTYPE, HuffmanBatchCodec
 QH_ERR_QPACK_HEADER_TOO_LARGE = -109
 QH_ERR_QPACK_DECOMPRESSION_FAILED = -401
 QH_ERR_QPACK_ENCODER_STREAM_ERROR = -402
+QH_ERR_QPACK_DECODER_STREAM_ERROR = -403
 
 SPAN_HUFFMAN, SPAN_NAME = 0x1, 0x2
 (FL_INDEXED, FL_INDEXED_PB, FL_INDEXED_NAME, FL_INDEXED_NAME_PB, FL_LITERAL,
@@ -63,6 +64,12 @@ assert ENC_STATE_DTYPE.itemsize == 64
 ENC_IMMEDIATE_ACK, ENC_STRAT_NONE, ENC_CAP_PENDING = 0x1, 0x2, 0x4
 ENC_SEC_STREAM_BLOCKED, ENC_SEC_STREAM_KNOWN = 0x1, 0x2
 NV_NEVER_INDEX, NV_TRY_INDEX = 0x1, 0x2
+# include/qhuff.h qh_enc_ref, qh_enc_refs
+ENC_REF_DTYPE = np.dtype([("stream_id", "<u8"), ("max_cnt", "<u8"), ("min_cnt", "<u8"),
+                          ("reserved", "<u8")])
+ENC_REFS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("dlen", "<u8"), ("flags", "<u8")])
+assert ENC_REF_DTYPE.itemsize == 32 and ENC_REFS_DTYPE.itemsize == 32
+ENC_REFS_BAD = 0x1
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -210,6 +217,33 @@ def _load():
         lib.qh_qpack_encode_conns.restype = i32
         lib.qh_encode_conns_batch.argtypes = [vp] + encc_args + [i32]
         lib.qh_encode_conns_batch.restype = i32
+        lib.qh_enc_refs_init.argtypes = [vp]
+        lib.qh_enc_refs_init.restype = None
+        sf_args = [vp, sz, vp, sz, vp, sz, vp, vp, vp, u64, vp, vp]
+        lib.qh_qpack_enc_sec_flags.argtypes = sf_args
+        lib.qh_qpack_enc_sec_flags.restype = i32
+        lib.qh_enc_sec_flags_batch.argtypes = [vp] + sf_args + [i32]
+        lib.qh_enc_sec_flags_batch.restype = i32
+        rec_args = [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, pu64, u64]
+        lib.qh_qpack_enc_refs_record.argtypes = rec_args
+        lib.qh_qpack_enc_refs_record.restype = i32
+        lib.qh_enc_refs_record_batch.argtypes = [vp] + rec_args + [i32]
+        lib.qh_enc_refs_record_batch.restype = i32
+        cmp_args = [vp, sz, sz, vp, vp, u64, vp, pu64, u64]
+        lib.qh_qpack_enc_refs_compact.argtypes = cmp_args
+        lib.qh_qpack_enc_refs_compact.restype = i32
+        lib.qh_enc_refs_compact_batch.argtypes = [vp] + cmp_args + [i32]
+        lib.qh_enc_refs_compact_batch.restype = i32
+        rd_args = [vp, vp, vp, sz, sz, vp, vp, vp, vp, u64, vp, vp]
+        lib.qh_qpack_enc_read_decoder.argtypes = rd_args
+        lib.qh_qpack_enc_read_decoder.restype = i32
+        lib.qh_enc_read_decoder_batch.argtypes = [vp] + rd_args + [i32]
+        lib.qh_enc_read_decoder_batch.restype = i32
+        wd_args = [vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, u64, vp, pu64]
+        lib.qh_qpack_dec_write_decoder.argtypes = wd_args
+        lib.qh_qpack_dec_write_decoder.restype = i32
+        lib.qh_dec_write_decoder_batch.argtypes = [vp] + wd_args + [i32]
+        lib.qh_dec_write_decoder_batch.restype = i32
         _L = lib
     return _L
 
@@ -1008,6 +1042,72 @@ class DynamicTableSet:
         self._apply(call, "qh_qpack_dtables_apply")
         return status[:nsel], consumed[:nsel]
 
+    def _write_decoder(self, dev, emit_result, block_sid, block_view, cancel, dst_cap):
+        if dev:
+            import torch
+            new = lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev)
+            ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+            size = lambda t: 0 if t is None else t.numel()
+            fn, what = self._lib.qh_dec_write_decoder_batch, "qh_dec_write_decoder_batch"
+            head, tail = (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,)
+        else:
+            new = lambda n: np.zeros(n, dtype=np.uint8)
+            ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
+            size = lambda a: 0 if a is None else a.size
+            fn, what = self._lib.qh_qpack_dec_write_decoder, "qh_qpack_dec_write_decoder"
+            head, tail = (), ()
+        if getattr(self, "written_icnt", None) is None:
+            self.written_icnt = new(max(self.ntables, 1) * 8)
+        nblocks = size(block_sid)
+        csid, cview = (None, None) if cancel is None else cancel
+        dstreams = new(max(self.ntables, 1) * 16)
+        cap = getattr(self, "_wd_cap", 256) if dst_cap is None else dst_cap
+        pad = 0 if dst_cap is None else 64  # (tests: sentinel bytes behind a fixed capacity)
+        for _ in range(2):
+            dst = new(cap + pad)
+            if pad:
+                dst[cap:] = 0xA5
+            need = ctypes.c_uint64(0)
+            rv = fn(*head, ptr(block_sid), ptr(block_view), ptr(emit_result["status"]),
+                    ptr(emit_result["ricnt"]), nblocks, ptr(csid), ptr(cview), size(csid),
+                    ptr(self.views), self.ntables, ptr(self.written_icnt), ptr(dst), cap,
+                    ptr(dstreams), ctypes.byref(need), *tail)
+            if rv != _lib.QH_ERR_NOMEM or dst_cap is not None:
+                break
+            while cap < int(need.value):
+                cap *= 2
+            self._wd_cap = cap
+        if dst_cap is None:
+            _lib.check(rv, what)
+        return {"rv": rv, "dst": dst, "dstreams": dstreams[:self.ntables * 16],
+                "dst_need": int(need.value)}
+
+    def write_decoder(self, emit_result, block_sid, block_view, cancel=None, dst_cap=None):
+        """The decoder streams after an ``emit_fields`` call (host form,
+        qh_qpack_dec_write_decoder): block_sid uint64 and block_view uint32,
+        one per emitted block (a table's blocks consecutive), cancel =
+        (stream ids uint64, tables uint32) or None.  -> dict: dst (uint8),
+        dstreams (SPAN_IN_DTYPE, one span per table: its Section
+        Acknowledgments, Stream Cancellations and Insert Count Increment),
+        dst_need, rv.  The object owns ``written_icnt`` (uint64 per table).
+        dst_cap: a fixed capacity instead of growing (the call's return value
+        is then handed back in ``rv``)."""
+        assert self.codec is None
+        a = lambda x, d: None if x is None else np.ascontiguousarray(x, dtype=d)
+        er = {"status": a(emit_result["status"], np.int32), "ricnt": a(emit_result["ricnt"], np.uint64)}
+        c = None if cancel is None else (a(cancel[0], np.uint64), a(cancel[1], np.uint32))
+        r = self._write_decoder(False, er, a(block_sid, np.uint64), a(block_view, np.uint32), c, dst_cap)
+        r["dstreams"] = r["dstreams"].view(SPAN_IN_DTYPE)
+        return r
+
+    def write_decoder_dev(self, emit_result, block_sid, block_view, cancel=None, dst_cap=None):
+        """qh_dec_write_decoder_batch: the same over torch tensors in HBM (an
+        ``emit_fields_dev`` result; block_sid int64, block_view int32, cancel
+        = (int64, int32) tensors).  -> dict of tensors (dstreams as bytes).
+        One host wait, for the total."""
+        assert self.codec is not None
+        return self._write_decoder(True, emit_result, block_sid, block_view, cancel, dst_cap)
+
     def compact(self, extra_views=None):
         """Compacts the log (qh_dtables_compact_batch on the device form,
         qh_qpack_dtables_compact on the numpy form): the live records of
@@ -1105,15 +1205,24 @@ class EncoderSet:
     grows them on QH_ERR_NOMEM and calls again, as DynamicTableSet does.
     With ``device=None`` they are numpy arrays and ``encode`` is the host
     twin; with a device index they are torch tensors there and
-    ``encode_dev(codec, ...)`` runs the walk on the GPU.  Acknowledgements
-    are the caller's: between calls it edits ``enc_records()`` (krcnt,
-    pin_min, nblocked, nstreams) and stores them back with
-    ``set_enc_records``."""
+    ``encode_dev(codec, ...)`` runs the walk on the GPU.
+
+    With ``refs=True`` the object also owns the acknowledgement state (``rv``,
+    one ENC_REFS_DTYPE record per connection, and the reference log
+    ``refs``): ``encode`` / ``encode_dev`` take ``stream_ids=`` and run
+    sec-flags -> encode -> record, ``read_decoder`` / ``read_decoder_dev``
+    apply the peer's decoder streams, ``refs_records()`` reads the state back
+    and ``compact_refs()`` gives the log's abandoned regions back.  Without
+    it acknowledgements are the caller's: between calls it edits
+    ``enc_records()`` (krcnt, pin_min, nblocked, nstreams) and stores them
+    back with ``set_enc_records``."""
 
     def __init__(self, hard_max, n: int, max_blocked=0, immediate_ack: bool = False, device=None,
-                 strat_none: bool = False):
+                 strat_none: bool = False, refs: bool = False):
         self._lib = _load()
         self.n = int(n)
+        self.has_refs = bool(refs)
+        self.nrefs = 0
         hm = np.broadcast_to(np.asarray(hard_max, dtype=np.uint64), (self.n,))
         mb = np.broadcast_to(np.asarray(max_blocked, dtype=np.uint64), (self.n,))
         flags = (ENC_IMMEDIATE_ACK if immediate_ack else 0) | (ENC_STRAT_NONE if strat_none else 0)
@@ -1128,6 +1237,9 @@ class EncoderSet:
         self.nbytes = 0
         self.device = device
         arrays = {"views": views, "acct": acct, "enc": enc}
+        if refs:  # (a fresh connection's record is all zeros: qh_enc_refs_init)
+            arrays["rv"] = np.zeros(max(self.n, 1), dtype=ENC_REFS_DTYPE)[:self.n]
+            arrays["refs"] = np.zeros(0, dtype=ENC_REF_DTYPE)
         if device is None:
             for k, a in arrays.items():
                 setattr(self, k, a.view(np.uint8).copy())
@@ -1253,15 +1365,158 @@ class EncoderSet:
         self.nentries, self.nbytes = needs[0], needs[1]
         return res
 
+    # -- acknowledgements (refs=True): the calls of csrc/qh_ack.c / qh_ack.inc
+
+    def _ack_fns(self, codec):
+        """-> (prefix args, suffix args, pointer of, new byte array) of the
+        host twins (codec None) or the device calls."""
+        if codec is None:
+            assert self.device is None
+            return (), (), (lambda a: None if a is None or a.size == 0 else _vp(a)), \
+                (lambda n: np.zeros(n, dtype=np.uint8))
+        import torch
+        assert self.device is not None
+        return (codec._ctx,), (_lib.QH_WHERE_DEVICE,), \
+            (lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())), \
+            (lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev))
+
+    @staticmethod
+    def _size(a):
+        return a.size if isinstance(a, np.ndarray) else a.numel()
+
+    def _sec_flags(self, codec, sids, conn_start, nsections, nconns, tsel):
+        """qh_qpack_enc_sec_flags / qh_enc_sec_flags_batch -> (sec_flags uint8,
+        status int32 as bytes), arrays of the object's kind."""
+        head, tail, ptr, new = self._ack_fns(codec)
+        fn = self._lib.qh_qpack_enc_sec_flags if codec is None else self._lib.qh_enc_sec_flags_batch
+        flags, status = new(max(nsections, 1)), new(max(nconns, 1) * 4)
+        rv = fn(*head, ptr(sids), nsections, ptr(conn_start), nconns, ptr(tsel), self.n,
+                ptr(self.enc), ptr(self.rv), ptr(self.refs), self.nrefs, ptr(flags), ptr(status),
+                *tail)
+        _lib.check(rv, "qh_enc_sec_flags")
+        return flags[:nsections], status
+
+    def _record(self, codec, sids, conn_start, nsections, nconns, tsel, r, refs_cap=None):
+        """qh_qpack_enc_refs_record / qh_enc_refs_record_batch after an encode
+        call with result r; the log grows on QH_ERR_NOMEM (refs_cap: a fixed
+        capacity instead, for tests: -> the call's return value)."""
+        head, tail, ptr, _ = self._ack_fns(codec)
+        fn = self._lib.qh_qpack_enc_refs_record if codec is None else \
+            self._lib.qh_enc_refs_record_batch
+        for _ in range(2):
+            nr = ctypes.c_uint64(self.nrefs)
+            cap = self._size(self.refs) // 32 if refs_cap is None else refs_cap
+            rv = fn(*head, ptr(sids), nsections, ptr(conn_start), nconns, ptr(tsel), self.n,
+                    ptr(r["max_cnt"]), ptr(r["min_cnt"]), ptr(r["status"]), ptr(self.enc),
+                    ptr(self.rv), ptr(self.refs), ctypes.byref(nr), cap, *tail)
+            if rv != _lib.QH_ERR_NOMEM or refs_cap is not None:
+                break
+            self._grow("refs", self.nrefs * 32, int(nr.value) * 32, 4096)
+        if refs_cap is not None:
+            if rv == 0:
+                self.nrefs = int(nr.value)
+            return rv, int(nr.value)
+        _lib.check(rv, "qh_enc_refs_record")
+        self.nrefs = int(nr.value)
+        return rv, self.nrefs
+
+    def _with_stream_ids(self, codec, call, sids, conn_start, nsections, nconns, tsel, sec_flags):
+        if sids is None:
+            return call(sec_flags)
+        if sec_flags is not None:
+            raise ValueError("pass stream_ids or sec_flags, not both")
+        if not self.has_refs:
+            raise ValueError("stream_ids needs an EncoderSet made with refs=True")
+        flags, st = self._sec_flags(codec, sids, conn_start, nsections, nconns, tsel)
+        r = call(flags)
+        r["sec_flags"], r["sec_status"] = flags, st
+        if r["rv"] == 0:
+            self._record(codec, sids, conn_start, nsections, nconns, tsel, r)
+        return r
+
+    def read_decoder(self, src, streams, tsel=None):
+        """Decoder-stream bytes applied on the host (qh_qpack_enc_read_decoder):
+        stream p is src[streams[p].off, + len) (src uint8, streams
+        SPAN_IN_DTYPE, tsel uint32 or None for stream p -> connection p).
+        -> (status int32, consumed uint32): per stream 0 or the first failing
+        instruction's error (-403; -108 once the connection is bad), and the
+        bytes of complete, applied instructions."""
+        assert self.device is None and self.has_refs
+        src = _u8(src)
+        streams = np.ascontiguousarray(streams, dtype=SPAN_IN_DTYPE)
+        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
+        nsel = self.n if sel is None else sel.size
+        status = np.zeros(max(nsel, 1), dtype=np.int32)
+        consumed = np.zeros(max(nsel, 1), dtype=np.uint32)
+        p_sel = None if sel is None else _vp(sel if sel.size else np.zeros(1, np.uint32))
+        ptr = lambda a: None if a.size == 0 else _vp(a)
+        rv = self._lib.qh_qpack_enc_read_decoder(
+            _vp(src), _vp(streams), p_sel, nsel, self.n, ptr(self.views), ptr(self.enc),
+            ptr(self.rv), ptr(self.refs), self.nrefs, _vp(status), _vp(consumed))
+        _lib.check(rv, "qh_qpack_enc_read_decoder")
+        return status[:nsel], consumed[:nsel]
+
+    def read_decoder_dev(self, codec: HuffmanBatchCodec, src, streams, tsel=None):
+        """qh_enc_read_decoder_batch: the same over torch tensors in HBM (src
+        uint8, streams int64 [nsel, 2] as SPAN_IN_DTYPE records, tsel int32).
+        -> (status int32, consumed int32) tensors.  Asynchronous on the codec
+        stream, no host wait."""
+        import torch
+        assert self.device is not None and self.has_refs
+        nsel = self.n if tsel is None else int(tsel.shape[0])
+        status = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
+        consumed = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
+        p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+        p_tsel = p(status) if tsel is not None and nsel == 0 else p(tsel)
+        rv = self._lib.qh_enc_read_decoder_batch(
+            codec._ctx, p(src), p(streams), p_tsel, nsel, self.n, p(self.views), p(self.enc),
+            p(self.rv), p(self.refs), self.nrefs, p(status), p(consumed), _lib.QH_WHERE_DEVICE)
+        _lib.check(rv, "qh_enc_read_decoder_batch")
+        return status[:nsel], consumed[:nsel]
+
+    def refs_records(self):
+        """-> (rv ENC_REFS_DTYPE [n], refs ENC_REF_DTYPE [nrefs]), numpy copies:
+        connection t's unacknowledged sections are refs[rv[t].base, + rv[t].n)."""
+        assert self.has_refs
+        return (self._host("rv", ENC_REFS_DTYPE),
+                self._host("refs", np.uint8)[:self.nrefs * 32].view(ENC_REF_DTYPE))
+
+    def compact_refs(self, codec: HuffmanBatchCodec | None = None):
+        """The reference log replaced by one that holds every connection's
+        references back to back, in connection order
+        (qh_qpack_enc_refs_compact; with the device form's codec
+        qh_enc_refs_compact_batch)."""
+        assert self.has_refs
+        head, tail, ptr, new = self._ack_fns(codec)
+        fn = self._lib.qh_qpack_enc_refs_compact if codec is None else \
+            self._lib.qh_enc_refs_compact_batch
+        nr = ctypes.c_uint64(0)
+        rv = fn(*head, None, self.n, self.n, ptr(self.rv), ptr(self.refs), self.nrefs, None,
+                ctypes.byref(nr), 0, *tail)  # the sizing call
+        if rv != _lib.QH_ERR_NOMEM:
+            _lib.check(rv, "qh_enc_refs_compact")
+        cap = 128
+        while cap < int(nr.value):
+            cap *= 2
+        out = new(cap * 32)
+        rv = fn(*head, None, self.n, self.n, ptr(self.rv), ptr(self.refs), self.nrefs, ptr(out),
+                ctypes.byref(nr), cap, *tail)
+        _lib.check(rv, "qh_enc_refs_compact")
+        self.refs, self.nrefs = out, int(nr.value)
+
     def encode(self, plain, strs, field_start, conn_start, nvflags=None, sec_flags=None, tsel=None,
-               caps=None):
+               caps=None, stream_ids=None):
         """The host twin (qh_qpack_encode_conns) over numpy arrays: plain
         uint8, strs SPAN_IN_DTYPE (two per field), field_start / conn_start
         uint32, nvflags / sec_flags uint8 or None, tsel uint32 or None.
         -> dict of numpy arrays: lines (FIELD_LINE_DTYPE), prefixes
         (PREFIX_DTYPE), max_cnt, min_cnt (uint64), dst (uint8, the sections'
         bytes), sections (SPAN_IN_DTYPE), edst (uint8), estreams
-        (SPAN_IN_DTYPE, one per listed connection), status (int32)."""
+        (SPAN_IN_DTYPE, one per listed connection), status (int32).
+        stream_ids (refs=True; uint64, one per section, instead of sec_flags):
+        the flags come from the reference log (qh_qpack_enc_sec_flags; the
+        result gains sec_flags and sec_status) and the call's references are
+        recorded after it (qh_qpack_enc_refs_record)."""
         assert self.device is None
         plain = _u8(plain)
         strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
@@ -1276,16 +1531,21 @@ class EncoderSet:
             ptr_sel = np.zeros(1, dtype=np.uint32)
         else:
             ptr_sel = sel
-        r = self._call(self._lib.qh_qpack_encode_conns, (), (), ptr, lambda a: a.size,
-                       lambda n: np.zeros(n, dtype=np.uint8), plain, strs, nfields, nv, fs,
-                       nsections, sf, cs, nconns, ptr_sel, caps)
+        sids = opt(stream_ids, np.uint64)
+        call = lambda flags: self._call(
+            self._lib.qh_qpack_encode_conns, (), (), ptr, lambda a: a.size,
+            lambda n: np.zeros(n, dtype=np.uint8), plain, strs, nfields, nv, fs, nsections, flags,
+            cs, nconns, ptr_sel, caps)
+        r = self._with_stream_ids(None, call, sids, cs, nsections, nconns, ptr_sel, sf)
         return self._unpack(r, lambda a: a)
 
     def encode_dev(self, codec: HuffmanBatchCodec, plain, strs, field_start, conn_start,
-                   nvflags=None, sec_flags=None, tsel=None, caps=None):
+                   nvflags=None, sec_flags=None, tsel=None, caps=None, stream_ids=None):
         """qh_encode_conns_batch: the same over torch tensors in HBM (plain
         uint8, strs int64 [2 nfields, 2] as SPAN_IN_DTYPE records,
-        field_start / conn_start / tsel int32, nvflags / sec_flags uint8).
+        field_start / conn_start / tsel int32, nvflags / sec_flags uint8,
+        stream_ids int64: qh_enc_sec_flags_batch before the call and
+        qh_enc_refs_record_batch after it).
         -> the same dict, of tensors viewed as bytes (``to_host`` converts)."""
         import torch
         assert self.device is not None
@@ -1294,12 +1554,13 @@ class EncoderSet:
         ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
         if tsel is not None and tsel.numel() == 0:
             tsel = torch.zeros(1, dtype=torch.int32, device=self._dev)
-        r = self._call(self._lib.qh_encode_conns_batch, (codec._ctx,), (_lib.QH_WHERE_DEVICE,), ptr,
-                       lambda t: t.numel(),
-                       lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev), plain, strs,
-                       nfields, nvflags, field_start, nsections, sec_flags, conn_start, nconns, tsel,
-                       caps)
-        return r
+        call = lambda flags: self._call(
+            self._lib.qh_encode_conns_batch, (codec._ctx,), (_lib.QH_WHERE_DEVICE,), ptr,
+            lambda t: t.numel(), lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev),
+            plain, strs, nfields, nvflags, field_start, nsections, flags, conn_start, nconns, tsel,
+            caps)
+        return self._with_stream_ids(codec, call, stream_ids, conn_start, nsections, nconns, tsel,
+                                     sec_flags)
 
     @staticmethod
     def _unpack(r, host):
@@ -1313,6 +1574,9 @@ class EncoderSet:
         out["estreams"] = host(r["estreams"])[:nc * 16].view(SPAN_IN_DTYPE)
         out["status"] = host(r["status"])[:nc * 4].view(np.int32)
         out["dst"], out["edst"] = host(r["dst"]), host(r["edst"])  # (needs[2], needs[3] bytes)
+        if "sec_status" in r:
+            out["sec_flags"] = host(r["sec_flags"])[:ns]
+            out["sec_status"] = host(r["sec_status"])[:nc * 4].view(np.int32)
         return out
 
     @classmethod
