@@ -1367,6 +1367,130 @@ QH_EXPORT int qh_dec_write_decoder_batch(
     size_t ncancel, const qh_dtable_view *views, size_t ntables, uint64_t *written_icnt,
     uint8_t *dst, uint64_t dst_cap, qh_span_in *dstreams, uint64_t *dst_need, int where);
 
+/* ---- Blocked field sections: queued, released and cancelled per batch ----
+ *
+ * What a decoder keeps for the sections qh_emit_fields_batch found blocked
+ * (QH_EMIT_BLOCKED): which stream waits, for which table, at which Required
+ * Insert Count, and the section's bytes -- the reference's per-connection
+ * priority queue (lib/nghttp3_conn.c:263-271, :1463-1479, :1355, the limit
+ * :1892-1895; examples/qpack_decode.cc:99-174) for many connections, with no
+ * library object.  Table t's blocked sections are blks[bq[t].base, + bq[t].n)
+ * in arrival order, in one caller-owned log blks[0, *nblks); their bytes are
+ * pend[off, + len) in one caller-owned, append-only byte log pend[0, *npend).
+ * bq[] lies beside views and acct.  Layout rules, the same on host and
+ * device, so that both write the same bytes:
+ *   - a table that gains a record in a call moves: its records are copied in
+ *     order to the cursor and the new ones follow in list order; the cursor
+ *     starts at *nblks and moves past each moved table in order of first
+ *     appearance in the call's list;
+ *   - removal never moves a table: its region is compacted in place, order
+ *     kept, n shrinks (the records past the new n are left as they are);
+ *   - new bytes go to pend at the byte cursor (*npend on entry), back to
+ *     back in the order of the new records; older bytes are never moved;
+ *   - when a capacity is short the call returns QH_ERR_NOMEM with the exact
+ *     needs in *nblks / *npend (or the call's own need words) and nothing
+ *     else written.
+ * Each call has a host form over host pointers and a device form over
+ * pointers in HBM (where must be QH_WHERE_DEVICE; counts are host scalars),
+ * asynchronous on the context stream after the host wait named below.
+ *
+ * push, after an emit: every array is indexed by position in the emit
+ * call's sel (src and blocks: the sections call's spans of the selected
+ * blocks).  The blocks of one table must be consecutive; a second run of a
+ * table or an index >= ntables gives QH_ERR_INVALID_ARGUMENT, nothing
+ * written.  Per table the positions with status == QH_EMIT_BLOCKED are
+ * examined in list order:
+ *   1. the stream id is queued for the table, or was accepted earlier in the
+ *      call: verdict QH_ERR_INVALID_ARGUMENT, not queued (a blocked stream
+ *      delivers nothing further in the reference: a caller error);
+ *   2. else n + the records accepted so far >= max_blocked: verdict
+ *      QH_ERR_QPACK_DECOMPRESSION_FAILED, not queued (conn.c:1892-1895);
+ *   3. else queued as {sid, ricnt, off, len}, its bytes copied, verdict
+ *      QH_EMIT_BLOCKED.
+ * Every other position gets verdict = status.  src needs no padding: nothing
+ * is read outside src[blocks[p].off, + len).  Device: runs, a count pass (a
+ * 16-lane group per table), one scan, one host wait (the totals and the
+ * list's errors), then the verdicts, the record copy, the byte copy and the
+ * rebase.
+ *
+ * release, after an apply: for each listed table (tsel, each at most once;
+ * NULL: all, nsel = ntables) every record with ricnt <= views[t].insert_count
+ * is removed and written to positions [rel_start[i], rel_start[i + 1]) of
+ * rel_blocks (spans of pend), rel_sid, rel_view and rel_ricnt, ordered by
+ * ascending ricnt, then queue position (the reference's (ricnt, seq) order);
+ * the rest is compacted in place.  The outputs go as they are, with src =
+ * pend, into qh_decode_sections_batch (blocks), qh_emit_fields_batch
+ * (block_view) and qh_dec_write_decoder_batch (block_sid, block_view).
+ * QH_ERR_NOMEM when rel_cap is short (*nreleased the need, nothing changed);
+ * QH_ERR_INVALID_ARGUMENT for a table named twice or out of range.  Device:
+ * a count pass, a scan, one host wait, a write pass (a group per table).
+ *
+ * cancel: the queued record of stream cancel_sid[i] of table cancel_view[i],
+ * if there is one, is removed in place; removed[i] = 1 when one was (an
+ * unknown stream is no error, qpack.c:3889-3913).  A table's cancellations
+ * are consecutive.  The host form refuses a second run of a table or an index
+ * out of range (QH_ERR_INVALID_ARGUMENT, nothing written); the device form
+ * has no host wait and cannot: there the first run of a table is served and
+ * the items of a later run, or of a table out of range, get removed[i] =
+ * 0xFF and remove nothing.
+ *
+ * compact: the records of the listed tables copied to blks_out back to back
+ * in list order, their bytes to pend_out in record order, off rewritten and
+ * bq[].base rebased; QH_ERR_NOMEM with *nblks_out / *npend_out exact when a
+ * capacity is short (nothing written); a record whose bytes lie outside
+ * pend[0, npend) gives QH_ERR_INVALID_ARGUMENT.  When to compact is the
+ * caller's decision.  Device: a count pass, a scan, one host wait, the
+ * record copy, the byte copy, the rebase.
+ *
+ * Not built: emission with a given Required Insert Count.  A released block
+ * is emitted like any other, so its Required Insert Count is reconstructed
+ * again against the table's newer state, where the reference keeps the first
+ * value; for a conformant encoder the two agree (a referenced entry is still
+ * live).  rel_ricnt hands the queued value back so that a caller can compare. */
+typedef struct qh_dec_blk  { uint64_t stream_id, ricnt, off; uint32_t len, reserved; } qh_dec_blk;  /* 32 B */
+typedef struct qh_dec_blks { uint64_t base, n, max_blocked, flags; } qh_dec_blks;                  /* 32 B */
+QH_EXPORT void qh_dec_blks_init(uint64_t max_blocked, qh_dec_blks *bq);
+
+QH_EXPORT int qh_qpack_dec_blocked_push(
+    const uint8_t *src, const qh_span_in *blocks, const uint64_t *block_sid,
+    const uint32_t *block_view, const int32_t *status, const uint64_t *ricnt, size_t nblocks,
+    size_t ntables, qh_dec_blks *bq, qh_dec_blk *blks, uint64_t *nblks, uint64_t blks_cap,
+    uint8_t *pend, uint64_t *npend, uint64_t pend_cap, int32_t *verdict);
+QH_EXPORT int qh_dec_blocked_push_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *blocks, const uint64_t *block_sid,
+    const uint32_t *block_view, const int32_t *status, const uint64_t *ricnt, size_t nblocks,
+    size_t ntables, qh_dec_blks *bq, qh_dec_blk *blks, uint64_t *nblks, uint64_t blks_cap,
+    uint8_t *pend, uint64_t *npend, uint64_t pend_cap, int32_t *verdict, int where);
+
+QH_EXPORT int qh_qpack_dec_blocked_release(
+    const uint32_t *tsel, size_t nsel, size_t ntables, const qh_dtable_view *views,
+    qh_dec_blks *bq, qh_dec_blk *blks, uint64_t nblks, qh_span_in *rel_blocks, uint64_t *rel_sid,
+    uint32_t *rel_view, uint64_t *rel_ricnt, uint32_t *rel_start, uint64_t *nreleased,
+    uint64_t rel_cap);
+QH_EXPORT int qh_dec_blocked_release_batch(
+    qh_ctx *ctx, const uint32_t *tsel, size_t nsel, size_t ntables, const qh_dtable_view *views,
+    qh_dec_blks *bq, qh_dec_blk *blks, uint64_t nblks, qh_span_in *rel_blocks, uint64_t *rel_sid,
+    uint32_t *rel_view, uint64_t *rel_ricnt, uint32_t *rel_start, uint64_t *nreleased,
+    uint64_t rel_cap, int where);
+
+QH_EXPORT int qh_qpack_dec_blocked_cancel(
+    const uint64_t *cancel_sid, const uint32_t *cancel_view, size_t ncancel, size_t ntables,
+    qh_dec_blks *bq, qh_dec_blk *blks, uint64_t nblks, uint8_t *removed);
+QH_EXPORT int qh_dec_blocked_cancel_batch(
+    qh_ctx *ctx, const uint64_t *cancel_sid, const uint32_t *cancel_view, size_t ncancel,
+    size_t ntables, qh_dec_blks *bq, qh_dec_blk *blks, uint64_t nblks, uint8_t *removed,
+    int where);
+
+QH_EXPORT int qh_qpack_dec_blocked_compact(
+    const uint32_t *tsel, size_t nsel, size_t ntables, qh_dec_blks *bq, const qh_dec_blk *blks,
+    uint64_t nblks, const uint8_t *pend, uint64_t npend, qh_dec_blk *blks_out, uint64_t *nblks_out,
+    uint64_t blks_out_cap, uint8_t *pend_out, uint64_t *npend_out, uint64_t pend_out_cap);
+QH_EXPORT int qh_dec_blocked_compact_batch(
+    qh_ctx *ctx, const uint32_t *tsel, size_t nsel, size_t ntables, qh_dec_blks *bq,
+    const qh_dec_blk *blks, uint64_t nblks, const uint8_t *pend, uint64_t npend,
+    qh_dec_blk *blks_out, uint64_t *nblks_out, uint64_t blks_out_cap, uint8_t *pend_out,
+    uint64_t *npend_out, uint64_t pend_out_cap, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

@@ -200,6 +200,17 @@ EXPORTED_FUNCTIONS = (
     "qh_enc_read_decoder_batch",
     "qh_qpack_dec_write_decoder",
     "qh_dec_write_decoder_batch",
+    # blocked sections: queued, released, cancelled and compacted per batch
+    # (csrc/qh_blocked.c, csrc/qh_blocked.inc)
+    "qh_dec_blks_init",
+    "qh_qpack_dec_blocked_push",
+    "qh_dec_blocked_push_batch",
+    "qh_qpack_dec_blocked_release",
+    "qh_dec_blocked_release_batch",
+    "qh_qpack_dec_blocked_cancel",
+    "qh_dec_blocked_cancel_batch",
+    "qh_qpack_dec_blocked_compact",
+    "qh_dec_blocked_compact_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -41,6 +41,8 @@ enum BufId {
   kBufDtcWork,      // ... per-output-record byte counts, the second scan's header
   kBufEncConn,      // qh_encode_conns_batch: the walk's inserts, keys, instructions and results
   kBufAck,          // the acknowledgement calls (qh_ack.inc): owner words, counts, scan headers
+  kBufBlocked,      // the blocked-section calls (qh_blocked.inc): runs, counts, per-block records, scan headers
+  kBufBlockedWork,  // ... compaction's flat list of output records
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap
@@ -54,6 +56,7 @@ enum BufId {
   kBufDtcHost,     // compaction's totals read back (16 words)
   kBufEncConnHost,  // the connection encoder's totals read back (8 words)
   kBufAckHost,      // the acknowledgement calls' totals read back (8 words)
+  kBufBlockedHost,  // the blocked-section calls' totals read back (8 words)
   kNumBuf
 };
 

@@ -20,6 +20,7 @@
 //   qh_k_dts_*         encoder streams applied to many dynamic tables in one log
 //   qh_k_encc_*        the encoder with inserts for many connections: walk and commit
 //   qh_k_ack_*, qh_k_ackw_*  acknowledgements: the reference log, decoder streams read and written
+//   qh_k_blk_*         blocked sections: queued, released, cancelled, compacted
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
 // Development variants (the pair decoder, the segment encoder) build only
 // with -DQH_DEV_VARIANTS (make dev -> libqhuff_dev.so); the kernels that
@@ -79,4 +80,5 @@
 #include "qh_dtset.inc"         // encoder streams of many connections -> dynamic tables in one log
 #include "qh_encconn.inc"       // fields of many connections -> sections, encoder streams and tables, with inserts
 #include "qh_ack.inc"           // acknowledgements: reference log, decoder streams read and written
+#include "qh_blocked.inc"       // blocked sections: the queue log, push, release, cancel, compact
 

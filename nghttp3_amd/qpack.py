@@ -70,6 +70,10 @@ ENC_REF_DTYPE = np.dtype([("stream_id", "<u8"), ("max_cnt", "<u8"), ("min_cnt", 
 ENC_REFS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("dlen", "<u8"), ("flags", "<u8")])
 assert ENC_REF_DTYPE.itemsize == 32 and ENC_REFS_DTYPE.itemsize == 32
 ENC_REFS_BAD = 0x1
+DEC_BLK_DTYPE = np.dtype([("stream_id", "<u8"), ("ricnt", "<u8"), ("off", "<u8"), ("len", "<u4"),
+                          ("reserved", "<u4")])
+DEC_BLKS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("max_blocked", "<u8"), ("flags", "<u8")])
+assert DEC_BLK_DTYPE.itemsize == 32 and DEC_BLKS_DTYPE.itemsize == 32
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -244,6 +248,28 @@ def _load():
         lib.qh_qpack_dec_write_decoder.restype = i32
         lib.qh_dec_write_decoder_batch.argtypes = [vp] + wd_args + [i32]
         lib.qh_dec_write_decoder_batch.restype = i32
+        lib.qh_dec_blks_init.argtypes = [u64, vp]
+        lib.qh_dec_blks_init.restype = None
+        bp_args = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, pu64, u64, vp, pu64, u64, vp]
+        lib.qh_qpack_dec_blocked_push.argtypes = bp_args
+        lib.qh_qpack_dec_blocked_push.restype = i32
+        lib.qh_dec_blocked_push_batch.argtypes = [vp] + bp_args + [i32]
+        lib.qh_dec_blocked_push_batch.restype = i32
+        br_args = [vp, sz, sz, vp, vp, vp, u64, vp, vp, vp, vp, vp, pu64, u64]
+        lib.qh_qpack_dec_blocked_release.argtypes = br_args
+        lib.qh_qpack_dec_blocked_release.restype = i32
+        lib.qh_dec_blocked_release_batch.argtypes = [vp] + br_args + [i32]
+        lib.qh_dec_blocked_release_batch.restype = i32
+        bc_args = [vp, vp, sz, sz, vp, vp, u64, vp]
+        lib.qh_qpack_dec_blocked_cancel.argtypes = bc_args
+        lib.qh_qpack_dec_blocked_cancel.restype = i32
+        lib.qh_dec_blocked_cancel_batch.argtypes = [vp] + bc_args + [i32]
+        lib.qh_dec_blocked_cancel_batch.restype = i32
+        bk_args = [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64]
+        lib.qh_qpack_dec_blocked_compact.argtypes = bk_args
+        lib.qh_qpack_dec_blocked_compact.restype = i32
+        lib.qh_dec_blocked_compact_batch.argtypes = [vp] + bk_args + [i32]
+        lib.qh_dec_blocked_compact_batch.restype = i32
         _L = lib
     return _L
 
@@ -930,9 +956,17 @@ class DynamicTableSet:
     dynamic planners, ``keys()`` with them.  Without a codec the same state is
     numpy arrays and ``read_encoder`` the host twin.  Applying only grows the
     log: a copy of ``views`` taken before a call stays valid after it.
-    ``compact()`` replaces the log by one that holds the live records alone."""
+    ``compact()`` replaces the log by one that holds the live records alone.
 
-    def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None):
+    With `max_blocked` (a scalar, or one value per table) the set also keeps
+    the sections that emit found blocked: ``bq`` (uint8 [ntables * 32],
+    DEC_BLKS_DTYPE), the record log ``blks`` / ``nblks`` (DEC_BLK_DTYPE) and
+    the byte log ``pend`` / ``npend``, fed by ``push_blocked`` after an emit,
+    drained by ``release_blocked`` after ``read_encoder`` and by
+    ``cancel_blocked``; ``compact_blocked`` replaces the two logs."""
+
+    def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None,
+                 max_blocked=None):
         self._lib = _load()
         self.codec = codec
         self.ntables = int(ntables)
@@ -959,6 +993,24 @@ class DynamicTableSet:
             self.entries = torch.empty(0, dtype=torch.uint8, device=self._dev)
             self.dyn_bytes = torch.empty(0, dtype=torch.uint8, device=self._dev)
             self._keys = torch.empty(0, dtype=torch.uint8, device=self._dev)
+        self.max_blocked = max_blocked
+        if max_blocked is not None:
+            mb = np.broadcast_to(np.asarray(max_blocked, dtype=np.uint64), (self.ntables,))
+            bq = np.zeros(max(self.ntables, 1), dtype=DEC_BLKS_DTYPE)[:self.ntables]
+            b1 = np.zeros(1, dtype=DEC_BLKS_DTYPE)
+            for t in range(self.ntables):
+                self._lib.qh_dec_blks_init(int(mb[t]), _vp(b1))
+                bq[t] = b1[0]
+            self.nblks = 0
+            self.npend = 0
+            if codec is None:
+                self.bq = bq.view(np.uint8).copy()
+                self.blks = np.zeros(0, dtype=np.uint8)
+                self.pend = np.zeros(0, dtype=np.uint8)
+            else:
+                self.bq = torch.from_numpy(bq.view(np.uint8).copy()).to(self._dev)
+                self.blks = torch.empty(0, dtype=torch.uint8, device=self._dev)
+                self.pend = torch.empty(0, dtype=torch.uint8, device=self._dev)
 
     # -- capacity: the arrays grow by doubling, the log's prefix kept
 
@@ -1107,6 +1159,228 @@ class DynamicTableSet:
         One host wait, for the total."""
         assert self.codec is not None
         return self._write_decoder(True, emit_result, block_sid, block_view, cancel, dst_cap)
+
+    # -- blocked sections (max_blocked given): qh_dec_blocked_* / qh_qpack_dec_blocked_*
+
+    def _blk_io(self):
+        """-> (new, ptr, size, head, tail, suffix) of the form the set is in."""
+        if self.max_blocked is None:
+            raise ValueError("the set was made without max_blocked")
+        if self.codec is not None:
+            import torch
+            new = lambda n, d=torch.uint8: torch.zeros(n, dtype=d, device=self._dev)
+            ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+            size = lambda t: 0 if t is None else t.numel()
+            return new, ptr, size, (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,), "_batch"
+        new = lambda n, d=np.uint8: np.zeros(n, dtype=d)
+        ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
+        size = lambda a: 0 if a is None else a.size
+        return new, ptr, size, (), (), ""
+
+    def _push_blocked(self, src, blocks, block_sid, block_view, emit_result, caps):
+        new, ptr, size, head, tail, sfx = self._blk_io()
+        dev = self.codec is not None
+        fn = getattr(self._lib, "qh_dec_blocked_push_batch" if dev else "qh_qpack_dec_blocked_push")
+        nblocks = size(block_sid)
+        if dev:
+            import torch
+            verdict = new(max(nblocks, 1), torch.int32)
+        else:
+            verdict = new(max(nblocks, 1), np.int32)
+        for _ in range(2):
+            nr, nb = ctypes.c_uint64(self.nblks), ctypes.c_uint64(self.npend)
+            rcap, bcap = (size(self.blks) // 32, size(self.pend)) if caps is None else caps
+            rv = fn(*head, ptr(src), ptr(blocks), ptr(block_sid), ptr(block_view),
+                    ptr(emit_result["status"]), ptr(emit_result["ricnt"]), nblocks, self.ntables,
+                    ptr(self.bq), ptr(self.blks), ctypes.byref(nr), rcap, ptr(self.pend),
+                    ctypes.byref(nb), bcap, ptr(verdict), *tail)
+            if rv != _lib.QH_ERR_NOMEM or caps is not None:
+                break
+            # the exact needs are known: the arrays grow by doubling, the logs kept
+            self._grow("blks", self.nblks * 32, int(nr.value) * 32, 4096)
+            self._grow("pend", self.npend, int(nb.value), 4096)
+        if caps is None:
+            _lib.check(rv, "qh_dec_blocked_push" + sfx)
+        if rv == 0:
+            self.nblks, self.npend = int(nr.value), int(nb.value)
+        return {"rv": rv, "verdict": verdict[:nblocks], "nblks": int(nr.value),
+                "npend": int(nb.value)}
+
+    def push_blocked(self, src, blocks, block_sid, block_view, emit_result, caps=None):
+        """After ``emit_fields`` (host form, qh_qpack_dec_blocked_push): queues
+        the blocks whose status is EMIT_BLOCKED.  Every array is indexed by
+        position in the emit call's sel: blocks SPAN_IN_DTYPE spans of src,
+        block_sid uint64, block_view uint32 (a table's blocks consecutive),
+        emit_result the emit call's dict (status, ricnt).  -> dict: verdict
+        (int32: EMIT_BLOCKED queued, -101 the stream is queued already, -401
+        too many blocked streams, else the block's status), rv, nblks, npend.
+        The logs grow as needed; caps = (records, bytes) fixes the
+        capacities instead and hands the call's return value back in rv."""
+        assert self.codec is None
+        a = lambda x, d: None if x is None else np.ascontiguousarray(x, dtype=d)
+        er = {"status": a(emit_result["status"], np.int32), "ricnt": a(emit_result["ricnt"], np.uint64)}
+        return self._push_blocked(_u8(src), a(blocks, SPAN_IN_DTYPE), a(block_sid, np.uint64),
+                                  a(block_view, np.uint32), er, caps)
+
+    def push_blocked_dev(self, src, blocks, block_sid, block_view, emit_result, caps=None):
+        """qh_dec_blocked_push_batch: the same over torch tensors in HBM (src
+        uint8, blocks int64 [n, 2], block_sid int64, block_view int32, an
+        ``emit_fields_dev`` result).  One host wait, for the totals."""
+        assert self.codec is not None
+        return self._push_blocked(src, blocks, block_sid, block_view, emit_result, caps)
+
+    def _release_blocked(self, tsel, rel_cap):
+        new, ptr, size, head, tail, sfx = self._blk_io()
+        dev = self.codec is not None
+        fn = getattr(self._lib,
+                     "qh_dec_blocked_release_batch" if dev else "qh_qpack_dec_blocked_release")
+        nsel = self.ntables if tsel is None else size(tsel)
+        cap = getattr(self, "_rel_cap", 64) if rel_cap is None else rel_cap
+        pad = 0 if rel_cap is None else 4  # (tests: sentinel records behind a fixed capacity)
+        start = new((nsel + 1) * 4)
+        # (an empty list still has to be a list, not tsel = NULL's "all tables")
+        p_tsel = ptr(start) if tsel is not None and nsel == 0 else ptr(tsel)
+        for _ in range(2):
+            o = {"blocks": new((cap + pad) * 16), "sid": new((cap + pad) * 8),
+                 "view": new((cap + pad) * 4), "ricnt": new((cap + pad) * 8)}
+            for a in o.values():  # (sentinel bytes behind a fixed capacity)
+                a[a.shape[0] // (cap + pad) * cap:] = 0xA5
+            need = ctypes.c_uint64(0)
+            rv = fn(*head, p_tsel, nsel, self.ntables, ptr(self.views), ptr(self.bq), ptr(self.blks),
+                    self.nblks, ptr(o["blocks"]), ptr(o["sid"]), ptr(o["view"]), ptr(o["ricnt"]),
+                    ptr(start), ctypes.byref(need), cap, *tail)
+            if rv != _lib.QH_ERR_NOMEM or rel_cap is not None:
+                break
+            while cap < int(need.value):
+                cap *= 2
+            self._rel_cap = cap
+        if rel_cap is None:
+            _lib.check(rv, "qh_dec_blocked_release" + sfx)
+        o.update({"rv": rv, "start": start, "nreleased": int(need.value), "cap": cap})
+        return o
+
+    def release_blocked(self, tsel=None, rel_cap=None):
+        """After ``read_encoder`` (host form, qh_qpack_dec_blocked_release): the
+        queued sections of the listed tables (uint32, each at most once; None:
+        all) whose Required Insert Count the table now holds are removed.  ->
+        dict: nreleased, blocks (SPAN_IN_DTYPE spans of ``pend``), sid
+        (uint64), view (uint32), ricnt (uint64), the released sections of
+        listed table i at [start[i], start[i + 1]) in (ricnt, arrival) order;
+        rv.  blocks / view go into decode_blocks and emit_fields with src =
+        ``pend``, sid / view into write_decoder.  rel_cap: a fixed capacity
+        instead of growing."""
+        assert self.codec is None
+        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
+        o = self._release_blocked(sel, rel_cap)
+        n = o["nreleased"] if o["rv"] == 0 else 0
+        for k, d in (("blocks", SPAN_IN_DTYPE), ("sid", np.uint64), ("view", np.uint32),
+                     ("ricnt", np.uint64)):
+            o[k + "_raw"] = o[k]
+            o[k] = o[k].view(d)[:n]
+        o["start"] = o["start"].view(np.uint32)
+        return o
+
+    def release_blocked_dev(self, tsel=None, rel_cap=None):
+        """qh_dec_blocked_release_batch: the same on the device (tsel int32 or
+        None).  -> dict of tensors: blocks int64 [n, 2], sid int64, view int32,
+        ricnt int64, start int32 [nsel + 1]; nreleased, rv.  One host wait."""
+        import torch
+        assert self.codec is not None
+        o = self._release_blocked(tsel, rel_cap)
+        n = o["nreleased"] if o["rv"] == 0 else 0
+        for k, d in (("blocks", torch.int64), ("sid", torch.int64), ("view", torch.int32),
+                     ("ricnt", torch.int64)):
+            o[k + "_raw"] = o[k]
+            o[k] = o[k].view(d)[:n * (2 if k == "blocks" else 1)]
+        o["blocks"] = o["blocks"].reshape(-1, 2)
+        o["start"] = o["start"].view(torch.int32)
+        return o
+
+    @staticmethod
+    def released_status(emit_result, rel):
+        """The status of released blocks after their emit: -401 where a block
+        came out blocked again or with another Required Insert Count than the
+        one it was queued with (the reference keeps the first value; emit
+        reconstructs it again).  numpy arrays or torch tensors."""
+        st, ri, want = emit_result["status"], emit_result["ricnt"], rel["ricnt"]
+        n = want.shape[0]
+        st, ri = st[:n], ri[:n]
+        if isinstance(st, np.ndarray):
+            bad = (st == EMIT_BLOCKED) | ((st == 0) & (ri.view(np.uint64) != want.view(np.uint64)))
+            return np.where(bad, np.int32(QH_ERR_QPACK_DECOMPRESSION_FAILED), st).astype(np.int32)
+        import torch
+        bad = (st == EMIT_BLOCKED) | ((st == 0) & (ri != want))
+        return torch.where(bad, torch.full_like(st, QH_ERR_QPACK_DECOMPRESSION_FAILED), st)
+
+    def _cancel_blocked(self, sid, view):
+        new, ptr, size, head, tail, sfx = self._blk_io()
+        dev = self.codec is not None
+        fn = getattr(self._lib, "qh_dec_blocked_cancel_batch" if dev else "qh_qpack_dec_blocked_cancel")
+        n = size(sid)
+        removed = new(max(n, 1))
+        rv = fn(*head, ptr(sid), ptr(view), n, self.ntables, ptr(self.bq), ptr(self.blks), self.nblks,
+                ptr(removed), *tail)
+        return rv, removed[:n]
+
+    def cancel_blocked(self, cancel_sid, cancel_view, check=True):
+        """Host form (qh_qpack_dec_blocked_cancel): the queued sections of the
+        cancelled streams (uint64 ids, uint32 tables; a table's consecutive)
+        leave the queue.  -> removed (uint8: 1 where one was queued)."""
+        assert self.codec is None
+        rv, removed = self._cancel_blocked(np.ascontiguousarray(cancel_sid, dtype=np.uint64),
+                                           np.ascontiguousarray(cancel_view, dtype=np.uint32))
+        if check:
+            _lib.check(rv, "qh_qpack_dec_blocked_cancel")
+            return removed
+        return rv, removed
+
+    def cancel_blocked_dev(self, cancel_sid, cancel_view):
+        """qh_dec_blocked_cancel_batch (int64 ids, int32 tables): no host wait;
+        removed is 0xFF for the items of a table's second run or of a table
+        out of range, which remove nothing."""
+        assert self.codec is not None
+        rv, removed = self._cancel_blocked(cancel_sid, cancel_view)
+        _lib.check(rv, "qh_dec_blocked_cancel_batch")
+        return removed
+
+    def compact_blocked(self):
+        """Replaces ``blks`` and ``pend`` by logs that hold the queued records
+        of every table alone, back to back in table order, ``bq`` rebased.
+        When to call is the caller's decision: compare ``nblks`` and ``npend``
+        with what is queued.  A failed call leaves the object as it was."""
+        new, ptr, size, head, tail, sfx = self._blk_io()
+        dev = self.codec is not None
+        fn = getattr(self._lib,
+                     "qh_dec_blocked_compact_batch" if dev else "qh_qpack_dec_blocked_compact")
+        bq = self.bq.clone() if dev else self.bq.copy()
+
+        def call(q, recs, byts):
+            nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rv = fn(*head, None, self.ntables, self.ntables, ptr(q), ptr(self.blks), self.nblks,
+                    ptr(self.pend), self.npend, ptr(recs), ctypes.byref(nr), size(recs) // 32,
+                    ptr(byts), ctypes.byref(nb), size(byts), *tail)
+            return rv, int(nr.value), int(nb.value)
+        rv, nr, nb = call(bq, None, None)  # the sizing call
+        if rv != _lib.QH_ERR_NOMEM:
+            _lib.check(rv, "qh_dec_blocked_compact" + sfx)
+        caps = []
+        for need in (nr * 32, nb):
+            cap = 4096
+            while cap < need:
+                cap *= 2
+            caps.append(cap)
+        recs, byts = new(caps[0]), new(caps[1])
+        rv, nr, nb = call(bq, recs, byts)
+        _lib.check(rv, "qh_dec_blocked_compact" + sfx)
+        self.bq, self.blks, self.pend, self.nblks, self.npend = bq, recs, byts, nr, nb
+
+    def blocked_records(self):
+        """-> (bq DEC_BLKS_DTYPE [ntables], blks DEC_BLK_DTYPE [nblks], pend
+        uint8 [npend]): host copies of the queue state."""
+        self._blk_io()
+        h = (lambda a: a.copy()) if self.codec is None else (lambda t: t.cpu().numpy())
+        return (h(self.bq).view(DEC_BLKS_DTYPE), h(self.blks[:self.nblks * 32]).view(DEC_BLK_DTYPE),
+                h(self.pend[:self.npend]))
 
     def compact(self, extra_views=None):
         """Compacts the log (qh_dtables_compact_batch on the device form,
