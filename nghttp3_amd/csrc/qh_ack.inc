@@ -5,9 +5,10 @@
 // qh_ack.c.  The parser, the per-instruction checks and the writer's sizes and
 // bytes are qh_ack_core.h, the source the host functions compile; only the
 // steps that read many references are restated here, a 16-lane group at a
-// time, and the header's layout rules fix every record's and byte's place, so
-// flags, statuses, the log, the records and the stream bytes are equal byte
-// for byte.
+// time (qh_group.inc: the group, the table claim, the scan header and its
+// error flag), and the header's layout rules fix every record's and byte's
+// place, so flags, statuses, the log, the records and the stream bytes are
+// equal byte for byte.
 //
 //   sec_flags     qh_k_ack_flags, 16 lanes per connection: the listed streams
 //                 checked for a repeat, then per section the group scans the
@@ -17,7 +18,7 @@
 //   compact       gains, whether it moves, the records its region needs;
 //                 qh_k_scan_seg over those; (sync) the total and the error
 //                 flag; qh_k_ack_copy, a lane per output record (its
-//                 connection by a binary search, as qh_k_dtc_records): an old
+//                 connection by span_find): an old
 //                 reference copied or a new one formed, so connections with
 //                 unequal queues balance; qh_k_ack_rebase, a lane per
 //                 connection (its own launch: the copy reads the records it
@@ -43,8 +44,6 @@
 
 namespace qhk {
 
-constexpr uint32_t kAkLanes = 16;
-static_assert(kAkLanes == kPdLanes, "pd_group_ballot is shared");
 // LDS bytes per group of the reader: a stream that fits is staged, a longer
 // one (up to the 4 KiB the length rule lets through) is parsed from global
 // memory (measured at 512 and 4,096: DESIGN 3.11).
@@ -54,46 +53,8 @@ static_assert(kAkLanes == kPdLanes, "pd_group_ballot is shared");
 constexpr uint32_t kAkStage = QH_ACK_STAGE;
 constexpr uint32_t kAkReadThreads = 64;  // 4 groups
 
-// The header words ahead of a scan's tile states (as qh_encconn.inc's).
-enum : uint32_t { kAkCtr = 0, kAkTot = 1, kAkTimeouts = 5, kAkErr = 6, kAkHdr = 8 };
-
-__device__ __forceinline__ void ak_err(uint64_t *hdr) {
-  atomicExch(reinterpret_cast<unsigned long long *>(hdr + kAkErr), 1ull);
-}
 __device__ __forceinline__ bool ak_region_ok(const qh_enc_refs &v, uint64_t nrefs) {
   return v.base <= nrefs && v.n <= nrefs - v.base;
-}
-__device__ __forceinline__ unsigned long long ak_group_max64(unsigned long long v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kAkLanes; k <<= 1) {
-    const unsigned long long y = __shfl_xor(v, k, kAkLanes);
-    v = y > v ? y : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long ak_group_min64(unsigned long long v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kAkLanes; k <<= 1) {
-    const unsigned long long y = __shfl_xor(v, k, kAkLanes);
-    v = y < v ? y : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long ak_group_sum64(unsigned long long v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kAkLanes; k <<= 1) v += __shfl_xor(v, k, kAkLanes);
-  return v;
-}
-
-// The connection a group or lane serves: its table, claimed once per call
-// (owner: 0xFFFFFFFF per table on entry; NULL without a list).  false: the
-// index is out of range or the table is named twice.
-__device__ __forceinline__ bool ak_claim(const uint32_t *tsel, uint32_t *owner, uint64_t c,
-                                         uint64_t ntables, uint64_t *tt) {
-  *tt = tsel ? tsel[c] : c;
-  if (*tt >= ntables) return false;
-  if (tsel && atomicExch(&owner[*tt], (uint32_t)c) != 0xFFFFFFFFu) return false;
-  return true;
 }
 
 __global__ void __launch_bounds__(256) qh_k_ack_flags(
@@ -102,14 +63,14 @@ __global__ void __launch_bounds__(256) qh_k_ack_flags(
     const qh_enc_state *__restrict__ enc, const qh_enc_refs *__restrict__ rv,
     const qh_enc_ref *__restrict__ refs, uint64_t nrefs, uint8_t *__restrict__ sec_flags,
     int32_t *__restrict__ status, uint32_t *__restrict__ owner) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kAkLanes;
-  const uint32_t sl = threadIdx.x % kAkLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= nconns) return;  // (whole 16-lane groups)
   uint64_t tt = 0;
   int ok = 1;
-  if (sl == 0) ok = ak_claim(tsel, owner, c, ntables, &tt);
-  ok = __shfl(ok, 0, kAkLanes);
-  tt = __shfl((unsigned long long)tt, 0, kAkLanes);
+  if (sl == 0) ok = table_claim(tsel, owner, c, ntables, &tt);
+  ok = __shfl(ok, 0, kGroupLanes);
+  tt = __shfl((unsigned long long)tt, 0, kGroupLanes);
   const uint64_t s0 = conn_start[c], s1 = conn_start[c + 1];
   if (s0 > s1 || s1 > nsec) {  // (nothing is indexed outside its array)
     if (sl == 0) status[c] = QH_ERR_INVALID_ARGUMENT;
@@ -123,11 +84,11 @@ __global__ void __launch_bounds__(256) qh_k_ack_flags(
     ok = ak_region_ok(v, nrefs);
   }
   bool rep = false;  // a stream listed twice
-  for (uint64_t s = s0 + sl; s < s1 && ok; s += kAkLanes) {
+  for (uint64_t s = s0 + sl; s < s1 && ok; s += kGroupLanes) {
     const uint64_t sid = sec_sid[s];
     for (uint64_t s2 = s0; s2 < s && !rep; ++s2) rep = sec_sid[s2] == sid;
   }
-  if (pd_group_ballot(rep)) ok = 0;
+  if (group_ballot(rep)) ok = 0;
   if (sl == 0) status[c] = ok ? 0 : QH_ERR_INVALID_ARGUMENT;
   for (uint64_t s = s0; s < s1; ++s) {
     uint8_t fl = 0;
@@ -135,15 +96,15 @@ __global__ void __launch_bounds__(256) qh_k_ack_flags(
       const uint64_t sid = sec_sid[s];
       unsigned long long mx = 0;
       bool known = false;
-      for (uint64_t i = sl; i < v.n; i += kAkLanes) {
+      for (uint64_t i = sl; i < v.n; i += kGroupLanes) {
         const qh_enc_ref r = refs[v.base + i];
         if (r.stream_id == sid) {
           known = true;
           mx = r.max_cnt > mx ? r.max_cnt : mx;
         }
       }
-      mx = ak_group_max64(mx);
-      if (pd_group_ballot(known))
+      mx = group_max64(mx);
+      if (group_ballot(known))
         fl = (uint8_t)(QH_ENC_SEC_STREAM_KNOWN | (mx > krcnt ? QH_ENC_SEC_STREAM_BLOCKED : 0));
     }
     if (sl == 0) sec_flags[s] = fl;
@@ -177,8 +138,8 @@ __global__ void __launch_bounds__(256) qh_k_ack_count(const AkRec a) {
   if (c >= a.nconns) return;
   uint64_t tt;
   SpanOut o = {0, 0, 0};
-  if (!ak_claim(a.tsel, a.owner, c, a.ntables, &tt)) {
-    ak_err(a.hdr);
+  if (!table_claim(a.tsel, a.owner, c, a.ntables, &tt)) {
+    hdr_err(a.hdr);
     o.status = -1;  // (not to be touched)
     a.cnt[c] = o;
     return;
@@ -203,7 +164,7 @@ __global__ void __launch_bounds__(256) qh_k_ack_count(const AkRec a) {
   }
   if (len > 0xFFFFFFFFull) ok = false;  // (one scan item)
   if (!ok) {
-    ak_err(a.hdr);
+    hdr_err(a.hdr);
     o.status = -1;
     len = 0;
   }
@@ -215,13 +176,7 @@ __global__ void __launch_bounds__(256) qh_k_ack_count(const AkRec a) {
 __global__ void __launch_bounds__(256) qh_k_ack_copy(const AkRec a, uint64_t total) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= total) return;
-  // the last connection whose offset is <= r: the ones before it with the same offset are empty
-  uint64_t lo = 0, hi = a.nconns;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a.cnt[mid].off <= r) lo = mid;
-    else hi = mid;
-  }
+  const uint64_t lo = span_find(a.cnt, a.nconns, r);  // its connection
   const uint64_t tt = a.tsel ? a.tsel[lo] : lo;
   const qh_enc_refs v = a.rv[tt];
   uint64_t k = r - a.cnt[lo].off;
@@ -268,16 +223,16 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
     const qh_dtable_view *__restrict__ views, qh_enc_state *__restrict__ enc,
     qh_enc_refs *__restrict__ rv, qh_enc_ref *__restrict__ refs, uint64_t nrefs,
     int32_t *__restrict__ status, uint32_t *__restrict__ consumed, uint32_t *__restrict__ owner) {
-  __shared__ uint8_t s_stage[kAkReadThreads / kAkLanes][kAkStage];
-  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kAkLanes;
-  const uint32_t sl = threadIdx.x % kAkLanes;
+  __shared__ uint8_t s_stage[kAkReadThreads / kGroupLanes][kAkStage];
+  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (p >= nsel) return;  // (whole 16-lane groups; the kernel has no barrier)
-  uint8_t *const stage = s_stage[threadIdx.x / kAkLanes];
+  uint8_t *const stage = s_stage[threadIdx.x / kGroupLanes];
   uint64_t tt = 0;
   int ok = 1;
-  if (sl == 0) ok = ak_claim(tsel, owner, p, ntables, &tt);
-  ok = __shfl(ok, 0, kAkLanes);
-  tt = __shfl((unsigned long long)tt, 0, kAkLanes);
+  if (sl == 0) ok = table_claim(tsel, owner, p, ntables, &tt);
+  ok = __shfl(ok, 0, kGroupLanes);
+  tt = __shfl((unsigned long long)tt, 0, kGroupLanes);
   qh_enc_refs v = {0, 0, 0, 0};
   if (ok) {
     v = rv[tt];
@@ -303,7 +258,7 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
   // (len <= 4096 here: dlen + len passed the rule)
   const bool staged = sp.len <= kAkStage;
   if (staged) {
-    for (uint32_t k = sl; k < sp.len; k += kAkLanes) stage[k] = src[sp.off + k];
+    for (uint32_t k = sl; k < sp.len; k += kGroupLanes) stage[k] = src[sp.off + k];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -326,12 +281,12 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
         rc = qh_ack_add_icnt(&e.krcnt, insert_count, val);
       } else {  // qh_ack_apply by the group, oldest first
         rc = op == QH_DS_SECTION_ACK ? QH_ERR_QPACK_DECODER_STREAM_ERROR : 0;
-        for (uint64_t i0 = 0; i0 < v.n; i0 += kAkLanes) {
+        for (uint64_t i0 = 0; i0 < v.n; i0 += kGroupLanes) {
           const uint64_t i = i0 + sl;
           qh_enc_ref x = {0, 0, 0, QH_ENC_REF_GONE};
           if (i < v.n) x = r[i];
           const bool hit = x.reserved != QH_ENC_REF_GONE && x.stream_id == val;
-          const uint32_t m = pd_group_ballot(hit);
+          const uint32_t m = group_ballot(hit);
           if (op == QH_DS_STREAM_CANCEL) {
             if (hit) r[i].reserved = QH_ENC_REF_GONE;
             continue;
@@ -339,7 +294,7 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
           if (m) {
             const uint32_t j = (uint32_t)__ffs((int)m) - 1;
             if (sl == j) r[i].reserved = QH_ENC_REF_GONE;
-            const uint64_t mx = __shfl((unsigned long long)x.max_cnt, (int)j, kAkLanes);
+            const uint64_t mx = __shfl((unsigned long long)x.max_cnt, (int)j, kGroupLanes);
             if (e.krcnt < mx) e.krcnt = mx;
             rc = 0;
             break;
@@ -360,12 +315,12 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
 
   if (any) {  // qh_ack_squeeze: a round's sixteen are all read before one is stored
     uint64_t k = 0;
-    for (uint64_t i0 = 0; i0 < v.n; i0 += kAkLanes) {
+    for (uint64_t i0 = 0; i0 < v.n; i0 += kGroupLanes) {
       const uint64_t i = i0 + sl;
       qh_enc_ref x = {0, 0, 0, QH_ENC_REF_GONE};
       if (i < v.n) x = r[i];
       const bool keep = x.reserved != QH_ENC_REF_GONE;
-      const uint32_t m = pd_group_ballot(keep);
+      const uint32_t m = group_ballot(keep);
       const uint64_t to = k + __popc(m & ((1u << sl) - 1u));
       if (keep && to != i) r[to] = x;
       k += __popc(m);
@@ -379,7 +334,7 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
 
   // qh_ack_scalars: lane sl takes the references i = sl mod 16
   unsigned long long pin = UINT64_MAX, ns = 0, nb = 0;
-  for (uint64_t i = sl; i < v.n; i += kAkLanes) {
+  for (uint64_t i = sl; i < v.n; i += kGroupLanes) {
     const qh_enc_ref x = r[i];
     pin = x.min_cnt < pin ? x.min_cnt : pin;
     bool first = true;
@@ -393,9 +348,9 @@ __global__ void __launch_bounds__(kAkReadThreads) qh_k_ack_read(
     ++ns;
     nb += mx > e.krcnt;
   }
-  e.pin_min = ak_group_min64(pin);
-  e.nstreams = ak_group_sum64(ns);
-  e.nblocked = ak_group_sum64(nb);
+  e.pin_min = group_min64(pin);
+  e.nstreams = group_sum(ns);
+  e.nblocked = group_sum(nb);
   if (sl == 0) {
     enc[tt] = e;
     rv[tt] = v;
@@ -450,11 +405,11 @@ __global__ void __launch_bounds__(256) qh_k_ackw_size(const AkW a) {
   const uint32_t t = view[k];
   uint32_t len = 0;
   if (t >= a.ntables) {
-    ak_err(a.hdr_t);
+    hdr_err(a.hdr_t);
   } else {
     AkTab *const x = &a.tab[t];
     if (k == 0 || view[k - 1] != t) {  // a run starts: one per table and list
-      if (atomicAdd(blk ? &x->nbrun : &x->ncrun, 1u) != 0) ak_err(a.hdr_t);
+      if (atomicAdd(blk ? &x->nbrun : &x->ncrun, 1u) != 0) hdr_err(a.hdr_t);
       *(blk ? &x->b0 : &x->c0) = (uint32_t)k;
     }
     if (k + 1 == (blk ? a.nblocks : a.ncancel) || view[k + 1] != t)
@@ -471,7 +426,7 @@ __global__ void __launch_bounds__(256) qh_k_ackw_size(const AkW a) {
 
 // item[i].off after the scan; past the last item: the total.
 __device__ __forceinline__ uint64_t akw_pos(const AkW &a, uint64_t i) {
-  return i < a.nblocks + a.ncancel ? a.item[i].off : a.hdr_i[kAkTot];
+  return i < a.nblocks + a.ncancel ? a.item[i].off : a.hdr_i[kHdrTot];
 }
 
 __global__ void __launch_bounds__(256) qh_k_ackw_tables(const AkW a) {
@@ -483,7 +438,7 @@ __global__ void __launch_bounds__(256) qh_k_ackw_tables(const AkW a) {
   if (x.c1 > x.c0) n += akw_pos(a, a.nblocks + x.c1) - akw_pos(a, a.nblocks + x.c0);
   n += qh_ack_icnt_len(x.w, a.views[t].insert_count);
   if (n > 0xFFFFFFFFull) {  // (one scan item, a span's length)
-    ak_err(a.hdr_t);
+    hdr_err(a.hdr_t);
     n = 0;
   }
   a.tlen[t].len = (uint32_t)n;
@@ -524,16 +479,6 @@ __global__ void __launch_bounds__(256) qh_k_ackw_write(const AkW a) {
 
 }  // namespace qhk
 
-namespace {
-
-// The owner words of a call with a table list: 0xFFFFFFFF each on entry.
-int ack_owner(qh_ctx *c, const uint32_t *tsel, size_t ntables, uint32_t *owner) {
-  if (tsel && ntables) QH_HIP(hipMemsetAsync(owner, 0xFF, ntables * 4, c->stream));
-  return 0;
-}
-
-}  // namespace
-
 QH_EXPORT int qh_enc_sec_flags_batch(qh_ctx *c, const uint64_t *sec_sid, size_t nsections,
                                      const uint32_t *conn_start, size_t nconns,
                                      const uint32_t *tsel, size_t ntables, const qh_enc_state *enc,
@@ -549,14 +494,10 @@ QH_EXPORT int qh_enc_sec_flags_batch(qh_ctx *c, const uint64_t *sec_sid, size_t 
   if (nconns == 0) return nsections ? QH_ERR_INVALID_ARGUMENT : 0;
   uint32_t *owner = nullptr;
   r = reserve_layout(c, kBufAck, [&](qhs::Layout &l) { owner = l.take<uint32_t>(ntables); });
-  if (r || (r = ack_owner(c, tsel, ntables, owner))) return r;
-  Timed t(c, "qh_k_ack_flags");
-  const unsigned grid = (unsigned)(((uint64_t)nconns * qhk::kAkLanes + 255) / 256);
-  hipLaunchKernelGGL(qhk::qh_k_ack_flags, dim3(grid), dim3(256), 0, c->stream, sec_sid,
-                     (uint64_t)nsections, conn_start, (uint64_t)nconns, tsel, (uint64_t)ntables, enc,
-                     rv, refs, nrefs, sec_flags, status, owner);
-  QH_HIP(hipGetLastError());
-  return 0;
+  if (r || (r = table_owner_reset(c, tsel, ntables, owner))) return r;
+  return QH_LAUNCH(c, qh_k_ack_flags, (uint64_t)nconns * qhk::kGroupLanes, 256, sec_sid,
+                   (uint64_t)nsections, conn_start, (uint64_t)nconns, tsel, (uint64_t)ntables, enc,
+                   rv, refs, nrefs, sec_flags, status, owner);
 }
 
 namespace {
@@ -564,43 +505,25 @@ namespace {
 // The relocation pass over a source and a destination log: count, scan, the
 // one wait, then (when the destination holds) copy and rebase.
 int ack_relocate(qh_ctx *c, qhk::AkRec &a, uint64_t out_cap, uint64_t *total) {
-  const uint64_t tps = (a.nconns + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kAkHdr + tps;
+  const uint64_t tiles = (a.nconns + qhk::kScanTile - 1) / qhk::kScanTile;
   int r = reserve_layout(c, kBufAck, [&](qhs::Layout &l) {
     a.cnt = l.take<qhk::SpanOut>(a.nconns);
     a.owner = l.take<uint32_t>(a.ntables);
-    a.hdr = l.take<uint64_t>(hwords);
+    a.hdr = l.take<uint64_t>(qhk::kHdrWords + tiles);
   });
   if (r) return r;
-  if ((r = reserve(c, kBufAckHost, 8 * sizeof(uint64_t), qhs::kExact))) return r;
-  uint64_t *h = mem<uint64_t>(c, kBufAckHost);
-  QH_HIP(hipMemsetAsync(a.hdr, 0, hwords * sizeof(uint64_t), c->stream));
-  if ((r = ack_owner(c, a.tsel, a.ntables, a.owner))) return r;
-  const unsigned grid = (unsigned)((a.nconns + 255) / 256);
-  {
-    Timed t(c, "qh_k_ack_count");
-    hipLaunchKernelGGL(qhk::qh_k_ack_count, dim3(grid), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((r = launch_scan_seg(c, a.cnt, a.nconns, 1, a.hdr, qhk::kAkHdr, qhk::kAkTot, qhk::kAkTimeouts)))
-    return r;
-  QH_HIP(hipMemcpyAsync(h, a.hdr + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  QH_HIP(hipStreamSynchronize(c->stream));  // the wait
-  if ((r = scan_seg_check(h[qhk::kAkTimeouts - 1], "reference-log"))) return r;
-  if (h[qhk::kAkErr - 1]) return QH_ERR_INVALID_ARGUMENT;
-  *total = h[qhk::kAkTot - 1];
+  uint64_t *h;
+  if ((r = scan_hdr_host(c, &h))) return r;
+  if ((r = scan_hdr_reset(c, a.hdr, tiles))) return r;
+  if ((r = table_owner_reset(c, a.tsel, a.ntables, a.owner))) return r;
+  if ((r = QH_LAUNCH(c, qh_k_ack_count, a.nconns, 256, a))) return r;
+  if ((r = launch_scan_seg(c, a.cnt, a.nconns, 1, a.hdr))) return r;
+  if ((r = scan_hdr_wait(c, a.hdr, h, "reference-log"))) return r;  // the wait
+  *total = h[qhk::kHdrTot - 1];
   if (*total > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;  // (grid)
   if (a.at + *total > out_cap) return QH_ERR_NOMEM;
-  if (*total) {
-    Timed t(c, "qh_k_ack_copy");
-    hipLaunchKernelGGL(qhk::qh_k_ack_copy, dim3((unsigned)((*total + 255) / 256)), dim3(256), 0,
-                       c->stream, a, *total);
-    QH_HIP(hipGetLastError());
-  }
-  Timed t(c, "qh_k_ack_rebase");
-  hipLaunchKernelGGL(qhk::qh_k_ack_rebase, dim3(grid), dim3(256), 0, c->stream, a);
-  QH_HIP(hipGetLastError());
-  return 0;
+  if (*total && (r = QH_LAUNCH(c, qh_k_ack_copy, *total, 256, a, *total))) return r;
+  return QH_LAUNCH(c, qh_k_ack_rebase, a.nconns, 256, a);
 }
 
 }  // namespace
@@ -685,15 +608,10 @@ QH_EXPORT int qh_enc_read_decoder_batch(qh_ctx *c, const uint8_t *src, const qh_
   if (nsel == 0) return 0;
   uint32_t *owner = nullptr;
   r = reserve_layout(c, kBufAck, [&](qhs::Layout &l) { owner = l.take<uint32_t>(ntables); });
-  if (r || (r = ack_owner(c, tsel, ntables, owner))) return r;
-  Timed t(c, "qh_k_ack_read");
-  const unsigned grid =
-      (unsigned)(((uint64_t)nsel * qhk::kAkLanes + qhk::kAkReadThreads - 1) / qhk::kAkReadThreads);
-  hipLaunchKernelGGL(qhk::qh_k_ack_read, dim3(grid), dim3(qhk::kAkReadThreads), 0, c->stream, src,
-                     reinterpret_cast<const qhk::SpanIn *>(streams), tsel, (uint64_t)nsel,
-                     (uint64_t)ntables, views, enc, rv, refs, nrefs, status, consumed, owner);
-  QH_HIP(hipGetLastError());
-  return 0;
+  if (r || (r = table_owner_reset(c, tsel, ntables, owner))) return r;
+  return QH_LAUNCH(c, qh_k_ack_read, (uint64_t)nsel * qhk::kGroupLanes, qhk::kAkReadThreads, src,
+                   reinterpret_cast<const qhk::SpanIn *>(streams), tsel, (uint64_t)nsel,
+                   (uint64_t)ntables, views, enc, rv, refs, nrefs, status, consumed, owner);
 }
 
 QH_EXPORT int qh_dec_write_decoder_batch(qh_ctx *c, const uint64_t *block_sid,
@@ -717,18 +635,17 @@ QH_EXPORT int qh_dec_write_decoder_batch(qh_ctx *c, const uint64_t *block_sid,
   const uint64_t nitems = (uint64_t)nblocks + ncancel;
   const uint64_t tps_i = (nitems + qhk::kScanTile - 1) / qhk::kScanTile;
   const uint64_t tps_t = (ntables + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = 2 * qhk::kAkHdr + tps_i + tps_t;
   qhk::AkW a{};
   r = reserve_layout(c, kBufAck, [&](qhs::Layout &l) {
     a.tab = l.take<qhk::AkTab>(ntables);
     a.item = l.take<qhk::SpanOut>(nitems);
     a.tlen = l.take<qhk::SpanOut>(ntables);
-    a.hdr_i = l.take<uint64_t>(hwords);
+    a.hdr_i = l.take<uint64_t>(2 * qhk::kHdrWords + tps_i + tps_t);
   });
   if (r) return r;
-  a.hdr_t = a.hdr_i + qhk::kAkHdr + tps_i;
-  if ((r = reserve(c, kBufAckHost, 8 * sizeof(uint64_t), qhs::kExact))) return r;
-  uint64_t *h = mem<uint64_t>(c, kBufAckHost);
+  a.hdr_t = a.hdr_i + qhk::kHdrWords + tps_i;
+  uint64_t *h;
+  if ((r = scan_hdr_host(c, &h))) return r;
   a.block_sid = block_sid;
   a.block_view = block_view;
   a.status = status;
@@ -742,43 +659,19 @@ QH_EXPORT int qh_dec_write_decoder_batch(qh_ctx *c, const uint64_t *block_sid,
   a.written_icnt = written_icnt;
   a.dst = dst;
   a.dstreams = reinterpret_cast<qhk::SpanIn *>(dstreams);
-  QH_HIP(hipMemsetAsync(a.hdr_i, 0, hwords * sizeof(uint64_t), c->stream));
-  const unsigned grid_t = (unsigned)((ntables + 255) / 256);
-  {
-    Timed t(c, "qh_k_ackw_init");
-    hipLaunchKernelGGL(qhk::qh_k_ackw_init, dim3(grid_t), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
+  // (both headers with one memset: they lie side by side)
+  if ((r = scan_hdr_reset(c, a.hdr_i, qhk::kHdrWords + tps_i + tps_t))) return r;
+  if ((r = QH_LAUNCH(c, qh_k_ackw_init, ntables, 256, a))) return r;
   if (nitems) {
-    {
-      Timed t(c, "qh_k_ackw_size");
-      hipLaunchKernelGGL(qhk::qh_k_ackw_size, dim3((unsigned)((nitems + 255) / 256)), dim3(256), 0,
-                         c->stream, a);
-      QH_HIP(hipGetLastError());
-    }
-    if ((r = launch_scan_seg(c, a.item, nitems, 1, a.hdr_i, qhk::kAkHdr, qhk::kAkTot,
-                             qhk::kAkTimeouts)))
-      return r;
+    if ((r = QH_LAUNCH(c, qh_k_ackw_size, nitems, 256, a))) return r;
+    if ((r = launch_scan_seg(c, a.item, nitems, 1, a.hdr_i))) return r;
   }
-  {
-    Timed t(c, "qh_k_ackw_tables");
-    hipLaunchKernelGGL(qhk::qh_k_ackw_tables, dim3(grid_t), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((r = launch_scan_seg(c, a.tlen, ntables, 1, a.hdr_t, qhk::kAkHdr, qhk::kAkTot,
-                           qhk::kAkTimeouts)))
-    return r;
-  QH_HIP(hipMemcpyAsync(h, a.hdr_t + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  QH_HIP(hipMemcpyAsync(h + 7, a.hdr_i + qhk::kAkTimeouts, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                        c->stream));
-  QH_HIP(hipStreamSynchronize(c->stream));  // the wait
-  if ((r = scan_seg_check(h[qhk::kAkTimeouts - 1] | h[7], "decoder-stream"))) return r;
-  if (h[qhk::kAkErr - 1]) return QH_ERR_INVALID_ARGUMENT;
-  *dst_need = h[qhk::kAkTot - 1];
+  if ((r = QH_LAUNCH(c, qh_k_ackw_tables, ntables, 256, a))) return r;
+  if ((r = launch_scan_seg(c, a.tlen, ntables, 1, a.hdr_t))) return r;
+  // the wait: the tables' total and error flag, both scans' time-outs
+  if ((r = scan_hdr_wait2(c, a.hdr_t, a.hdr_i, h, "decoder-stream"))) return r;
+  if (h[qhk::kHdrErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  *dst_need = h[qhk::kHdrTot - 1];
   if (*dst_need > dst_cap) return QH_ERR_NOMEM;
-  Timed t(c, "qh_k_ackw_write");
-  hipLaunchKernelGGL(qhk::qh_k_ackw_write, dim3((unsigned)((nitems + ntables + 255) / 256)),
-                     dim3(256), 0, c->stream, a);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_ackw_write, nitems + ntables, 256, a);
 }

@@ -52,11 +52,7 @@ enum BufId {
   kBufEnds,        // host pipelines: a slice's dense end (64 words)
   kBufEncSecHost,  // the sections encoder's totals read back (8 words)
   kBufEmitHost,    // field emission's totals read back (8 words)
-  kBufDtsetHost,   // the table set's totals read back (8 words)
-  kBufDtcHost,     // compaction's totals read back (16 words)
-  kBufEncConnHost,  // the connection encoder's totals read back (8 words)
-  kBufAckHost,      // the acknowledgement calls' totals read back (8 words)
-  kBufBlockedHost,  // the blocked-section calls' totals read back (8 words)
+  kBufScanHost,    // scan_hdr_host: a state call's scan headers read back (16 words: two headers)
   kNumBuf
 };
 
@@ -254,6 +250,22 @@ struct Timed {
   }
 };
 
+// A kernel launched on the context's stream, no dynamic LDS, timed under its
+// own name: ceil(lanes / block) workgroups (QH_LAUNCH), or `grid` of them
+// (QH_LAUNCH_GRID).  The name is the kernel's symbol.
+template <class K, class... A>
+int launch_grid(qh_ctx *c, const char *name, K kernel, uint64_t grid, unsigned block, A &&...args) {
+  // (the batch validators' limit; every other caller bounds its counts below it first)
+  if (grid > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
+  Timed t(c, name);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, c->stream, std::forward<A>(args)...);
+  QH_HIP(hipGetLastError());
+  return 0;
+}
+#define QH_LAUNCH_GRID(c, k, grid, block, ...) launch_grid(c, #k, qhk::k, grid, block, __VA_ARGS__)
+#define QH_LAUNCH(c, k, lanes, block, ...) \
+  QH_LAUNCH_GRID(c, k, ((uint64_t)(lanes) + (block) - 1) / (block), block, __VA_ARGS__)
+
 int ensure_tile_state(qh_ctx *c, uint64_t n) {
   const size_t tiles = (size_t)((n + kScanTile - 1) / kScanTile) + 1;
   return reserve(c, kBufTileState, (tiles + 2) * sizeof(uint64_t), qhs::Policy{1024 * sizeof(uint64_t)});
@@ -270,11 +282,7 @@ int launch_scan(qh_ctx *c, const SpanIn *in, SpanOut *out, uint64_t n) {
   QH_HIP(hipMemsetAsync(ts, 0, (tiles + 1) * sizeof(uint64_t), c->stream));
   uint32_t *ctr = reinterpret_cast<uint32_t *>(ts);
   uint64_t *states = ts + 1;
-  Timed t(c, "qh_k_scan");
-  hipLaunchKernelGGL(qh_k_scan, dim3((unsigned)tiles), dim3(kBlock), 0,
-                     c->stream, in, out, n, states, ctr, c->d_stats);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH_GRID(c, qh_k_scan, tiles, kBlock, in, out, n, states, ctr, c->d_stats);
 }
 
 // qh_k_scan_seg over nseg segments of n entries each.  hdr (zeroed by the
@@ -283,19 +291,57 @@ int launch_scan(qh_ctx *c, const SpanIn *in, SpanOut *out, uint64_t n) {
 int launch_scan_seg(qh_ctx *c, qhk::SpanOut *out, uint64_t n, uint32_t nseg, uint64_t *hdr,
                     uint64_t states, uint64_t tot, uint64_t timeouts) {
   const uint64_t tps = (n + qhk::kScanTile - 1) / qhk::kScanTile;
-  Timed t(c, "qh_k_scan_seg");
-  hipLaunchKernelGGL(qhk::qh_k_scan_seg, dim3((unsigned)(nseg * tps)), dim3(qhk::kBlock), 0,
-                     c->stream, out, n, nseg, hdr + states, reinterpret_cast<uint32_t *>(hdr),
-                     reinterpret_cast<unsigned long long *>(hdr + tot),
-                     reinterpret_cast<unsigned long long *>(hdr + timeouts));
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH_GRID(c, qh_k_scan_seg, nseg * tps, qhk::kBlock, out, n, nseg, hdr + states,
+                        reinterpret_cast<uint32_t *>(hdr),
+                        reinterpret_cast<unsigned long long *>(hdr + tot),
+                        reinterpret_cast<unsigned long long *>(hdr + timeouts));
+}
+// ... over the shared header (qh_group.inc kHdr*).
+int launch_scan_seg(qh_ctx *c, qhk::SpanOut *out, uint64_t n, uint32_t nseg, uint64_t *hdr) {
+  return launch_scan_seg(c, out, n, nseg, hdr, qhk::kHdrWords, qhk::kHdrTot, qhk::kHdrTimeouts);
 }
 // The read-back `timeouts` word of such a scan: an error when not 0.
 int scan_seg_check(uint64_t timeouts, const char *what) {
   if (!timeouts) return 0;
   fprintf(stderr, "qhuff: %s scan look-back timed out\n", what);
   return QH_ERR_FATAL;
+}
+
+// The shared header of `tiles` tile states, zeroed.
+int scan_hdr_reset(qh_ctx *c, uint64_t *hdr, uint64_t tiles) {
+  QH_HIP(hipMemsetAsync(hdr, 0, (qhk::kHdrWords + tiles) * sizeof(uint64_t), c->stream));
+  return 0;
+}
+// Where the waits below leave a call's header words: pinned, 16 words.  Every
+// caller waits on the context's stream and has read the words before it
+// returns or calls on, so one buffer serves them all.
+int scan_hdr_host(qh_ctx *c, uint64_t **h) {
+  const int r = reserve(c, kBufScanHost, 2 * qhk::kHdrWords * sizeof(uint64_t), qhs::kExact);
+  *h = mem<uint64_t>(c, kBufScanHost);
+  return r;
+}
+// The wait on two headers (hdr2 may be NULL): words 1-7 of hdr to h[0, 7),
+// of hdr2 to h[8, 15), one synchronise, then the scans' time-outs.  The error
+// flags (h[kHdrErr - 1], h[8 + kHdrErr - 1]) are left to the caller.
+int scan_hdr_wait2(qh_ctx *c, const uint64_t *hdr, const uint64_t *hdr2, uint64_t *h,
+                   const char *what) {
+  QH_HIP(hipMemcpyAsync(h, hdr + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  if (hdr2) QH_HIP(hipMemcpyAsync(h + 8, hdr2 + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  QH_HIP(hipStreamSynchronize(c->stream));
+  return scan_seg_check(h[qhk::kHdrTimeouts - 1] | (hdr2 ? h[8 + qhk::kHdrTimeouts - 1] : 0), what);
+}
+// The wait on one header: its time-outs, then its error flag
+// (QH_ERR_INVALID_ARGUMENT); the totals are h[0] on.
+int scan_hdr_wait(qh_ctx *c, const uint64_t *hdr, uint64_t *h, const char *what) {
+  const int r = scan_hdr_wait2(c, hdr, nullptr, h, what);
+  if (r) return r;
+  return h[qhk::kHdrErr - 1] ? QH_ERR_INVALID_ARGUMENT : 0;
+}
+// The owner words of a call with a table list (qh_group.inc table_claim):
+// 0xFFFFFFFF each on entry.
+int table_owner_reset(qh_ctx *c, const uint32_t *tsel, size_t ntables, uint32_t *owner) {
+  if (tsel && ntables) QH_HIP(hipMemsetAsync(owner, 0xFF, ntables * 4, c->stream));
+  return 0;
 }
 
 int reset_stats(qh_ctx *c, uint64_t n) {

@@ -3,9 +3,10 @@
 // qh_dec_blocked_cancel_batch, qh_dec_blocked_compact_batch): the device twins
 // of qh_blocked.c.  The per-record rules are qh_blocked_core.h, the source
 // the host functions compile; only the steps that read many records are
-// restated here, a 16-lane group at a time, and the header's layout rules fix
-// every record's and byte's place, so the logs, the table records and every
-// output are equal byte for byte.
+// restated here, a 16-lane group at a time (qh_group.inc: the group, the
+// table claim, the scan header and its error flag), and the header's layout
+// rules fix every record's and byte's place, so the logs, the table records
+// and every output are equal byte for byte.
 //
 //   push     qh_k_blk_runs, a lane per position: the run of each table (one
 //            per table, else the error flag), the counts zeroed;
@@ -15,16 +16,15 @@
 //            segments (records, bytes, accepted blocks); (sync) the totals and
 //            the error flag; qh_k_blk_fill, a lane per position: the verdict,
 //            the flat list of new records with their byte prefix sums;
-//            qh_k_blk_copy, a lane per output record (its table by a binary
-//            search, as qh_k_ack_copy); qh_k_blk_bytes, a lane per 16-byte
-//            piece of the new bytes (its record by a binary search over the
-//            prefix sums, so one long section and many short ones balance);
+//            qh_k_blk_copy, a lane per output record (its table by
+//            span_find); qh_k_blk_bytes, a lane per 16-byte piece of the new
+//            bytes (its record by span_find over the prefix sums, so one long
+//            section and many short ones balance);
 //            qh_k_blk_rebase.
 //   release  qh_k_blk_relcount, 16 lanes per table; qh_k_scan_seg; (sync);
 //            qh_k_blk_relwrite, 16 lanes per table: ranks (the rounds that
 //            release nothing skipped), outputs, then the
-//            in-place squeeze (a round's sixteen loaded before one is stored,
-//            as qh_k_ack_read).
+//            in-place squeeze (a round's sixteen loaded before one is stored).
 //   cancel   qh_k_blk_cruns (the first run of a table owns it),
 //            qh_k_blk_cancel, 16 lanes per run.  No host wait.
 //   compact  qh_k_blk_ccount, 16 lanes per table: records, bytes, each
@@ -37,34 +37,7 @@
 
 namespace qhk {
 
-constexpr uint32_t kBkLanes = 16;
-static_assert(kBkLanes == kPdLanes, "pd_group_ballot is shared");
 constexpr uint32_t kBkNone = 0xFFFFFFFFu;
-
-// The header words ahead of a scan's tile states: the totals of up to three
-// segments from kBkTot on.
-enum : uint32_t { kBkCtr = 0, kBkTot = 1, kBkTimeouts = 5, kBkErr = 6, kBkHdr = 8 };
-
-__device__ __forceinline__ unsigned long long bk_group_incl64(unsigned long long v, uint32_t sl) {
-#pragma unroll
-  for (uint32_t k = 1; k < kBkLanes; k <<= 1) {
-    const unsigned long long y = __shfl_up(v, k, kBkLanes);
-    if (sl >= k) v += y;
-  }
-  return v;
-}
-
-// The last i in [0, n) with a[i].off <= x (the entries before it with the
-// same offset are empty).  n > 0 and a[0].off == 0.
-__device__ __forceinline__ uint64_t bk_find(const SpanOut *a, uint64_t n, uint64_t x) {
-  uint64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a[mid].off <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // Whether a record of r[0, n) has the lane's stream id: the group loads
 // sixteen records at a time, every lane compares its own id with the sixteen.
@@ -72,12 +45,12 @@ __device__ __forceinline__ uint64_t bk_find(const SpanOut *a, uint64_t n, uint64
 __device__ __forceinline__ bool bk_group_has_sid(const qh_dec_blk *r, uint64_t n,
                                                  unsigned long long sid, uint32_t sl) {
   bool has = false;
-  for (uint64_t i0 = 0; i0 < n; i0 += kBkLanes) {
+  for (uint64_t i0 = 0; i0 < n; i0 += kGroupLanes) {
     const uint64_t i = i0 + sl;
     const unsigned long long s = i < n ? r[i].stream_id : 0;
-    const uint32_t left = n - i0 < kBkLanes ? (uint32_t)(n - i0) : kBkLanes;
+    const uint32_t left = n - i0 < kGroupLanes ? (uint32_t)(n - i0) : kGroupLanes;
 #pragma unroll
-    for (uint32_t l = 0; l < kBkLanes; ++l) has |= l < left && __shfl(s, (int)l, kBkLanes) == sid;
+    for (uint32_t l = 0; l < kGroupLanes; ++l) has |= l < left && __shfl(s, (int)l, kGroupLanes) == sid;
   }
   return has;
 }
@@ -88,13 +61,13 @@ __device__ __forceinline__ bool bk_group_has_sid(const qh_dec_blk *r, uint64_t n
 template <class Keep>
 __device__ __forceinline__ uint64_t bk_squeeze(qh_dec_blk *r, uint64_t n, uint32_t sl, Keep keep) {
   uint64_t k = 0;
-  for (uint64_t i0 = 0; i0 < n; i0 += kBkLanes) {
+  for (uint64_t i0 = 0; i0 < n; i0 += kGroupLanes) {
     const uint64_t i = i0 + sl;
     qh_dec_blk x = {0, 0, 0, 0, 0};
     if (i < n) x = r[i];
     const bool kp = keep(i, x);  // (every lane calls it: its loops are uniform)
     const bool stay = i < n && kp;
-    const uint32_t m = pd_group_ballot(stay);
+    const uint32_t m = group_ballot(stay);
     const uint64_t to = k + __popc(m & ((1u << sl) - 1u));
     if (stay && to != i) r[to] = x;
     k += __popc(m);
@@ -145,12 +118,12 @@ __global__ void __launch_bounds__(256) qh_k_blk_runs(const BkPush a) {
   a.pb0[p] = 0;
   const uint32_t t = a.view[p];
   if (t >= a.ntables) {
-    ak_err(a.hdr);
+    hdr_err(a.hdr);
     return;
   }
   BkTab *const x = &a.tab[t];
   if (p == 0 || a.view[p - 1] != t) {  // a run starts: one per table
-    if (atomicAdd(&x->nrun, 1u) != 0) ak_err(a.hdr);
+    if (atomicAdd(&x->nrun, 1u) != 0) hdr_err(a.hdr);
     x->b0 = (uint32_t)p;
   }
   if (p + 1 == a.nblocks || a.view[p + 1] != t) x->b1 = (uint32_t)p + 1;
@@ -159,21 +132,21 @@ __global__ void __launch_bounds__(256) qh_k_blk_runs(const BkPush a) {
 // A table per 16-lane group.  Every value but p, the block's own and the
 // ranks is the same in all of a group's lanes; every loop's trip count is.
 __global__ void __launch_bounds__(256) qh_k_blk_count(const BkPush a) {
-  const uint64_t t = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBkLanes;
-  const uint32_t sl = threadIdx.x % kBkLanes;
+  const uint64_t t = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (t >= a.ntables) return;  // (whole 16-lane groups)
   const BkTab x = a.tab[t];
   // (more runs than one: the flag is up, b0 and b1 may be of different runs)
   if (x.nrun != 1 || x.b0 >= x.b1 || x.b1 > a.nblocks) return;
   const qh_dec_blks v = a.bq[t];
   if (!qh_blk_region_ok(&v, a.at) || v.n > 0xFFFFFFFFull) {
-    if (sl == 0) ak_err(a.hdr);
+    if (sl == 0) hdr_err(a.hdr);
     return;
   }
   const uint64_t b0 = x.b0, b1 = x.b1;
   SpanOut *const pos = a.pos;
   uint64_t ncand = 0, acc = 0, bytes = 0;
-  for (uint64_t i0 = b0; i0 < b1; i0 += kBkLanes) {
+  for (uint64_t i0 = b0; i0 < b1; i0 += kGroupLanes) {
     const uint64_t p = i0 + sl;
     const bool in = p < b1 && a.view[p] == t;
     const int32_t st = in ? a.status[p] : 0;
@@ -182,40 +155,40 @@ __global__ void __launch_bounds__(256) qh_k_blk_count(const BkPush a) {
     const bool inq = bk_group_has_sid(a.blks + v.base, v.n, sid, sl);
     // the first blocked position of the run with this stream id, if before p
     uint64_t p0 = UINT64_MAX;
-    const uint64_t qe = i0 + kBkLanes < b1 ? i0 + kBkLanes : b1;
+    const uint64_t qe = i0 + kGroupLanes < b1 ? i0 + kGroupLanes : b1;
     for (uint64_t q = b0; q < qe; ++q) {
       const bool same = a.status[q] == QH_EMIT_BLOCKED && a.sid[q] == sid && a.view[q] == t;
       if (q < p && p0 == UINT64_MAX && same) p0 = q;
     }
     const bool cand = blocked && !inq && p0 == UINT64_MAX;
-    const uint32_t m = pd_group_ballot(cand);
+    const uint32_t m = group_ballot(cand);
     const uint64_t rank = ncand + __popc(m & ((1u << sl) - 1u));
     const bool took =
         cand && qh_blk_push_verdict(0, v.n, rank, v.max_blocked) == QH_EMIT_BLOCKED;
     // whether the earlier block of the same stream was accepted: this round's
     // from its lane, an earlier round's from what the group stored
     const bool here = p0 != UINT64_MAX && p0 >= i0;
-    const int took0 = __shfl((int)took, here ? (int)(p0 - i0) : (int)sl, kBkLanes);
+    const int took0 = __shfl((int)took, here ? (int)(p0 - i0) : (int)sl, kGroupLanes);
     bool dup = inq;
     if (blocked && !inq && p0 != UINT64_MAX)
       dup = here ? took0 != 0 : pos[p0].len != kBkNone;
     int32_t vd = st;
     if (blocked) vd = took ? QH_EMIT_BLOCKED : dup ? QH_ERR_INVALID_ARGUMENT : QH_ERR_QPACK_DECOMPRESSION_FAILED;
     const unsigned long long len = took ? a.blocks[p].len : 0;
-    const unsigned long long incl = bk_group_incl64(len, sl);
+    const unsigned long long incl = group_incl64(len, sl);
     if (in) {
       const SpanOut o = {bytes + incl - len, took ? (uint32_t)rank : kBkNone, vd};
       pos[p] = o;
       a.pb0[p] = (uint32_t)b0;
     }
-    bytes += __shfl(incl, kBkLanes - 1, kBkLanes);
+    bytes += __shfl(incl, kGroupLanes - 1, kGroupLanes);
     ncand += __popc(m);
-    acc += __popc(pd_group_ballot(took));
+    acc += __popc(group_ballot(took));
     __threadfence_block();  // (a later round reads pos of this one: one wave, one L1)
   }
   if (sl != 0 || acc == 0) return;
   if (v.n + acc > 0xFFFFFFFFull || bytes > 0xFFFFFFFFull) {  // (one scan item each)
-    ak_err(a.hdr);
+    hdr_err(a.hdr);
     return;
   }
   a.cnt[b0].len = (uint32_t)(v.n + acc);
@@ -239,7 +212,7 @@ __global__ void __launch_bounds__(256) qh_k_blk_fill(const BkPush a) {
 __global__ void __launch_bounds__(256) qh_k_blk_copy(const BkPush a, uint64_t total) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= total) return;
-  const uint64_t lo = bk_find(a.cnt, a.nblocks, r);
+  const uint64_t lo = span_find(a.cnt, a.nblocks, r);
   const qh_dec_blks v = a.bq[a.view[lo]];
   const uint64_t k = r - a.cnt[lo].off;
   qh_dec_blk x;
@@ -286,7 +259,7 @@ __global__ void __launch_bounds__(256) qh_k_blk_bytes(const BkBytes a) {
   if (q >= (mis + a.total + 15) / 16) return;
   uint64_t b = q * 16 < mis ? 0 : q * 16 - mis;
   const uint64_t end = (q + 1) * 16 - mis < a.total ? (q + 1) * 16 - mis : a.total;
-  for (uint64_t j = bk_find(a.rec, a.n, b); b < end && j < a.n; ++j) {
+  for (uint64_t j = span_find(a.rec, a.n, b); b < end && j < a.n; ++j) {
     const SpanOut e = a.rec[j];
     uint64_t soff;
     uint32_t len;
@@ -334,14 +307,14 @@ struct BkRel {
 };
 
 __global__ void __launch_bounds__(256) qh_k_blk_relcount(const BkRel a) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBkLanes;
-  const uint32_t sl = threadIdx.x % kBkLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.nsel) return;  // (whole 16-lane groups)
   uint64_t tt = 0;
   int ok = 1;
-  if (sl == 0) ok = ak_claim(a.tsel, a.owner, c, a.ntables, &tt);
-  ok = __shfl(ok, 0, kBkLanes);
-  tt = __shfl((unsigned long long)tt, 0, kBkLanes);
+  if (sl == 0) ok = table_claim(a.tsel, a.owner, c, a.ntables, &tt);
+  ok = __shfl(ok, 0, kGroupLanes);
+  tt = __shfl((unsigned long long)tt, 0, kGroupLanes);
   qh_dec_blks v = {0, 0, 0, 0};
   if (ok) {
     v = a.bq[tt];
@@ -350,7 +323,7 @@ __global__ void __launch_bounds__(256) qh_k_blk_relcount(const BkRel a) {
   SpanOut o = {0, 0, 0};
   if (!ok) {
     if (sl == 0) {
-      ak_err(a.hdr);
+      hdr_err(a.hdr);
       o.status = -1;
       a.cnt[c] = o;
     }
@@ -358,9 +331,9 @@ __global__ void __launch_bounds__(256) qh_k_blk_relcount(const BkRel a) {
   }
   const uint64_t ic = a.views[tt].insert_count;
   uint64_t n = 0;
-  for (uint64_t i0 = 0; i0 < v.n; i0 += kBkLanes) {
+  for (uint64_t i0 = 0; i0 < v.n; i0 += kGroupLanes) {
     const uint64_t i = i0 + sl;
-    n += __popc(pd_group_ballot(i < v.n && qh_blk_released(a.blks[v.base + (i < v.n ? i : 0)].ricnt, ic)));
+    n += __popc(group_ballot(i < v.n && qh_blk_released(a.blks[v.base + (i < v.n ? i : 0)].ricnt, ic)));
   }
   o.len = (uint32_t)n;
   if (sl == 0) a.cnt[c] = o;
@@ -368,8 +341,8 @@ __global__ void __launch_bounds__(256) qh_k_blk_relcount(const BkRel a) {
 
 // After the scan and once rel_cap holds.
 __global__ void __launch_bounds__(256) qh_k_blk_relwrite(const BkRel a, uint64_t total) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBkLanes;
-  const uint32_t sl = threadIdx.x % kBkLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.nsel) return;
   const SpanOut o = a.cnt[c];
   if (sl == 0) {
@@ -381,24 +354,24 @@ __global__ void __launch_bounds__(256) qh_k_blk_relwrite(const BkRel a, uint64_t
   const qh_dec_blks v = a.bq[tt];
   const uint64_t ic = a.views[tt].insert_count;
   qh_dec_blk *const r = a.blks + v.base;
-  for (uint64_t i0 = 0; i0 < v.n; i0 += kBkLanes) {
+  for (uint64_t i0 = 0; i0 < v.n; i0 += kGroupLanes) {
     const uint64_t i = i0 + sl;
     qh_dec_blk x = {0, UINT64_MAX, 0, 0, 0};
     if (i < v.n) x = r[i];
     const bool rel = i < v.n && qh_blk_released(x.ricnt, ic);
-    if (!pd_group_ballot(rel)) continue;  // (none of the sixteen leaves)
+    if (!group_ballot(rel)) continue;  // (none of the sixteen leaves)
     // its rank: the group loads sixteen records at a time, every lane
     // compares its own record with the sixteen
     uint64_t rank = 0;
-    for (uint64_t j0 = 0; j0 < v.n; j0 += kBkLanes) {
+    for (uint64_t j0 = 0; j0 < v.n; j0 += kGroupLanes) {
       const uint64_t j = j0 + sl;
       const unsigned long long y = j < v.n ? r[j].ricnt : 0;
       const int yrel = j < v.n && qh_blk_released(y, ic);
-      if (!pd_group_ballot(yrel)) continue;
+      if (!group_ballot(yrel)) continue;
 #pragma unroll
-      for (uint32_t l = 0; l < kBkLanes; ++l) {
-        const unsigned long long yl = __shfl(y, (int)l, kBkLanes);
-        rank += __shfl(yrel, (int)l, kBkLanes) && qh_blk_before(yl, j0 + l, x.ricnt, i);
+      for (uint32_t l = 0; l < kGroupLanes; ++l) {
+        const unsigned long long yl = __shfl(y, (int)l, kGroupLanes);
+        rank += __shfl(yrel, (int)l, kGroupLanes) && qh_blk_before(yl, j0 + l, x.ricnt, i);
       }
     }
     if (rel && rank < o.len) {  // (always below: the order is total)
@@ -436,8 +409,8 @@ __global__ void __launch_bounds__(256) qh_k_blk_cruns(const BkCan a) {
 }
 
 __global__ void __launch_bounds__(256) qh_k_blk_cancel(const BkCan a) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBkLanes;
-  const uint32_t sl = threadIdx.x % kBkLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.ncancel) return;  // (whole 16-lane groups)
   const uint32_t t = a.view[c];
   if (c != 0 && a.view[c - 1] == t) return;  // (its run's first group serves it)
@@ -450,21 +423,21 @@ __global__ void __launch_bounds__(256) qh_k_blk_cancel(const BkCan a) {
     ok = qh_blk_region_ok(&v, a.nblks);
   }
   if (!ok) {
-    for (uint64_t q = c + sl; q < e; q += kBkLanes) a.removed[q] = 0xFF;
+    for (uint64_t q = c + sl; q < e; q += kGroupLanes) a.removed[q] = 0xFF;
     return;
   }
   qh_dec_blk *const r = a.blks + v.base;
   bool any = false;
-  for (uint64_t q0 = c; q0 < e; q0 += kBkLanes) {
+  for (uint64_t q0 = c; q0 < e; q0 += kGroupLanes) {
     const uint64_t q = q0 + sl;
     const uint64_t sid = q < e ? a.sid[q] : 0;
     bool found = false, again = false;
     found = bk_group_has_sid(r, v.n, sid, sl);
-    const uint64_t qe = q0 + kBkLanes < e ? q0 + kBkLanes : e;
+    const uint64_t qe = q0 + kGroupLanes < e ? q0 + kGroupLanes : e;
     for (uint64_t q2 = c; q2 < qe; ++q2) again |= q2 < q && a.sid[q2] == sid;
     const bool rm = q < e && found && !again;
     if (q < e) a.removed[q] = rm;
-    any |= pd_group_ballot(rm) != 0;
+    any |= group_ballot(rm) != 0;
   }
   if (!any) return;
   const uint64_t k = bk_squeeze(r, v.n, sl, [&](uint64_t, const qh_dec_blk &x) {
@@ -492,34 +465,34 @@ struct BkCmp {
 };
 
 __global__ void __launch_bounds__(256) qh_k_blk_ccount(const BkCmp a) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBkLanes;
-  const uint32_t sl = threadIdx.x % kBkLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.nsel) return;  // (whole 16-lane groups)
   uint64_t tt = 0;
   int ok = 1;
-  if (sl == 0) ok = ak_claim(a.tsel, a.owner, c, a.ntables, &tt);
-  ok = __shfl(ok, 0, kBkLanes);
-  tt = __shfl((unsigned long long)tt, 0, kBkLanes);
+  if (sl == 0) ok = table_claim(a.tsel, a.owner, c, a.ntables, &tt);
+  ok = __shfl(ok, 0, kGroupLanes);
+  tt = __shfl((unsigned long long)tt, 0, kGroupLanes);
   qh_dec_blks v = {0, 0, 0, 0};
   if (ok) {
     v = a.bq[tt];
     ok = qh_blk_region_ok(&v, a.nblks) && v.n <= 0xFFFFFFFFull;
   }
   uint64_t bytes = 0;
-  for (uint64_t i0 = 0; i0 < v.n && ok; i0 += kBkLanes) {
+  for (uint64_t i0 = 0; i0 < v.n && ok; i0 += kGroupLanes) {
     const uint64_t i = i0 + sl;
     qh_dec_blk x = {0, 0, 0, 0, 0};
     if (i < v.n) x = a.blks[v.base + i];
-    if (pd_group_ballot(!qh_blk_bytes_ok(&x, a.npend))) ok = 0;
-    const unsigned long long incl = bk_group_incl64(x.len, sl);
+    if (group_ballot(!qh_blk_bytes_ok(&x, a.npend))) ok = 0;
+    const unsigned long long incl = group_incl64(x.len, sl);
     if (i < v.n) a.pfx[v.base + i] = bytes + incl - x.len;
-    bytes += __shfl(incl, kBkLanes - 1, kBkLanes);
+    bytes += __shfl(incl, kGroupLanes - 1, kGroupLanes);
   }
   if (bytes > 0xFFFFFFFFull) ok = 0;  // (one scan item)
   if (sl != 0) return;
   SpanOut o = {0, 0, 0};
   if (!ok) {
-    ak_err(a.hdr);
+    hdr_err(a.hdr);
     o.status = -1;
     a.cnt[c] = o;
     a.cnt[a.nsel + c] = o;
@@ -534,7 +507,7 @@ __global__ void __launch_bounds__(256) qh_k_blk_ccount(const BkCmp a) {
 __global__ void __launch_bounds__(256) qh_k_blk_crec(const BkCmp a, uint64_t total) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= total) return;
-  const uint64_t lo = bk_find(a.cnt, a.nsel, r);
+  const uint64_t lo = span_find(a.cnt, a.nsel, r);
   const qh_dec_blks v = a.bq[a.tsel ? a.tsel[lo] : lo];
   const uint64_t i = v.base + (r - a.cnt[lo].off);
   const qh_dec_blk x = a.blks[i];
@@ -555,25 +528,10 @@ __global__ void __launch_bounds__(256) qh_k_blk_crebase(const BkCmp a) {
 
 namespace {
 
-unsigned blk_grid(uint64_t lanes) { return (unsigned)((lanes + 255) / 256); }
-
-// The scan's totals, its timeouts and the error flag, read back: the wait.
-int blk_wait(qh_ctx *c, const uint64_t *hdr, uint64_t *h, const char *what) {
-  QH_HIP(hipMemcpyAsync(h, hdr + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  QH_HIP(hipStreamSynchronize(c->stream));
-  int r = scan_seg_check(h[qhk::kBkTimeouts - 1], what);
-  if (r) return r;
-  return h[qhk::kBkErr - 1] ? QH_ERR_INVALID_ARGUMENT : 0;
-}
-
 int blk_bytes(qh_ctx *c, const qhk::BkBytes &b) {
   if (!b.total) return 0;
   const uint64_t mis = reinterpret_cast<uintptr_t>(b.dst) & 15;
-  Timed t(c, "qh_k_blk_bytes");
-  hipLaunchKernelGGL(qhk::qh_k_blk_bytes, dim3(blk_grid((mis + b.total + 15) / 16)), dim3(256), 0,
-                     c->stream, b);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_blk_bytes, (mis + b.total + 15) / 16, 256, b);
 }
 
 }  // namespace
@@ -594,8 +552,7 @@ QH_EXPORT int qh_dec_blocked_push_batch(qh_ctx *c, const uint8_t *src, const qh_
     return QH_ERR_INVALID_ARGUMENT;
   if (nblocks == 0) return 0;
   if (ntables == 0) return QH_ERR_INVALID_ARGUMENT;
-  const uint64_t tps = (nblocks + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kBkHdr + 3 * tps;
+  const uint64_t tiles = 3 * ((nblocks + qhk::kScanTile - 1) / qhk::kScanTile);
   qhk::BkPush a{};
   r = reserve_layout(c, kBufBlocked, [&](qhs::Layout &l) {
     a.tab = l.take<qhk::BkTab>(ntables);
@@ -603,11 +560,11 @@ QH_EXPORT int qh_dec_blocked_push_batch(qh_ctx *c, const uint8_t *src, const qh_
     a.pos = l.take<qhk::SpanOut>(nblocks);
     a.pb0 = l.take<uint32_t>(nblocks);
     a.nrec = l.take<qhk::SpanOut>(nblocks);
-    a.hdr = l.take<uint64_t>(hwords);
+    a.hdr = l.take<uint64_t>(qhk::kHdrWords + tiles);
   });
   if (r) return r;
-  if ((r = reserve(c, kBufBlockedHost, 8 * sizeof(uint64_t), qhs::kExact))) return r;
-  uint64_t *h = mem<uint64_t>(c, kBufBlockedHost);
+  uint64_t *h;
+  if ((r = scan_hdr_host(c, &h))) return r;
   a.src = src;
   a.blocks = reinterpret_cast<const qhk::SpanIn *>(blocks);
   a.sid = block_sid;
@@ -621,42 +578,21 @@ QH_EXPORT int qh_dec_blocked_push_batch(qh_ctx *c, const uint8_t *src, const qh_
   a.at = *nblks;
   a.bat = *npend;
   a.verdict = verdict;
-  QH_HIP(hipMemsetAsync(a.hdr, 0, hwords * sizeof(uint64_t), c->stream));
+  if ((r = scan_hdr_reset(c, a.hdr, tiles))) return r;
   QH_HIP(hipMemsetAsync(a.tab, 0, ntables * sizeof(qhk::BkTab), c->stream));
-  {
-    Timed t(c, "qh_k_blk_runs");
-    hipLaunchKernelGGL(qhk::qh_k_blk_runs, dim3(blk_grid(nblocks)), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  {
-    Timed t(c, "qh_k_blk_count");
-    hipLaunchKernelGGL(qhk::qh_k_blk_count, dim3(blk_grid((uint64_t)ntables * qhk::kBkLanes)),
-                       dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((r = launch_scan_seg(c, a.cnt, nblocks, 3, a.hdr, qhk::kBkHdr, qhk::kBkTot, qhk::kBkTimeouts)))
-    return r;
-  if ((r = blk_wait(c, a.hdr, h, "blocked-push"))) return r;
+  if ((r = QH_LAUNCH(c, qh_k_blk_runs, nblocks, 256, a))) return r;
+  if ((r = QH_LAUNCH(c, qh_k_blk_count, (uint64_t)ntables * qhk::kGroupLanes, 256, a))) return r;
+  if ((r = launch_scan_seg(c, a.cnt, nblocks, 3, a.hdr))) return r;
+  if ((r = scan_hdr_wait(c, a.hdr, h, "blocked-push"))) return r;
   const uint64_t nrec = h[0], nbytes = h[1];
   *nblks = a.at + nrec;
   *npend = a.bat + nbytes;
   if (*nblks > blks_cap || *npend > pend_cap) return QH_ERR_NOMEM;
-  {
-    Timed t(c, "qh_k_blk_fill");
-    hipLaunchKernelGGL(qhk::qh_k_blk_fill, dim3(blk_grid(nblocks)), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if (nrec) {
-    Timed t(c, "qh_k_blk_copy");
-    hipLaunchKernelGGL(qhk::qh_k_blk_copy, dim3(blk_grid(nrec)), dim3(256), 0, c->stream, a, nrec);
-    QH_HIP(hipGetLastError());
-  }
+  if ((r = QH_LAUNCH(c, qh_k_blk_fill, nblocks, 256, a))) return r;
+  if (nrec && (r = QH_LAUNCH(c, qh_k_blk_copy, nrec, 256, a, nrec))) return r;
   const qhk::BkBytes b{a.nrec, h[2], nbytes, src, a.blocks, nullptr, pend + a.bat};
   if ((r = blk_bytes(c, b))) return r;
-  Timed t(c, "qh_k_blk_rebase");
-  hipLaunchKernelGGL(qhk::qh_k_blk_rebase, dim3(blk_grid(nblocks)), dim3(256), 0, c->stream, a);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_blk_rebase, nblocks, 256, a);
 }
 
 QH_EXPORT int qh_dec_blocked_release_batch(qh_ctx *c, const uint32_t *tsel, size_t nsel,
@@ -675,17 +611,16 @@ QH_EXPORT int qh_dec_blocked_release_batch(qh_ctx *c, const uint32_t *tsel, size
     return QH_ERR_INVALID_ARGUMENT;
   *nreleased = 0;
   if (nsel == 0) return 0;
-  const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kBkHdr + tps;
+  const uint64_t tiles = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
   qhk::BkRel a{};
   r = reserve_layout(c, kBufBlocked, [&](qhs::Layout &l) {
     a.cnt = l.take<qhk::SpanOut>(nsel);
     a.owner = l.take<uint32_t>(ntables);
-    a.hdr = l.take<uint64_t>(hwords);
+    a.hdr = l.take<uint64_t>(qhk::kHdrWords + tiles);
   });
   if (r) return r;
-  if ((r = reserve(c, kBufBlockedHost, 8 * sizeof(uint64_t), qhs::kExact))) return r;
-  uint64_t *h = mem<uint64_t>(c, kBufBlockedHost);
+  uint64_t *h;
+  if ((r = scan_hdr_host(c, &h))) return r;
   a.tsel = tsel;
   a.nsel = nsel;
   a.ntables = ntables;
@@ -698,24 +633,16 @@ QH_EXPORT int qh_dec_blocked_release_batch(qh_ctx *c, const uint32_t *tsel, size
   a.rel_view = rel_view;
   a.rel_ricnt = rel_ricnt;
   a.rel_start = rel_start;
-  QH_HIP(hipMemsetAsync(a.hdr, 0, hwords * sizeof(uint64_t), c->stream));
-  if ((r = ack_owner(c, tsel, ntables, a.owner))) return r;
-  const unsigned grid = blk_grid((uint64_t)nsel * qhk::kBkLanes);
-  {
-    Timed t(c, "qh_k_blk_relcount");
-    hipLaunchKernelGGL(qhk::qh_k_blk_relcount, dim3(grid), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((r = launch_scan_seg(c, a.cnt, nsel, 1, a.hdr, qhk::kBkHdr, qhk::kBkTot, qhk::kBkTimeouts)))
-    return r;
-  if ((r = blk_wait(c, a.hdr, h, "blocked-release"))) return r;
+  if ((r = scan_hdr_reset(c, a.hdr, tiles))) return r;
+  if ((r = table_owner_reset(c, tsel, ntables, a.owner))) return r;
+  const uint64_t lanes = (uint64_t)nsel * qhk::kGroupLanes;
+  if ((r = QH_LAUNCH(c, qh_k_blk_relcount, lanes, 256, a))) return r;
+  if ((r = launch_scan_seg(c, a.cnt, nsel, 1, a.hdr))) return r;
+  if ((r = scan_hdr_wait(c, a.hdr, h, "blocked-release"))) return r;
   *nreleased = h[0];
   if (h[0] > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;  // (rel_start is 32 bits wide)
   if (h[0] > rel_cap) return QH_ERR_NOMEM;
-  Timed t(c, "qh_k_blk_relwrite");
-  hipLaunchKernelGGL(qhk::qh_k_blk_relwrite, dim3(grid), dim3(256), 0, c->stream, a, h[0]);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_blk_relwrite, lanes, 256, a, h[0]);
 }
 
 QH_EXPORT int qh_dec_blocked_cancel_batch(qh_ctx *c, const uint64_t *cancel_sid,
@@ -733,16 +660,8 @@ QH_EXPORT int qh_dec_blocked_cancel_batch(qh_ctx *c, const uint64_t *cancel_sid,
   r = reserve_layout(c, kBufBlocked, [&](qhs::Layout &l) { a.owner = l.take<uint32_t>(ntables + 1); });
   if (r) return r;
   QH_HIP(hipMemsetAsync(a.owner, 0xFF, (ntables + 1) * 4, c->stream));
-  {
-    Timed t(c, "qh_k_blk_cruns");
-    hipLaunchKernelGGL(qhk::qh_k_blk_cruns, dim3(blk_grid(ncancel)), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  Timed t(c, "qh_k_blk_cancel");
-  hipLaunchKernelGGL(qhk::qh_k_blk_cancel, dim3(blk_grid((uint64_t)ncancel * qhk::kBkLanes)),
-                     dim3(256), 0, c->stream, a);
-  QH_HIP(hipGetLastError());
-  return 0;
+  if ((r = QH_LAUNCH(c, qh_k_blk_cruns, ncancel, 256, a))) return r;
+  return QH_LAUNCH(c, qh_k_blk_cancel, (uint64_t)ncancel * qhk::kGroupLanes, 256, a);
 }
 
 QH_EXPORT int qh_dec_blocked_compact_batch(qh_ctx *c, const uint32_t *tsel, size_t nsel,
@@ -762,18 +681,17 @@ QH_EXPORT int qh_dec_blocked_compact_batch(qh_ctx *c, const uint32_t *tsel, size
   *nblks_out = 0;
   *npend_out = 0;
   if (nsel == 0) return 0;
-  const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kBkHdr + 2 * tps;
+  const uint64_t tiles = 2 * ((nsel + qhk::kScanTile - 1) / qhk::kScanTile);
   qhk::BkCmp a{};
   r = reserve_layout(c, kBufBlocked, [&](qhs::Layout &l) {
     a.cnt = l.take<qhk::SpanOut>(2 * nsel);
     a.pfx = l.take<uint64_t>(nblks);
     a.owner = l.take<uint32_t>(ntables);
-    a.hdr = l.take<uint64_t>(hwords);
+    a.hdr = l.take<uint64_t>(qhk::kHdrWords + tiles);
   });
   if (r) return r;
-  if ((r = reserve(c, kBufBlockedHost, 8 * sizeof(uint64_t), qhs::kExact))) return r;
-  uint64_t *h = mem<uint64_t>(c, kBufBlockedHost);
+  uint64_t *h;
+  if ((r = scan_hdr_host(c, &h))) return r;
   a.tsel = tsel;
   a.nsel = nsel;
   a.ntables = ntables;
@@ -782,17 +700,11 @@ QH_EXPORT int qh_dec_blocked_compact_batch(qh_ctx *c, const uint32_t *tsel, size
   a.nblks = nblks;
   a.npend = npend;
   a.out = blks_out;
-  QH_HIP(hipMemsetAsync(a.hdr, 0, hwords * sizeof(uint64_t), c->stream));
-  if ((r = ack_owner(c, tsel, ntables, a.owner))) return r;
-  {
-    Timed t(c, "qh_k_blk_ccount");
-    hipLaunchKernelGGL(qhk::qh_k_blk_ccount, dim3(blk_grid((uint64_t)nsel * qhk::kBkLanes)),
-                       dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((r = launch_scan_seg(c, a.cnt, nsel, 2, a.hdr, qhk::kBkHdr, qhk::kBkTot, qhk::kBkTimeouts)))
-    return r;
-  if ((r = blk_wait(c, a.hdr, h, "blocked-compact"))) return r;
+  if ((r = scan_hdr_reset(c, a.hdr, tiles))) return r;
+  if ((r = table_owner_reset(c, tsel, ntables, a.owner))) return r;
+  if ((r = QH_LAUNCH(c, qh_k_blk_ccount, (uint64_t)nsel * qhk::kGroupLanes, 256, a))) return r;
+  if ((r = launch_scan_seg(c, a.cnt, nsel, 2, a.hdr))) return r;
+  if ((r = scan_hdr_wait(c, a.hdr, h, "blocked-compact"))) return r;
   const uint64_t nrec = h[0], nbytes = h[1];
   *nblks_out = nrec;
   *npend_out = nbytes;
@@ -802,16 +714,9 @@ QH_EXPORT int qh_dec_blocked_compact_batch(qh_ctx *c, const uint32_t *tsel, size
     if ((r = reserve_layout(c, kBufBlockedWork,
                             [&](qhs::Layout &l) { a.rec = l.take<qhk::SpanOut>(nrec); })))
       return r;
-    {
-      Timed t(c, "qh_k_blk_crec");
-      hipLaunchKernelGGL(qhk::qh_k_blk_crec, dim3(blk_grid(nrec)), dim3(256), 0, c->stream, a, nrec);
-      QH_HIP(hipGetLastError());
-    }
+    if ((r = QH_LAUNCH(c, qh_k_blk_crec, nrec, 256, a, nrec))) return r;
     const qhk::BkBytes b{a.rec, nrec, nbytes, pend, nullptr, blks, pend_out};
     if ((r = blk_bytes(c, b))) return r;
   }
-  Timed t(c, "qh_k_blk_crebase");
-  hipLaunchKernelGGL(qhk::qh_k_blk_crebase, dim3(blk_grid(nsel)), dim3(256), 0, c->stream, a);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_blk_crebase, nsel, 256, a);
 }

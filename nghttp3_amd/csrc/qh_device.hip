@@ -22,6 +22,9 @@
 //   qh_k_ack_*, qh_k_ackw_*  acknowledgements: the reference log, decoder streams read and written
 //   qh_k_blk_*         blocked sections: queued, released, cancelled, compacted
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
+// The kernels from qh_k_encsec_* to qh_k_blk_* work a 16-lane group per table,
+// connection or block and leave their totals in one scan header: both are
+// qh_group.inc's.
 // Development variants (the pair decoder, the segment encoder) build only
 // with -DQH_DEV_VARIANTS (make dev -> libqhuff_dev.so); the kernels that
 // exist only for them live outside the package, in dev/csrc (-I).  The older
@@ -41,6 +44,7 @@
 #include <thread>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/qhuff.h"
@@ -53,6 +57,7 @@
 #include "qh_common.h"      // span/stat types, tables, small helpers
 #include "qh_chunk.inc"      // block ranges, windows, chunk rounds, scans
 #include "qh_scan.inc"       // batch prefix sum (synthetic inputs)
+#include "qh_group.inc"      // the state kernels' 16-lane group, the segmented scan's header
 #include "qh_dec_common.inc"  // decode table blob, slot reservation
 #include "qh_check.inc"       // field name / value checks (device)
 #include "qh_sched.inc"       // batch-wide length-class schedule (QH_DECODER_SORTED)

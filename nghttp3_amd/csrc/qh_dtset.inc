@@ -3,7 +3,9 @@
 // device twin of qh_dtset.c.  The parser is qh_qpack_core.h and the walk
 // qh_dtable_core.h, the sources the host function compiles, and the layout
 // rule of the header fixes every record's and byte's place, so the two logs
-// are equal byte for byte.
+// are equal byte for byte.  The 16-lane group, the table claim, the scan
+// header (its word kHdrAux here: the long Huffman strings) and the wait on it
+// are qh_group.inc's and qh_api.inc's.
 //
 //   count   qh_k_dts_count, a lane per stream: the table list checked (an
 //           index past ntables, a table named twice), the stream parsed in
@@ -38,19 +40,6 @@
 
 namespace qhk {
 
-constexpr uint32_t kDtLanes = 16;
-
-// The header words ahead of the scan's tile states (zeroed before each scan;
-// words 1-7 read back with one copy).
-enum : uint32_t {
-  kDtCtr = 0,       // scan tile counter
-  kDtTot = 1,       // the scan's totals: up to four words
-  kDtTimeouts = 5,  // scan look-backs that gave up
-  kDtErr = 6,       // a bad table list, a stream or a table past the 32-bit counts
-  kDtNLong = 7,     // Huffman strings of at least QH_LONG_MIN encoded bytes
-  kDtHdr = 8
-};
-
 // The work buffer's room, in records.  The chain from the write pass to the
 // second scan may be queued before the host has seen the parser's totals
 // (over a buffer sized by earlier calls): a stream whose records would pass
@@ -81,9 +70,8 @@ __global__ void __launch_bounds__(256) qh_k_dts_count(
     uint32_t *__restrict__ done, uint64_t *__restrict__ hdr) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nsel) return;
-  const uint64_t t = tsel ? tsel[p] : p;
-  bool err = t >= ntables;
-  if (!err && tsel) err = atomicExch(&owner[t], (uint32_t)p) != 0xFFFFFFFFu;  // (named twice)
+  uint64_t t;
+  bool err = !table_claim(tsel, owner, p, ntables, &t);
   const SpanIn s = streams[p];
   if (s.len > (1u << 30) || (s.len && !src)) err = true;
   scan_out o;
@@ -97,9 +85,9 @@ __global__ void __launch_bounds__(256) qh_k_dts_count(
   cnt[3 * nsel + p].len = (uint32_t)o.hslots;  // (at most 8/5 of 2^30 bytes + 80 per string)
   sv[p] = v;
   done[p] = (uint32_t)dn;
-  if (err) atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
-  if (o.nlong)
-    atomicAdd(reinterpret_cast<unsigned long long *>(hdr + kDtNLong), (unsigned long long)o.nlong);
+  if (err) hdr_err(hdr);
+  if (o.nlong)  // (kHdrAux: Huffman strings of at least QH_LONG_MIN encoded bytes)
+    atomicAdd(reinterpret_cast<unsigned long long *>(hdr + kHdrAux), (unsigned long long)o.nlong);
 }
 
 // After the scan: cnt[k nsel + p].off = stream p's first instruction, span,
@@ -191,30 +179,12 @@ __global__ void __launch_bounds__(256) qh_k_dts_size(
     }
   }
   if (nrec > 0xFFFFFFFFull || nbyte > 0xFFFFFFFFull) {
-    atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
+    hdr_err(hdr);
     nrec = nbyte = 0;
   }
   res[p] = r;
   cnt2[p].len = (uint32_t)nrec;
   cnt2[nsel + p].len = (uint32_t)nbyte;
-}
-
-// n bytes from -> to by a 16-lane group (any alignment): 16-byte pieces at
-// min(16 k, n - 16), the last overlapping the one before it, a lane each per
-// round; a string under 16 bytes a byte per lane.  Never touches a byte
-// outside [from, from + n) or [to, to + n).
-__device__ __forceinline__ void dts_group_copy(uint8_t *to, const uint8_t *from, uint32_t n,
-                                               uint32_t sl) {
-  if (n < 16) {
-    if (sl < n) to[sl] = from[sl];
-    return;
-  }
-  const uint32_t np = (n + 15) / 16;
-  for (uint32_t k = sl; k < np; k += kDtLanes) {
-    const uint32_t at = min(16 * k, n - 16);
-    const u32x4 w = *reinterpret_cast<const u32x4_ua *>(from + at);
-    *reinterpret_cast<u32x4_ua *>(to + at) = w;
-  }
 }
 
 // After the second scan: cnt2[p].off = the records appended before table p's
@@ -234,8 +204,8 @@ __global__ void __launch_bounds__(256, QH_DTS_MIN_WAVES) qh_k_dts_apply(
     const SpanOut *__restrict__ hout, const uint8_t *__restrict__ slots,
     uint32_t *__restrict__ lens, const SpanOut *__restrict__ cnt2, const DtRes *__restrict__ res,
     int32_t *__restrict__ status, uint32_t *__restrict__ consumed) {
-  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kDtLanes;
-  const uint32_t sl = threadIdx.x % kDtLanes;
+  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (p >= nsel) return;  // (whole 16-lane groups)
   const DtRes r = res[p];
   if (sl == 0) {
@@ -252,7 +222,7 @@ __global__ void __launch_bounds__(256, QH_DTS_MIN_WAVES) qh_k_dts_apply(
   qh_dt_begin(&w, &v, &a, entries, nbytes, stat);
   const uint64_t L = w.count_in - w.live_lo_in;
   if (cr.len) {  // the table moves: its live records first, a record per lane per round
-    for (uint64_t j = sl; j < L; j += kDtLanes) entries[ent_at + j] = w.old[w.live_lo_in + j];
+    for (uint64_t j = sl; j < L; j += kGroupLanes) entries[ent_at + j] = w.old[w.live_lo_in + j];
     w.neu = entries + ent_at + L;
     w.byte_at = nbytes + cb.off;
   } else {
@@ -270,13 +240,13 @@ __global__ void __launch_bounds__(256, QH_DTS_MIN_WAVES) qh_k_dts_apply(
       dts_inst(l, spans, aux, hout, &in);
       (void)qh_dt_step(&w, &in, &ad);
     }
-    if (!__shfl((int)ad.added, 0, kDtLanes)) continue;
-    const uint32_t name_src = __shfl((int)ad.name_src, 0, kDtLanes);
-    const uint32_t value_src = __shfl((int)ad.value_src, 0, kDtLanes);
-    const uint32_t name_len = __shfl(ad.e.name_len, 0, kDtLanes);
-    const uint32_t value_len = __shfl(ad.e.value_len, 0, kDtLanes);
-    const unsigned long long name_off = __shfl((unsigned long long)ad.e.name_off, 0, kDtLanes);
-    const unsigned long long value_off = __shfl((unsigned long long)ad.e.value_off, 0, kDtLanes);
+    if (!__shfl((int)ad.added, 0, kGroupLanes)) continue;
+    const uint32_t name_src = __shfl((int)ad.name_src, 0, kGroupLanes);
+    const uint32_t value_src = __shfl((int)ad.value_src, 0, kGroupLanes);
+    const uint32_t name_len = __shfl(ad.e.name_len, 0, kGroupLanes);
+    const uint32_t value_len = __shfl(ad.e.value_len, 0, kGroupLanes);
+    const unsigned long long name_off = __shfl((unsigned long long)ad.e.name_off, 0, kGroupLanes);
+    const unsigned long long value_off = __shfl((unsigned long long)ad.e.value_off, 0, kGroupLanes);
     if (name_src != QH_DT_SHARED) {
       const uint8_t *from;
       if (name_src == QH_DT_STATIC) {
@@ -286,12 +256,12 @@ __global__ void __launch_bounds__(256, QH_DTS_MIN_WAVES) qh_k_dts_apply(
         from = h != 0xFFFFFFFFu ? slots + hout[h].off : src + spans[l.name].off;
         if (sl == 0) ad.e.token = lookup_token(from, name_len);
       }
-      dts_group_copy(bytes + name_off, from, name_len, sl);
+      group_copy(bytes + name_off, from, name_len, sl);
     }
     if (value_src != QH_DT_SHARED) {
       const uint32_t h = (uint32_t)aux[l.value];
       const uint8_t *from = h != 0xFFFFFFFFu ? slots + hout[h].off : src + spans[l.value].off;
-      dts_group_copy(bytes + value_off, from, value_len, sl);
+      group_copy(bytes + value_off, from, value_len, sl);
     }
     if (sl == 0) w.neu[w.nnew - 1] = ad.e;
   }
@@ -382,7 +352,7 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
   // per-stream scratch, sized by the table list alone: the four counts, the
   // two sizes, verdicts, owners, and the two scans' headers and tile states
   const uint64_t tps = (nsel + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kDtHdr + 4 * tps;
+  const uint64_t hwords = qhk::kHdrWords + 4 * tps;
   qhk::SpanOut *cnt, *cnt2;
   qhk::DtRes *res;
   int32_t *sv;
@@ -399,8 +369,8 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
   });
   if (rv) return rv;
   uint64_t *const hdr_b = hdr_a + hwords;
-  if ((rv = reserve(c, kBufDtsetHost, 16 * sizeof(uint64_t), qhs::kExact))) return rv;
-  uint64_t *h = mem<uint64_t>(c, kBufDtsetHost);  // [0, 7): the parser's words 1-7, [8, 15): the size pass's
+  uint64_t *h;  // [0, 7): the parser's words 1-7, [8, 15): the size pass's
+  if ((rv = scan_hdr_host(c, &h))) return rv;
   DtWork W;
   const bool spec = c->dt_hint_nsel != 0;
   if (spec) {
@@ -412,60 +382,37 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
     if ((rv = dts_work(c, lay[0], lay[1], lay[2], lay[3], W))) return rv;
   }
 
-  QH_HIP(hipMemsetAsync(hdr_a, 0, 2 * hwords * sizeof(uint64_t), c->stream));
-  if (tsel) QH_HIP(hipMemsetAsync(owner, 0xFF, ntables * 4, c->stream));
-  const unsigned grid1 = (unsigned)((nsel + 255) / 256);
-  {
-    Timed t(c, "qh_k_dts_count");
-    hipLaunchKernelGGL(qhk::qh_k_dts_count, dim3(grid1), dim3(256), 0, c->stream, src,
-                       (const qhk::SpanIn *)streams, tsel, (uint64_t)nsel, (uint64_t)ntables, owner,
-                       cnt, sv, done, hdr_a);
-    QH_HIP(hipGetLastError());
-  }
-  auto scan = [&](qhk::SpanOut *x, uint32_t nseg, uint64_t *hdr) -> int {
-    return launch_scan_seg(c, x, nsel, nseg, hdr, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts);
-  };
+  // (both headers with one memset: they lie side by side)
+  if ((rv = scan_hdr_reset(c, hdr_a, hwords + 4 * tps))) return rv;
+  if ((rv = table_owner_reset(c, tsel, ntables, owner))) return rv;
+  if ((rv = QH_LAUNCH(c, qh_k_dts_count, nsel, 256, src, (const qhk::SpanIn *)streams, tsel,
+                      (uint64_t)nsel, (uint64_t)ntables, owner, cnt, sv, done, hdr_a)))
+    return rv;
   // words 1-7 of both headers, one wait
-  auto totals = [&]() -> int {
-    QH_HIP(hipMemcpyAsync(h, hdr_a + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    QH_HIP(hipMemcpyAsync(h + 8, hdr_b + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    QH_HIP(hipStreamSynchronize(c->stream));
-    return scan_seg_check(h[qhk::kDtTimeouts - 1] | h[8 + qhk::kDtTimeouts - 1], "table-set");
-  };
+  auto totals = [&]() -> int { return scan_hdr_wait2(c, hdr_a, hdr_b, h, "table-set"); };
   // write -> decode -> size -> scan over W's layout
   auto chain = [&]() -> int {
     int r = 0;
     if (W.caps.nh)  // (an entry no stream writes is an empty string)
       QH_HIP(hipMemsetAsync(W.huff, 0, W.caps.nh * sizeof(qh_span_in), c->stream));
-    if (W.caps.ni) {
-      Timed t(c, "qh_k_dts_write");
-      hipLaunchKernelGGL(qhk::qh_k_dts_write, dim3(grid1), dim3(256), 0, c->stream, src,
-                         (const qhk::SpanIn *)streams, (uint64_t)nsel, (const qhk::SpanOut *)cnt,
-                         (const uint32_t *)done, W.insts, W.ends, W.spans, W.aux, W.huff, W.caps);
-      QH_HIP(hipGetLastError());
-    }
+    if (W.caps.ni &&
+        (r = QH_LAUNCH(c, qh_k_dts_write, nsel, 256, src, (const qhk::SpanIn *)streams,
+                       (uint64_t)nsel, cnt, done, W.insts, W.ends, W.spans, W.aux, W.huff, W.caps)))
+      return r;
     if ((r = decode_device(c, src, W.huff, W.caps.nh, W.slots, W.slots_cap, W.hout, true, nullptr, 0)))
       return r;
-    QH_HIP(hipMemsetAsync(hdr_b, 0, hwords * sizeof(uint64_t), c->stream));
-    {
-      Timed t(c, "qh_k_dts_size");
-      hipLaunchKernelGGL(qhk::qh_k_dts_size, dim3(grid1), dim3(256), 0, c->stream, tsel,
-                         (uint64_t)nsel, (uint64_t)ntables, (const qh_dtable_view *)views,
-                         (const qh_dtable_acct *)acct, (const qh_dyn_entry *)entries, ne0, nb0, stat,
-                         W.caps, (const qhk::SpanOut *)cnt, (const int32_t *)sv,
-                         (const uint32_t *)done, (const qh_field_line *)W.insts,
-                         (const uint32_t *)W.ends, (const qhk::SpanIn *)W.spans,
-                         (const uint64_t *)W.aux, (const qhk::SpanOut *)W.hout, W.lens, cnt2, res,
-                         hdr_b);
-      QH_HIP(hipGetLastError());
-    }
-    return scan(cnt2, 2, hdr_b);
+    if ((r = scan_hdr_reset(c, hdr_b, 4 * tps))) return r;
+    if ((r = QH_LAUNCH(c, qh_k_dts_size, nsel, 256, tsel, (uint64_t)nsel, (uint64_t)ntables, views,
+                       acct, entries, ne0, nb0, stat, W.caps, cnt, sv, done, W.insts, W.ends,
+                       W.spans, W.aux, W.hout, W.lens, cnt2, res, hdr_b)))
+      return r;
+    return launch_scan_seg(c, cnt2, nsel, 2, hdr_b);
   };
 
-  if ((rv = scan(cnt, 4, hdr_a))) return rv;
+  if ((rv = launch_scan_seg(c, cnt, nsel, 4, hdr_a))) return rv;
   if (spec && (rv = chain())) return rv;
   if ((rv = totals())) return rv;  // the wait
-  if (h[qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  if (h[qhk::kHdrErr - 1]) return QH_ERR_INVALID_ARGUMENT;
   const uint64_t ni = h[0], ns = h[1], nh = h[2], slots_b = h[3];
   if (ni > 0x7fffffffull || ns > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
   if (!spec || ni > W.caps.ni || ns > W.caps.ns || nh > W.caps.nh ||
@@ -481,22 +428,13 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
   c->dt_hint[2] = nh;
   c->dt_hint[3] = slots_b;
   c->dt_hint_nsel = nsel;
-  if (h[8 + qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  if (h[8 + qhk::kHdrErr - 1]) return QH_ERR_INVALID_ARGUMENT;
   *nentries = ne0 + h[8];
   *nbytes = nb0 + h[9];
   if (*nentries > entries_cap || *nbytes > bytes_cap) return QH_ERR_NOMEM;
-  {
-    Timed t(c, "qh_k_dts_apply");
-    const unsigned grid = (unsigned)(((uint64_t)nsel * qhk::kDtLanes + 255) / 256);
-    hipLaunchKernelGGL(qhk::qh_k_dts_apply, dim3(grid), dim3(256), 0, c->stream, src, tsel,
-                       (uint64_t)nsel, views, acct, entries, ne0, bytes, nb0, stat, stat_bytes,
-                       (const qhk::SpanOut *)cnt, (const qh_field_line *)W.insts,
-                       (const qhk::SpanIn *)W.spans, (const uint64_t *)W.aux,
-                       (const qhk::SpanOut *)W.hout, (const uint8_t *)W.slots, W.lens,
-                       (const qhk::SpanOut *)cnt2, (const qhk::DtRes *)res, status, consumed);
-    QH_HIP(hipGetLastError());
-  }
-  return 0;
+  return QH_LAUNCH(c, qh_k_dts_apply, (uint64_t)nsel * qhk::kGroupLanes, 256, src, tsel,
+                   (uint64_t)nsel, views, acct, entries, ne0, bytes, nb0, stat, stat_bytes, cnt,
+                   W.insts, W.spans, W.aux, W.hout, W.slots, W.lens, cnt2, res, status, consumed);
 }
 
 // ---------------------------------------------------------------------------
@@ -508,13 +446,13 @@ QH_EXPORT int qh_dtables_apply_batch(qh_ctx *c, const uint8_t *src, const qh_spa
 //   views    qh_k_dtc_views, a lane per view: qh_dt_view_check, its live
 //            count L_t, status[t], the error flag;
 //   scan     qh_k_scan_seg over L: E_t and the record total R;
-//   records  qh_k_dtc_records, a lane per output record: its view by a binary
-//            search in E, the source record bounds-checked (on failure the
+//   records  qh_k_dtc_records, a lane per output record: its view by
+//            span_find in E, the source record bounds-checked (on failure the
 //            error flag and its view's status), name_len + value_len;
 //   scan     qh_k_scan_seg over the lengths: B_r and the byte total;
 //   (sync)   one: both totals, both error flags, the scans' time-out words;
 //   write    qh_k_dtc_write, 16 lanes per output record: the two strings by
-//            dts_group_copy, the record by lane 0;
+//            group_copy, the record by lane 0;
 //   rebase   qh_k_dtc_rebase, a lane per view: ent_base = E_t - live_lo (its
 //            own launch: the write kernel reads the views it replaces).
 // No atomics in the write: regions are disjoint and fixed by the scans.
@@ -535,10 +473,10 @@ __global__ void __launch_bounds__(256) qh_k_dtc_views(
   }
   vcnt[t].len = (uint32_t)L;
   status[t] = ok ? 0 : QH_ERR_INVALID_ARGUMENT;
-  if (!ok) atomicExch(reinterpret_cast<unsigned long long *>(hdr + kDtErr), 1ull);
+  if (!ok) hdr_err(hdr);
 }
 
-// After the first scan: vcnt[t].off = E_t, hdr_a[kDtTot] = R.  Lanes r in
+// After the first scan: vcnt[t].off = E_t, hdr_a[kHdrTot] = R.  Lanes r in
 // [R, cap) zero their scan item (cap: the room of rcnt, laid out before R was
 // known on the host).  rcnt[r].status = the record's view.
 __global__ void __launch_bounds__(256) qh_k_dtc_records(
@@ -548,24 +486,18 @@ __global__ void __launch_bounds__(256) qh_k_dtc_records(
     int32_t *__restrict__ status, uint64_t *__restrict__ hdr_b) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= cap) return;
-  if (r >= hdr_a[kDtTot]) {
+  if (r >= hdr_a[kHdrTot]) {
     rcnt[r].len = 0;
     return;
   }
-  // the last view whose E is <= r: the views before it with the same E are empty
-  uint64_t lo = 0, hi = nviews;  // (E[lo] <= r < E[hi], E[nviews] = R)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (vcnt[mid].off <= r) lo = mid;
-    else hi = mid;
-  }
+  const uint64_t lo = span_find(vcnt, nviews, r);  // its view (E[lo] <= r < E[lo + 1], E[nviews] = R)
   const qh_dtable_view v = views[lo];
   const qh_dyn_entry e = entries[(uint64_t)v.ent_base + v.live_lo + (r - vcnt[lo].off)];
   uint32_t n = e.name_len + e.value_len;
   if (qh_dt_rec_check(&e, nbytes) != 0) {
     n = 0;
     status[lo] = QH_ERR_INVALID_ARGUMENT;  // (every lane that stores here stores the same)
-    atomicExch(reinterpret_cast<unsigned long long *>(hdr_b + kDtErr), 1ull);
+    hdr_err(hdr_b);
   }
   rcnt[r].len = n;
   rcnt[r].status = (int32_t)lo;
@@ -578,16 +510,16 @@ __global__ void __launch_bounds__(256) qh_k_dtc_write(
     const uint8_t *__restrict__ bytes, const SpanOut *__restrict__ vcnt,
     const SpanOut *__restrict__ rcnt, uint64_t nrec, qh_dyn_entry *__restrict__ entries_out,
     uint8_t *__restrict__ bytes_out) {
-  const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kDtLanes;
-  const uint32_t sl = threadIdx.x % kDtLanes;
+  const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (r >= nrec) return;  // (whole 16-lane groups)
   const SpanOut rc = rcnt[r];
   const uint32_t t = (uint32_t)rc.status;
   const qh_dtable_view v = views[t];
   const qh_dyn_entry e = entries[(uint64_t)v.ent_base + v.live_lo + (r - vcnt[t].off)];
   const qh_dyn_entry n = qh_dt_rec_compact(&e, rc.off);
-  dts_group_copy(bytes_out + n.name_off, bytes + e.name_off, e.name_len, sl);
-  dts_group_copy(bytes_out + n.value_off, bytes + e.value_off, e.value_len, sl);
+  group_copy(bytes_out + n.name_off, bytes + e.name_off, e.name_len, sl);
+  group_copy(bytes_out + n.value_off, bytes + e.value_off, e.value_len, sl);
   if (sl == 0) entries_out[r] = n;
 }
 
@@ -631,53 +563,38 @@ QH_EXPORT int qh_dtables_compact_batch(qh_ctx *c, size_t nviews, qh_dtable_view 
   uint64_t *hdr_a, *hdr_b = nullptr;
   rv = reserve_layout(c, kBufDtc, [&](qhs::Layout &l) {
     vcnt = l.take<qhk::SpanOut>(nviews);
-    hdr_a = l.take<uint64_t>(qhk::kDtHdr + tps_v);
+    hdr_a = l.take<uint64_t>(qhk::kHdrWords + tps_v);
   });
   if (rv) return rv;
-  if ((rv = reserve(c, kBufDtcHost, 16 * sizeof(uint64_t), qhs::kExact))) return rv;
-  uint64_t *h = mem<uint64_t>(c, kBufDtcHost);  // [0, 7): the first scan's words 1-7, [8, 15): the second's
+  uint64_t *h;  // [0, 7): the first scan's words 1-7, [8, 15): the second's
+  if ((rv = scan_hdr_host(c, &h))) return rv;
   memset(h, 0, 16 * sizeof(uint64_t));
   // the per-record pass and its scan over room for `cap` records
   uint64_t cap = 0;
   auto records = [&](uint64_t room) -> int {
     cap = room;
     const uint64_t tps_r = (cap + qhk::kScanTile - 1) / qhk::kScanTile;
-    const int r = reserve_layout(c, kBufDtcWork, [&](qhs::Layout &l) {
+    int r = reserve_layout(c, kBufDtcWork, [&](qhs::Layout &l) {
       rcnt = l.take<qhk::SpanOut>(cap);
-      hdr_b = l.take<uint64_t>(qhk::kDtHdr + tps_r);
+      hdr_b = l.take<uint64_t>(qhk::kHdrWords + tps_r);
     });
-    if (r) return r;
-    QH_HIP(hipMemsetAsync(hdr_b, 0, (qhk::kDtHdr + tps_r) * sizeof(uint64_t), c->stream));
-    {
-      Timed t(c, "qh_k_dtc_records");
-      hipLaunchKernelGGL(qhk::qh_k_dtc_records, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
-                         c->stream, (const qh_dtable_view *)views, (uint64_t)nviews, entries, nbytes,
-                         (const qhk::SpanOut *)vcnt, (const uint64_t *)hdr_a, rcnt, cap, status, hdr_b);
-      QH_HIP(hipGetLastError());
-    }
-    return launch_scan_seg(c, rcnt, cap, 1, hdr_b, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts);
+    if (r || (r = scan_hdr_reset(c, hdr_b, tps_r))) return r;
+    if ((r = QH_LAUNCH(c, qh_k_dtc_records, cap, 256, views, (uint64_t)nviews, entries, nbytes, vcnt,
+                       hdr_a, rcnt, cap, status, hdr_b)))
+      return r;
+    return launch_scan_seg(c, rcnt, cap, 1, hdr_b);
   };
-  auto totals = [&]() -> int {
-    QH_HIP(hipMemcpyAsync(h, hdr_a + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (hdr_b)
-      QH_HIP(hipMemcpyAsync(h + 8, hdr_b + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    QH_HIP(hipStreamSynchronize(c->stream));
-    return scan_seg_check(h[qhk::kDtTimeouts - 1] | h[8 + qhk::kDtTimeouts - 1], "compaction");
-  };
+  // both headers (the second once it exists), one wait
+  auto totals = [&]() -> int { return scan_hdr_wait2(c, hdr_a, hdr_b, h, "compaction"); };
 
-  QH_HIP(hipMemsetAsync(hdr_a, 0, (qhk::kDtHdr + tps_v) * sizeof(uint64_t), c->stream));
-  {
-    Timed t(c, "qh_k_dtc_views");
-    hipLaunchKernelGGL(qhk::qh_k_dtc_views, dim3((unsigned)((nviews + 255) / 256)), dim3(256), 0,
-                       c->stream, (const qh_dtable_view *)views, (uint64_t)nviews, nentries, vcnt, status,
-                       hdr_a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((rv = launch_scan_seg(c, vcnt, nviews, 1, hdr_a, qhk::kDtHdr, qhk::kDtTot, qhk::kDtTimeouts)))
+  if ((rv = scan_hdr_reset(c, hdr_a, tps_v))) return rv;
+  if ((rv = QH_LAUNCH(c, qh_k_dtc_views, nviews, 256, views, (uint64_t)nviews, nentries, vcnt, status,
+                      hdr_a)))
     return rv;
+  if ((rv = launch_scan_seg(c, vcnt, nviews, 1, hdr_a))) return rv;
   if (c->dtc_hint && (rv = records(c->dtc_hint + c->dtc_hint / 8 + 16))) return rv;
   if ((rv = totals())) return rv;  // the wait
-  const uint64_t nrec = h[qhk::kDtTot - 1];
+  const uint64_t nrec = h[qhk::kHdrTot - 1];
   if (nrec > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;  // (grid)
   if (nrec > cap) {
     // more than the room (or no room yet): the pass again for exactly this
@@ -686,24 +603,13 @@ QH_EXPORT int qh_dtables_compact_batch(qh_ctx *c, size_t nviews, qh_dtable_view 
     if ((rv = totals())) return rv;
   }
   c->dtc_hint = nrec;
-  if (h[qhk::kDtErr - 1] | h[8 + qhk::kDtErr - 1]) return QH_ERR_INVALID_ARGUMENT;
-  const uint64_t nbyte = h[8 + qhk::kDtTot - 1];
+  if (h[qhk::kHdrErr - 1] | h[8 + qhk::kHdrErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  const uint64_t nbyte = h[8 + qhk::kHdrTot - 1];
   *nentries_out = nrec;
   *nbytes_out = nbyte;
   if (nrec > entries_out_cap || nbyte > bytes_out_cap) return QH_ERR_NOMEM;
-  if (nrec) {
-    Timed t(c, "qh_k_dtc_write");
-    const unsigned grid = (unsigned)((nrec * qhk::kDtLanes + 255) / 256);
-    hipLaunchKernelGGL(qhk::qh_k_dtc_write, dim3(grid), dim3(256), 0, c->stream,
-                       (const qh_dtable_view *)views, entries, bytes, (const qhk::SpanOut *)vcnt,
-                       (const qhk::SpanOut *)rcnt, nrec, entries_out, bytes_out);
-    QH_HIP(hipGetLastError());
-  }
-  {
-    Timed t(c, "qh_k_dtc_rebase");
-    hipLaunchKernelGGL(qhk::qh_k_dtc_rebase, dim3((unsigned)((nviews + 255) / 256)), dim3(256), 0,
-                       c->stream, views, (uint64_t)nviews, (const qhk::SpanOut *)vcnt);
-    QH_HIP(hipGetLastError());
-  }
-  return 0;
+  if (nrec && (rv = QH_LAUNCH(c, qh_k_dtc_write, nrec * qhk::kGroupLanes, 256, views, entries, bytes,
+                              vcnt, rcnt, nrec, entries_out, bytes_out)))
+    return rv;
+  return QH_LAUNCH(c, qh_k_dtc_rebase, nviews, 256, views, (uint64_t)nviews, vcnt);
 }

@@ -6,7 +6,8 @@
 // table's byte log) into one buffer, all in HBM.  The per-line work is
 // qh_emit_core.h, the source the host function (qh_emit.c) compiles.
 //
-//   resolve  qh_k_emit_resolve, 16 lanes per selected block: the prefix
+//   resolve  qh_k_emit_resolve, 16 lanes (a group of qh_group.inc) per
+//            selected block: the prefix
 //            (reconstruct_ricnt, Base, blocked) once per block, then a lane
 //            per line in rounds of 16: the line's entry record and strs
 //            records gathered side by side, its field record into scratch
@@ -39,7 +40,6 @@ extern "C" void qh_plan_static_chains(const int8_t **first, const int8_t **next)
 
 namespace qhk {
 
-constexpr uint32_t kEmLanes = 16;
 constexpr uint32_t kEmStatRecs = 2048;  // the records' room ahead of the blob (99 * 20 B)
 constexpr uint32_t kEmStatBlob = 2048;  // the blob's room (about 1.6 KB)
 constexpr uint32_t kEmStatValueMax = 64;  // no static value is longer (the longest has 53 bytes)
@@ -65,7 +65,8 @@ struct EmLong {
 };
 
 // The header words behind the scan's tile states (zeroed per call; words
-// 1-6 read back with one copy).
+// 1-6 read back with one copy).  Its own layout, not qh_group.inc's: three
+// words more than the shared header has room for.
 enum : uint32_t {
   kEmCtr = 0,       // scan tile counter
   kEmFields = 1,    // total fields
@@ -78,13 +79,6 @@ enum : uint32_t {
   kEmHdr = 8
 };
 
-template <typename T>
-__device__ __forceinline__ T em_group_sum(T v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kEmLanes; k <<= 1) v += __shfl_xor(v, k, kEmLanes);
-  return v;
-}
-
 // cnt[p].len = block p's fields, cnt[nsel + p].len = its bytes in out;
 // tmp[i] = line i's field with its strings where they are (i < tmp_cap).
 __global__ void __launch_bounds__(256) qh_k_emit_resolve(
@@ -95,8 +89,8 @@ __global__ void __launch_bounds__(256) qh_k_emit_resolve(
   __shared__ uint32_t s_blocked, s_long;
   if (threadIdx.x == 0) s_blocked = s_long = 0;
   __syncthreads();
-  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kEmLanes;
-  const uint32_t sl = threadIdx.x % kEmLanes;
+  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (p < nsel) {  // (whole 16-lane groups)
     const uint64_t b = sel ? sel[p] : p;
     qh_emit_blk k;
@@ -112,11 +106,11 @@ __global__ void __launch_bounds__(256) qh_k_emit_resolve(
       qh_emit_head(&pf, v, in.status[b], &k);
       if (k.todo == QH_EMIT_RESCAN) {  // (rare: one lane parses the block again)
         if (sl == 0) k.status = qh_emit_rescan(&in, b, &k);
-        k.status = __shfl(k.status, 0, kEmLanes);
+        k.status = __shfl(k.status, 0, kGroupLanes);
       } else if (k.todo == QH_EMIT_LINES) {
         const uint32_t l0 = in.line_start[b], l1 = in.line_start[b + 1];
         int bad = 0;
-        for (uint32_t c0 = l0; c0 < l1; c0 += kEmLanes) {
+        for (uint32_t c0 = l0; c0 < l1; c0 += kGroupLanes) {
           const uint32_t i = c0 + sl;
           if (i < l1) {
             const qh_field_line l = in.lines[i];
@@ -133,10 +127,10 @@ __global__ void __launch_bounds__(256) qh_k_emit_resolve(
           }
         }
         {  // (any lane's failure is the block's; 2: a line past the scratch)
-          const int b1 = em_group_sum(bad & 1), b2 = em_group_sum(bad & 2);
+          const int b1 = group_sum(bad & 1), b2 = group_sum(bad & 2);
           bad = b2 ? 2 : (b1 ? 1 : 0);
         }
-        nbytes = em_group_sum((unsigned long long)nbytes);
+        nbytes = group_sum((unsigned long long)nbytes);
         if (bad) {
           k.status = QH_ERR_QPACK_DECOMPRESSION_FAILED;
           err = bad == 2;
@@ -192,8 +186,8 @@ __global__ void __launch_bounds__(256) qh_k_emit_write(
     const qh_field *__restrict__ tmp, qh_field *__restrict__ fields,
     uint32_t *__restrict__ field_start, uint8_t *__restrict__ out, SpanIn *__restrict__ out_blocks,
     uint32_t long_min, EmLong *__restrict__ list, uint64_t *__restrict__ hdr) {
-  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kEmLanes;
-  const uint32_t sl = threadIdx.x % kEmLanes;
+  const uint64_t p = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (p >= nsel) return;  // (whole 16-lane groups)
   const uint64_t b = sel ? sel[p] : p;
   const SpanOut cf = cnt[p], cb = cnt[nsel + p];
@@ -207,7 +201,7 @@ __global__ void __launch_bounds__(256) qh_k_emit_write(
   if (cb.len == 0 && nf == 0) return;  // failed, blocked, or nothing to write
   const uint32_t l0 = in.line_start[b];
   unsigned long long at = cb.off;
-  for (uint32_t c0 = 0; c0 < nf; c0 += kEmLanes) {
+  for (uint32_t c0 = 0; c0 < nf; c0 += kGroupLanes) {
     const uint32_t j = c0 + sl;
     qh_field f;
     unsigned long long x = 0;
@@ -215,14 +209,9 @@ __global__ void __launch_bounds__(256) qh_k_emit_write(
       f = tmp[l0 + j];
       x = qh_emit_field_bytes(&f, in.opts);
     }
-    unsigned long long incl = x;
-#pragma unroll
-    for (uint32_t k = 1; k < kEmLanes; k <<= 1) {
-      const unsigned long long y = __shfl_up(incl, k, kEmLanes);
-      if (sl >= k) incl += y;
-    }
+    const unsigned long long incl = group_incl64(x, sl);
     const unsigned long long mine = at + incl - x;
-    at += __shfl(incl, kEmLanes - 1, kEmLanes);
+    at += __shfl(incl, kGroupLanes - 1, kGroupLanes);
     if (j < nf) {
       if (out) {
         const uint8_t *nm = qh_emit_bytes(&in, f.name_where, f.name_off, 0);
@@ -377,15 +366,11 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
   if ((rv = ensure_tile_state(c, hwords * qhk::kScanTile))) return rv;
   uint64_t *hdr = mem<uint64_t>(c, kBufTileState);
   QH_HIP(hipMemsetAsync(hdr, 0, hwords * sizeof(uint64_t), c->stream));
-  const unsigned grid = (unsigned)((nsel * qhk::kEmLanes + 255) / 256);
+  const uint64_t lanes = (uint64_t)nsel * qhk::kGroupLanes;
   const uint32_t long_min = c->emit_long_min ? c->emit_long_min : kEmitLongMin;
-  {
-    Timed t(c, "qh_k_emit_resolve");
-    hipLaunchKernelGGL(qhk::qh_k_emit_resolve, dim3(grid), dim3(256), 0, c->stream, in, sel,
-                       (uint64_t)nsel, (uint64_t)nblocks, e->status, e->ricnt, cnt, tmp, nl, long_min,
-                       hdr);
-    QH_HIP(hipGetLastError());
-  }
+  if ((rv = QH_LAUNCH(c, qh_k_emit_resolve, lanes, 256, in, sel, (uint64_t)nsel, (uint64_t)nblocks,
+                      e->status, e->ricnt, cnt, tmp, nl, long_min, hdr)))
+    return rv;
   if ((rv = launch_scan_seg(c, cnt, nsel, 2, hdr, qhk::kEmHdr, qhk::kEmFields, qhk::kEmTimeouts)))
     return rv;
   if ((rv = reserve(c, kBufEmitHost, 8 * sizeof(uint64_t), qhs::kExact))) return rv;
@@ -399,20 +384,11 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
   if (h[4] || e->nfields > 0xFFFFFFFFull) return QH_ERR_INVALID_ARGUMENT;
   if (e->nfields > e->fields_cap || (e->out && e->out_need > e->out_cap)) return QH_ERR_NOMEM;
   if (e->nfields && !e->fields) return QH_ERR_INVALID_ARGUMENT;
-  {
-    Timed t(c, "qh_k_emit_write");
-    hipLaunchKernelGGL(qhk::qh_k_emit_write, dim3(grid), dim3(256), 0, c->stream, in, sel,
-                       (uint64_t)nsel, (const int32_t *)e->status, (const qhk::SpanOut *)cnt,
-                       (const qh_field *)tmp, e->fields, e->field_start, e->out,
-                       reinterpret_cast<qhk::SpanIn *>(e->out_blocks),
-                       long_min, list, hdr);
-    QH_HIP(hipGetLastError());
-  }
-  if (e->out && h[5]) {  // (some string is long; the list's length is read on the device)
-    Timed t(c, "qh_k_emit_copy_long");
-    hipLaunchKernelGGL(qhk::qh_k_emit_copy_long, dim3((unsigned)std::min(c->num_cus, 256)),
-                       dim3(256), 0, c->stream, (const qhk::EmLong *)list, (const uint64_t *)hdr);
-    QH_HIP(hipGetLastError());
-  }
+  if ((rv = QH_LAUNCH(c, qh_k_emit_write, lanes, 256, in, sel, (uint64_t)nsel, e->status, cnt, tmp,
+                      e->fields, e->field_start, e->out,
+                      reinterpret_cast<qhk::SpanIn *>(e->out_blocks), long_min, list, hdr)))
+    return rv;
+  if (e->out && h[5])  // (some string is long; the list's length is read on the device)
+    return QH_LAUNCH_GRID(c, qh_k_emit_copy_long, std::min(c->num_cus, 256), 256, list, hdr);
   return 0;
 }

@@ -9,7 +9,7 @@
 //           (the reference's rule, :1862, :1954, :1962); the strings that
 //           stay raw get length 0 in the encoder's span list, so the
 //           encoder writes the picked strings only, densely;
-//   size    qh_k_encsec_size, 16 lanes per section: its bytes (prefix +
+//   size    qh_k_encsec_size, 16 lanes (a group of qh_group.inc) per section: its bytes (prefix +
 //           representations) and each line's offset in it;
 //   scan    qh_k_scan over the section sizes: each section's offset in dst;
 //   (sync)  one: the picked Huffman bytes and dst bytes against the caps;
@@ -121,7 +121,6 @@ __global__ void __launch_bounds__(256) qh_k_encsec_pick(const SpanIn *__restrict
 //                 QH_ES_* instructions are accepted (qpack.c:2019-2069, :1272-1276);
 //   kEsSkippable  a section whose prefix has reserved != 0 is absent: no bytes.
 // Under either flag a line of opcode 0 is no bytes.
-constexpr uint32_t kSecLanes = 16;
 constexpr uint32_t kEsStream = 1u, kEsSkippable = 2u;
 __global__ void __launch_bounds__(256) qh_k_encsec_size(
     const qh_field_line *__restrict__ lines, const uint32_t *__restrict__ line_start,
@@ -129,8 +128,8 @@ __global__ void __launch_bounds__(256) qh_k_encsec_size(
     uint64_t nstrs, const uint32_t *__restrict__ hlen, uint64_t *__restrict__ loff,
     uint64_t loff_cap, SpanOut *__restrict__ sec, int32_t *__restrict__ err,
     unsigned long long *__restrict__ nlines_out, uint32_t flags) {
-  const uint64_t b = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kSecLanes;
-  const uint32_t sl = threadIdx.x % kSecLanes;
+  const uint64_t b = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (b >= nsec) return;  // (whole 16-lane groups)
   if (b == nsec - 1 && sl == 0) *nlines_out = line_start[nsec];
   unsigned long long sz = 2;
@@ -147,7 +146,7 @@ __global__ void __launch_bounds__(256) qh_k_encsec_size(
   }
   int bad = 0;
   const uint32_t l1 = line_start[b + 1];
-  for (uint32_t c0 = line_start[b]; c0 < l1; c0 += kSecLanes) {
+  for (uint32_t c0 = line_start[b]; c0 < l1; c0 += kGroupLanes) {
     const uint32_t i = c0 + sl;
     unsigned long long x = 0;
     if (i < l1 && !absent) {
@@ -186,17 +185,12 @@ __global__ void __launch_bounds__(256) qh_k_encsec_size(
         default: bad = 1;
       }
     }
-    unsigned long long incl = x;
-#pragma unroll
-    for (uint32_t k = 1; k < kSecLanes; k <<= 1) {
-      const unsigned long long y = __shfl_up(incl, k, kSecLanes);
-      if (sl >= k) incl += y;
-    }
+    const unsigned long long incl = group_incl64(x, sl);
     if (i < l1 && i < loff_cap) loff[i] = (b << 32) | (uint32_t)(sz + incl - x);
-    sz += __shfl(incl, kSecLanes - 1, kSecLanes);
+    sz += __shfl(incl, kGroupLanes - 1, kGroupLanes);
   }
 #pragma unroll
-  for (uint32_t k = 1; k < kSecLanes; k <<= 1) bad |= __shfl_xor(bad, k, kSecLanes);
+  for (uint32_t k = 1; k < kGroupLanes; k <<= 1) bad |= __shfl_xor(bad, k, kGroupLanes);
   if (sl) return;
   if (bad || sz > 0xFFFFFFFFull) {
     atomicExch(err, QH_ERR_INVALID_ARGUMENT);
@@ -408,26 +402,18 @@ int encsec_device(qh_ctx *c, EncSec &e) {
     if ((rv = count_device(c, e.plain, (const qhk::SpanIn *)e.strs, ns, hlen, nullptr)))
       return rv;
   }
-  auto pick_pass = [&]() -> int {
-    Timed t(c, "qh_k_encsec_pick");
-    hipLaunchKernelGGL(qhk::qh_k_encsec_pick, dim3((unsigned)((ns + 1023) / 1024)), dim3(256), 0,
-                       c->stream, (const qhk::SpanIn *)e.strs, (const uint32_t *)hlen, ns, in2,
-                       ctr, eout, (uint32_t)cgrid, reinterpret_cast<unsigned long long *>(btot));
-    QH_HIP(hipGetLastError());
-    return 0;
+  auto pick_pass = [&]() -> int {  // (four strings per lane)
+    return QH_LAUNCH_GRID(c, qh_k_encsec_pick, (ns + 1023) / 1024, 256, (const qhk::SpanIn *)e.strs,
+                          hlen, ns, in2, ctr, eout, (uint32_t)cgrid,
+                          reinterpret_cast<unsigned long long *>(btot));
   };
   if (ns && (rv = pick_pass())) return rv;
   qhk::SpanOut *sec = (qhk::SpanOut *)e.sections;
-  if (nb > 0x7fffffffull / qhk::kSecLanes * 256) return QH_ERR_INVALID_ARGUMENT;  // (grid)
+  if (nb > 0x7fffffffull / qhk::kGroupLanes * 256) return QH_ERR_INVALID_ARGUMENT;  // (grid)
   auto size_pass = [&](uint64_t cap) -> int {
-    Timed t(c, "qh_k_encsec_size");
-    hipLaunchKernelGGL(qhk::qh_k_encsec_size,
-                       dim3((unsigned)((nb * qhk::kSecLanes + 255) / 256)), dim3(256), 0,
-                       c->stream, e.lines, e.line_start, nb, e.pfx, (const qhk::SpanIn *)e.strs,
-                       ns, (const uint32_t *)hlen, mem<uint64_t>(c, kBufEncSecLoff), cap, sec, err,
-                       reinterpret_cast<unsigned long long *>(hdr + 5), e.flags);
-    QH_HIP(hipGetLastError());
-    return 0;
+    return QH_LAUNCH(c, qh_k_encsec_size, nb * qhk::kGroupLanes, 256, e.lines, e.line_start, nb, e.pfx,
+                     (const qhk::SpanIn *)e.strs, ns, hlen, mem<uint64_t>(c, kBufEncSecLoff), cap, sec,
+                     err, reinterpret_cast<unsigned long long *>(hdr + 5), e.flags);
   };
   if ((rv = size_pass(lcap))) return rv;
   if ((rv = launch_scan_seg(c, sec, nb, 1, hdr, kHdr, 1, 4))) return rv;
@@ -481,14 +467,9 @@ int encsec_device(qh_ctx *c, EncSec &e) {
     if ((rv = encode_picked_strings(picked + 64))) return rv;
   }
   const uint64_t items = nb + nl;
-  Timed t(c, "qh_k_encsec_write");
-  hipLaunchKernelGGL(qhk::qh_k_encsec_write, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
-                     c->stream, e.plain, (const qhk::SpanIn *)e.strs, (const uint32_t *)hlen,
-                     mem<const uint8_t>(c, kBufEncSecCodes), (const qhk::SpanOut *)eout, e.lines,
-                     e.line_start, nb, nl, e.pfx, mem<const uint64_t>(c, kBufEncSecLoff),
-                     (const qhk::SpanOut *)sec, e.dst, e.flags);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_encsec_write, items, 256, e.plain, (const qhk::SpanIn *)e.strs, hlen,
+                   mem<const uint8_t>(c, kBufEncSecCodes), eout, e.lines, e.line_start, nb, nl, e.pfx,
+                   mem<const uint64_t>(c, kBufEncSecLoff), sec, e.dst, e.flags);
 }
 
 }  // namespace

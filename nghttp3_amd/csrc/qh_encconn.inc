@@ -2,12 +2,12 @@
 // (include/qhuff.h qh_encode_conns_batch): the device twin of qh_encconn.c.
 // The per-field decision and the table step are qh_enc_core.h, the source the
 // host function compiles; only the two steps that read many entries (the
-// lookup, the head sum) are restated here, a 16-lane group at a time, and the
+// lookup, the head sum) are restated here, a 16-lane group at a time
+// (qh_group.inc: the group, the scan header and its error flag), and the
 // header's layout rule fixes every record's and byte's place, so lines, bytes,
 // log and state are equal byte for byte.
 //
-//   walk    qh_k_encc_walk, 16 lanes per connection (the shape of
-//           qh_k_dts_apply and the planner's lookup groups): the static image
+//   walk    qh_k_encc_walk, 16 lanes per connection: the static image
 //           in LDS; the connection's sections and fields in order; the state
 //           is held by every lane of the group (the same scalar code runs in
 //           all sixteen, so every branch is the same in the whole group and no
@@ -26,19 +26,13 @@
 //           streams as prefix-less sections of QH_ES_* lines; a sync each;
 //   commit  qh_k_encc_commit, 16 lanes per connection, once the four caps
 //           hold: live records and their keys relocated, new records, keys and
-//           bytes (dts_group_copy), view, acct and enc.
+//           bytes (group_copy), view, acct and enc.
 // No atomics but the table list's owner check: regions are disjoint and fixed
 // by the scan.
 
 #include "qh_enc_core.h"
 
 namespace qhk {
-
-constexpr uint32_t kEcLanes = 16;
-static_assert(kEcLanes == kPdLanes && kEcLanes == kDtLanes, "the group helpers are shared");
-
-// The header words ahead of the scan's tile states (as qh_dtset.inc's).
-enum : uint32_t { kEcCtr = 0, kEcTot = 1, kEcTimeouts = 5, kEcErr = 6, kEcHdr = 8 };
 
 // A connection's walk, left for the commit.
 struct EcRes {
@@ -87,12 +81,6 @@ struct EcArgs {
   uint64_t *hdr;
 };
 
-__device__ __forceinline__ unsigned long long ec_group_sum64(unsigned long long v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kEcLanes; k <<= 1) v += __shfl_xor(v, k, kEcLanes);
-  return v;
-}
-
 // qh_enc_find by a 16-lane group: every value but k, in, a, sp, incl and the
 // ballots' inputs is the same in all of its lanes, and every exit is taken by
 // the whole group.
@@ -104,24 +92,19 @@ __device__ __forceinline__ void ec_find(const qh_enc_tab &T, const qh_enc_walk &
   unsigned long long before = 0;  // the space of the entries newer than this round's
   bool last = false;
   for (uint64_t top = w.count; top > w.live_lo && !last;
-       top = top - w.live_lo > kEcLanes ? top - kEcLanes : w.live_lo) {
+       top = top - w.live_lo > kGroupLanes ? top - kGroupLanes : w.live_lo) {
     const bool in = top - w.live_lo > sl;  // lane sl looks at entry top - 1 - sl
     const uint64_t a = top - 1 - sl;
     qh_dyn_key k = {0, 0, 0, 0};
     if (in) k = qh_enc_key(&T, &w, a);
-    unsigned long long incl = in ? qh_enc_key_space(&k) : 0ull;
-#pragma unroll
-    for (uint32_t d = 1; d < kEcLanes; d <<= 1) {
-      const unsigned long long y = __shfl_up(incl, d, kEcLanes);
-      if (sl >= d) incl += y;
-    }
+    const unsigned long long incl = group_incl64(in ? qh_enc_key_space(&k) : 0ull, sl);
     const unsigned long long suffix = before + incl;
     const bool can = in && suffix <= w.cap;  // :791-795
-    if (pd_group_ballot(in && !can)) last = true;  // (the older ones are beyond the capacity too)
+    if (group_ballot(in && !can)) last = true;  // (the older ones are beyond the capacity too)
     const bool nm = can && qh_dyn_key_name(&k, f.name_id, name_len);
-    const uint32_t m_nm = pd_group_ballot(nm);
-    const uint32_t m_vc = pd_group_ballot(nm && qh_dyn_key_value(&k, value_len));
-    const uint32_t m_ref = pd_group_ballot(w.allow_blocking || a + 1 <= w.e.krcnt);  // :819
+    const uint32_t m_nm = group_ballot(nm);
+    const uint32_t m_vc = group_ballot(nm && qh_dyn_key_value(&k, value_len));
+    const uint32_t m_ref = group_ballot(w.allow_blocking || a + 1 <= w.e.krcnt);  // :819
     uint32_t m = m_nm;
     while (m) {  // candidates, newest first
       const uint32_t j = (uint32_t)__ffs((int)m) - 1;
@@ -144,19 +127,19 @@ __device__ __forceinline__ void ec_find(const qh_enc_tab &T, const qh_enc_walk &
       }
       if (!vc_j || vl != value_len) continue;
       if (!r->have_vhash) {
-        r->vhash = pd_group_sum(pd_hash_part(T.plain + value_off, value_len, sl, kEcLanes));
+        r->vhash = group_sum(pd_hash_part(T.plain + value_off, value_len, sl, kGroupLanes));
         r->have_vhash = 1;
       }
-      if ((uint32_t)__shfl(k.value_hash, (int)j, kEcLanes) != r->vhash) continue;
+      if ((uint32_t)__shfl(k.value_hash, (int)j, kGroupLanes) != r->vhash) continue;
       if (!pd_group_eq(vp, T.plain + value_off, value_len, sl)) continue;
       if (ref_j) {
         r->exact1 = aj + 1;
-        r->exact_suffix = __shfl(suffix, (int)j, kEcLanes);
+        r->exact_suffix = __shfl(suffix, (int)j, kGroupLanes);
         return;
       }
       r->pb = 1;
     }
-    before += __shfl(incl, (int)kEcLanes - 1, kEcLanes);
+    before += __shfl(incl, (int)kGroupLanes - 1, kGroupLanes);
   }
 }
 
@@ -164,14 +147,14 @@ __device__ __forceinline__ void ec_find(const qh_enc_tab &T, const qh_enc_walk &
 __device__ __forceinline__ uint64_t ec_head(const qh_enc_tab &T, const qh_enc_walk &w, uint64_t to,
                                             uint32_t sl) {
   unsigned long long s = 0;
-  for (uint64_t a0 = w.live_lo; a0 < to; a0 += kEcLanes) {
+  for (uint64_t a0 = w.live_lo; a0 < to; a0 += kGroupLanes) {
     const uint64_t a = a0 + sl;
     if (a < to) {
       const qh_dyn_key k = qh_enc_key(&T, &w, a);
       s += qh_enc_key_space(&k);
     }
   }
-  return ec_group_sum64(s);
+  return group_sum(s);
 }
 
 // (the walk is serial per connection and latency-bound; the parallelism is
@@ -183,8 +166,8 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
   __shared__ uint4 s_img[kEmStatImage / 16];
   for (uint32_t k = threadIdx.x; k < kEmStatImage / 16; k += 256) s_img[k] = a.image[k];
   __syncthreads();
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kEcLanes;
-  const uint32_t sl = threadIdx.x % kEcLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.nconns) return;  // (whole 16-lane groups)
   const uint8_t *const img = reinterpret_cast<const uint8_t *>(s_img);
   const EmStatExtra *const x = reinterpret_cast<const EmStatExtra *>(img + kEmStatRecs + kEmStatBlob);
@@ -195,12 +178,13 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
   t.next = x->next;
   t.tok = x;
 
-  // the table list and the connection's ranges: nothing is indexed before it
+  // the table list (table_claim's rule; every lane reads its own tt, so none
+  // is broadcast) and the connection's ranges: nothing is indexed before it
   // is known to lie inside its array
   const uint64_t tt = a.tsel ? a.tsel[c] : c;
   int err = tt >= a.ntables;
   if (!err && a.tsel && sl == 0) err = atomicExch(&a.owner[tt], (uint32_t)c) != 0xFFFFFFFFu;  // (named twice)
-  err = __shfl(err, 0, kEcLanes);
+  err = __shfl(err, 0, kGroupLanes);
   const uint64_t s0 = a.conn_start[c], s1 = a.conn_start[c + 1];
   uint64_t f0 = 0, f1 = 0;
   if (s0 > s1 || s1 > a.nsec || (c == 0 && s0 != 0) || (c + 1 == a.nconns && s1 != a.nsec)) {
@@ -215,7 +199,7 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
   memset(&res, 0, sizeof(res));
   if (err) {
     if (sl == 0) {
-      atomicExch(reinterpret_cast<unsigned long long *>(a.hdr + kEcErr), 1ull);
+      hdr_err(a.hdr);
       res.status = QH_ERR_INVALID_ARGUMENT;
       a.res[c] = res;
       a.cnt[c].len = 0;
@@ -274,7 +258,7 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
       if (f.lookup) {
         f.name_id = qh_dyn_name_id(
             f.token,
-            f.token == -1 ? pd_group_sum(pd_hash_part(a.plain + nm.off, nm.len, sl, kEcLanes)) : 0);
+            f.token == -1 ? group_sum(pd_hash_part(a.plain + nm.off, nm.len, sl, kGroupLanes)) : 0);
         ec_find(T, w, f, nm.off, nm.len, vs.off, vs.len, sl, &r);
         if (r.bad) {
           bad = true;
@@ -284,7 +268,7 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
       qh_enc_choose(&w, &r, &f);
       if (!f.decided) qh_enc_head_verdict(&f, ec_head(T, w, f.head_to, sl));
       if (f.verdict && f.kind != QH_EA_DUPLICATE && !r.have_vhash) {
-        r.vhash = pd_group_sum(pd_hash_part(a.plain + vs.off, vs.len, sl, kEcLanes));
+        r.vhash = group_sum(pd_hash_part(a.plain + vs.off, vs.len, sl, kGroupLanes));
         r.have_vhash = 1;
       }
       // (the scratch record and key of an insert are stored by every lane, the
@@ -308,15 +292,15 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
   uint64_t nrec = w.nnew ? (w.count_in - w.live_lo_in) + w.nnew : 0, nbyte = w.byte_at;
   if (nrec > 0xFFFFFFFFull || nbyte > 0xFFFFFFFFull) err = 1;  // (one scan item each)
   if (err) {
-    if (sl == 0) atomicExch(reinterpret_cast<unsigned long long *>(a.hdr + kEcErr), 1ull);
+    if (sl == 0) hdr_err(a.hdr);
     bad = true;
   }
   if (bad) {  // nothing of it is written: absent sections, an empty stream
     qh_field_line zl;
     memset(&zl, 0, sizeof(zl));
-    for (uint64_t i = f0 + sl; i < f1; i += kEcLanes) a.lines[i] = zl;
-    for (uint64_t k = sl; k < nes_all; k += kEcLanes) es[k] = zl;
-    for (uint64_t s = s0 + sl; s < s1; s += kEcLanes) {
+    for (uint64_t i = f0 + sl; i < f1; i += kGroupLanes) a.lines[i] = zl;
+    for (uint64_t k = sl; k < nes_all; k += kGroupLanes) es[k] = zl;
+    for (uint64_t s = s0 + sl; s < s1; s += kGroupLanes) {
       a.prefixes[s] = qh_section_prefix{0, 0, 0, 1u};  // (reserved: absent; the commit clears it)
       a.max_cnt[s] = 0;
       a.min_cnt[s] = UINT64_MAX;
@@ -345,13 +329,13 @@ __global__ void __launch_bounds__(256, QH_ENCC_MIN_WAVES) qh_k_encc_walk(const E
 // only the absent sections' marks are cleared, so that the caller's prefixes
 // are the host twin's on QH_ERR_NOMEM too.
 __global__ void __launch_bounds__(256) qh_k_encc_commit(const EcArgs a, int write) {
-  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kEcLanes;
-  const uint32_t sl = threadIdx.x % kEcLanes;
+  const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroupLanes;
+  const uint32_t sl = threadIdx.x % kGroupLanes;
   if (c >= a.nconns) return;  // (whole 16-lane groups)
   const EcRes r = a.res[c];
   const uint64_t s0 = a.conn_start[c], s1 = a.conn_start[c + 1];
   if (r.status != 0) {
-    for (uint64_t s = s0 + sl; s < s1; s += kEcLanes) a.prefixes[s].reserved = 0;
+    for (uint64_t s = s0 + sl; s < s1; s += kGroupLanes) a.prefixes[s].reserved = 0;
     return;
   }
   if (!write) return;
@@ -361,7 +345,7 @@ __global__ void __launch_bounds__(256) qh_k_encc_commit(const EcArgs a, int writ
   const uint64_t ent_at = a.nentries + a.cnt[c].off, byte0 = a.nbytes + a.cnt[a.nconns + c].off;
   if (r.nnew) {  // the table moves: its records live on entry and their keys, then the inserts
     const uint64_t L = r.live_in, from = (uint64_t)v.ent_base + v.live_lo;
-    for (uint64_t j = sl; j < L; j += kEcLanes) {
+    for (uint64_t j = sl; j < L; j += kGroupLanes) {
       a.entries[ent_at + j] = a.entries[from + j];
       a.keys[ent_at + j] = a.keys[from + j];
     }
@@ -373,10 +357,10 @@ __global__ void __launch_bounds__(256) qh_k_encc_commit(const EcArgs a, int writ
       const qh_enc_new n = a.nrec[f0 + j];
       const qh_dyn_entry e = qh_enc_commit_rec(&n, byte0);
       if (n.e.reserved & QH_EN_NAME_OWN)
-        dts_group_copy(a.bytes + e.name_off, qh_enc_src_ptr(&T, n.name_src), e.name_len, sl);
+        group_copy(a.bytes + e.name_off, qh_enc_src_ptr(&T, n.name_src), e.name_len, sl);
       if (n.e.reserved & QH_EN_VALUE_OWN)
-        dts_group_copy(a.bytes + e.value_off, qh_enc_src_ptr(&T, n.value_src), e.value_len, sl);
-      if (sl == j % kEcLanes) {
+        group_copy(a.bytes + e.value_off, qh_enc_src_ptr(&T, n.value_src), e.value_len, sl);
+      if (sl == j % kGroupLanes) {
         a.entries[ent_at + L + j] = e;
         a.keys[ent_at + L + j] = a.nkeys[f0 + j];
       }
@@ -434,7 +418,6 @@ QH_EXPORT int qh_encode_conns_batch(
   const uint64_t ne0 = *nentries, nb0 = *nbytes;
   const uint64_t nel = (uint64_t)nfields + 2 * (uint64_t)nsections;
   const uint64_t tps = (nconns + qhk::kScanTile - 1) / qhk::kScanTile;
-  const uint64_t hwords = qhk::kEcHdr + 2 * tps;
 
   qhk::EcArgs a{};
   rv = reserve_layout(c, kBufEncConn, [&](qhs::Layout &l) {
@@ -445,11 +428,11 @@ QH_EXPORT int qh_encode_conns_batch(
     a.res = l.take<qhk::EcRes>(nconns);
     a.cnt = l.take<qhk::SpanOut>(2 * (uint64_t)nconns);
     a.owner = l.take<uint32_t>(ntables);
-    a.hdr = l.take<uint64_t>(hwords);
+    a.hdr = l.take<uint64_t>(qhk::kHdrWords + 2 * tps);
   });
   if (rv) return rv;
-  if ((rv = reserve(c, kBufEncConnHost, 8 * sizeof(uint64_t), qhs::kExact))) return rv;
-  uint64_t *h = mem<uint64_t>(c, kBufEncConnHost);
+  uint64_t *h;
+  if ((rv = scan_hdr_host(c, &h))) return rv;
   a.plain = plain;
   a.strs = reinterpret_cast<const qhk::SpanIn *>(strs);
   a.nfields = nfields;
@@ -476,21 +459,14 @@ QH_EXPORT int qh_encode_conns_batch(
   a.status = status;
   a.image = mem<const uint4>(c, kBufEmitStatic);
 
-  QH_HIP(hipMemsetAsync(a.hdr, 0, hwords * sizeof(uint64_t), c->stream));
+  if ((rv = scan_hdr_reset(c, a.hdr, 2 * tps))) return rv;
   if (nel) QH_HIP(hipMemsetAsync(a.elines, 0, nel * sizeof(qh_field_line), c->stream));
-  if (tsel) QH_HIP(hipMemsetAsync(a.owner, 0xFF, ntables * 4, c->stream));
-  const unsigned grid = (unsigned)(((uint64_t)nconns * qhk::kEcLanes + 255) / 256);
-  {
-    Timed t(c, "qh_k_encc_walk");
-    hipLaunchKernelGGL(qhk::qh_k_encc_walk, dim3(grid), dim3(256), 0, c->stream, a);
-    QH_HIP(hipGetLastError());
-  }
-  if ((rv = launch_scan_seg(c, a.cnt, nconns, 2, a.hdr, qhk::kEcHdr, qhk::kEcTot, qhk::kEcTimeouts)))
-    return rv;
-  QH_HIP(hipMemcpyAsync(h, a.hdr + 1, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  QH_HIP(hipStreamSynchronize(c->stream));  // the first wait
-  if ((rv = scan_seg_check(h[qhk::kEcTimeouts - 1], "connection-encoder"))) return rv;
-  if (h[qhk::kEcErr - 1]) return QH_ERR_INVALID_ARGUMENT;
+  if ((rv = table_owner_reset(c, tsel, ntables, a.owner))) return rv;
+  const uint64_t lanes = (uint64_t)nconns * qhk::kGroupLanes;
+  if ((rv = QH_LAUNCH(c, qh_k_encc_walk, lanes, 256, a))) return rv;
+  if ((rv = launch_scan_seg(c, a.cnt, nconns, 2, a.hdr))) return rv;
+  if ((rv = scan_hdr_wait(c, a.hdr, h, "connection-encoder"))) return rv;  // the first wait
+  // (h is read here, before encsec_device's own waits)
   const uint64_t need_e = ne0 + h[0], need_b = nb0 + h[1];
 
   // the bytes: the sections, then the streams (a wait each)
@@ -507,10 +483,6 @@ QH_EXPORT int qh_encode_conns_batch(
   *dst_need = se.need;
   *edst_need = ee.need;
   const bool fits = !rv_s && !rv_e && need_e <= entries_cap && need_b <= bytes_cap;
-  {
-    Timed t(c, "qh_k_encc_commit");
-    hipLaunchKernelGGL(qhk::qh_k_encc_commit, dim3(grid), dim3(256), 0, c->stream, a, fits ? 1 : 0);
-    QH_HIP(hipGetLastError());
-  }
+  if ((rv = QH_LAUNCH(c, qh_k_encc_commit, lanes, 256, a, fits ? 1 : 0))) return rv;
   return fits ? 0 : QH_ERR_NOMEM;
 }

@@ -6,7 +6,8 @@
 // static choice, the section's table state, the key predicates, the line
 // and the prefix are qh_plan_core.h, the source the host function
 // (qh_static.c) compiles; only the walk over the live entries is restated
-// here, a 16-lane group at a time instead of an entry at a time.
+// here, a 16-lane group (qh_group.inc) at a time instead of an entry at a
+// time.
 //
 //   keys    qh_k_dyn_keys, one lane per log entry: the 16-byte key of
 //           (token or name hash, lengths, value hash);
@@ -37,7 +38,6 @@
 
 namespace qhk {
 
-constexpr uint32_t kPdLanes = 16;  // lanes of a lookup group (the emit and size kernels' shape)
 // The key hash's terms summed over the aligned 16-byte chunks first, first +
 // stride, ... of those that hold a byte of the n bytes at p.
 __device__ __forceinline__ uint32_t pd_hash_part(const uint8_t *__restrict__ p, uint32_t n,
@@ -62,28 +62,17 @@ __device__ __forceinline__ uint32_t pd_hash_part(const uint8_t *__restrict__ p, 
   return h;
 }
 
-__device__ __forceinline__ uint32_t pd_group_sum(uint32_t v) {
-#pragma unroll
-  for (uint32_t k = 1; k < kPdLanes; k <<= 1) v += __shfl_xor(v, k, kPdLanes);
-  return v;
-}
-
-// The group's 16 bits of a wave ballot.
-__device__ __forceinline__ uint32_t pd_group_ballot(bool p) {
-  return (uint32_t)(__ballot(p) >> ((threadIdx.x & 63u) & ~(kPdLanes - 1))) & 0xFFFFu;
-}
-
 // Whether the n bytes at a and at b are equal, by the group: lane sl takes
 // bytes [16 sl, +16) of every 256.
 __device__ __forceinline__ bool pd_group_eq(const uint8_t *__restrict__ a,
                                             const uint8_t *__restrict__ b, uint32_t n,
                                             uint32_t sl) {
   uint32_t diff = 0;
-  for (uint64_t at = 16 * sl; at < n; at += 16 * kPdLanes) {
+  for (uint64_t at = 16 * sl; at < n; at += 16 * kGroupLanes) {
     const uint32_t m = n - at < 16 ? (uint32_t)(n - at) : 16u;
     for (uint32_t j = 0; j < m; ++j) diff |= (uint32_t)(a[at + j] ^ b[at + j]);
   }
-  return pd_group_ballot(diff != 0) == 0;
+  return group_ballot(diff != 0) == 0;
 }
 
 __global__ void __launch_bounds__(256) qh_k_dyn_keys(const qh_dyn_entry *__restrict__ entries,
@@ -139,14 +128,14 @@ __device__ __forceinline__ void pd_find(const qh_plan_dyn &d, const uint8_t *__r
                                         const PdQ &q, uint32_t sl, PdR *out) {
   const uint32_t name_id = qh_dyn_name_id(
       q.token,
-      q.token == -1 ? pd_group_sum(pd_hash_part(plain + q.name_off, q.name_len, sl, kPdLanes)) : 0);
+      q.token == -1 ? group_sum(pd_hash_part(plain + q.name_off, q.name_len, sl, kGroupLanes)) : 0);
   uint32_t vhash = 0;
   bool have_vhash = false, done = false;
   uint64_t name1 = 0, exact1 = 0;
   // (Loading the keys of four rounds side by side and looking at them a
   // round at a time was slower: 336 us against 273 for config 4's fields and
   // 100 entries, at 149 registers and three waves per SIMD.)
-  for (uint64_t top = q.hi; top > q.lo && !done; top = top - q.lo > kPdLanes ? top - kPdLanes : q.lo) {
+  for (uint64_t top = q.hi; top > q.lo && !done; top = top - q.lo > kGroupLanes ? top - kGroupLanes : q.lo) {
     const bool in = top - q.lo > sl;  // lane sl looks at entry top - 1 - sl
     qh_dyn_key k = {0, 0, 0, 0};
     if (in) {
@@ -157,8 +146,8 @@ __device__ __forceinline__ void pd_find(const qh_plan_dyn &d, const uint8_t *__r
       k.value_hash = x.w;
     }
     const bool nm = in && qh_dyn_key_name(&k, name_id, q.name_len);
-    const uint32_t m_nm = pd_group_ballot(nm);
-    const uint32_t m_vc = pd_group_ballot(nm && qh_dyn_key_value(&k, q.value_len));
+    const uint32_t m_nm = group_ballot(nm);
+    const uint32_t m_vc = group_ballot(nm && qh_dyn_key_value(&k, q.value_len));
     uint32_t m = name1 ? m_vc : m_nm;
     while (m) {  // candidates, newest first
       const uint32_t j = (uint32_t)__ffs((int)m) - 1;
@@ -178,10 +167,10 @@ __device__ __forceinline__ void pd_find(const qh_plan_dyn &d, const uint8_t *__r
       }
       if (!((m_vc >> j) & 1) || e.value_len != q.value_len) continue;
       if (!have_vhash) {
-        vhash = pd_group_sum(pd_hash_part(plain + q.value_off, q.value_len, sl, kPdLanes));
+        vhash = group_sum(pd_hash_part(plain + q.value_off, q.value_len, sl, kGroupLanes));
         have_vhash = true;
       }
-      if (__shfl(k.value_hash, (int)j, kPdLanes) != vhash) continue;
+      if (__shfl(k.value_hash, (int)j, kGroupLanes) != vhash) continue;
       if (pd_group_eq(d.dyn_bytes + e.value_off, plain + q.value_off, q.value_len, sl)) {
         exact1 = a + 1;
         done = true;
@@ -225,7 +214,7 @@ __global__ void __launch_bounds__(256)
   t.first = x->first;
   t.next = x->next;
   t.tok = x;
-  const uint32_t grp = threadIdx.x / kPdLanes, sl = threadIdx.x % kPdLanes;
+  const uint32_t grp = threadIdx.x / kGroupLanes, sl = threadIdx.x % kGroupLanes;
 #pragma unroll 1
   for (uint32_t q = 0; q < kPlPer; ++q) {
     const uint64_t i = i0 + (uint64_t)q * 256 + threadIdx.x;
@@ -278,7 +267,7 @@ __global__ void __launch_bounds__(256)
     }
     __syncthreads();
     const uint32_t nq = s_nq[q];
-    for (uint32_t k = grp; k < nq; k += 256 / kPdLanes) pd_find(a.d, plain, s_q[k], sl, &s_r[k]);
+    for (uint32_t k = grp; k < nq; k += 256 / kGroupLanes) pd_find(a.d, plain, s_q[k], sl, &s_r[k]);
     __syncthreads();
     if (active) {
       uint64_t ref1 = 0;
@@ -356,21 +345,13 @@ int plan_dyn_device(qh_ctx *c, const uint8_t *plain, const qh_span_in *strs, con
                          a);
     QH_HIP(hipGetLastError());
   }
-  Timed t(c, "qh_k_plan_prefix");
-  hipLaunchKernelGGL(qhk::qh_k_plan_prefix, dim3((unsigned)((nsec + 255) / 256)), dim3(256), 0,
-                     c->stream, a, pfx);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_plan_prefix, nsec, 256, a, pfx);
 }
 
 int dyn_keys_device(qh_ctx *c, const qh_dyn_entry *entries, const uint8_t *bytes, uint64_t nbytes,
                     uint64_t first, uint64_t n, qh_dyn_key *keys) {
   if (n == 0) return 0;
-  Timed t(c, "qh_k_dyn_keys");
-  hipLaunchKernelGGL(qhk::qh_k_dyn_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                     entries, bytes, nbytes, first, n, keys);
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_dyn_keys, n, 256, entries, bytes, nbytes, first, n, keys);
 }
 
 // The table states of a host call: their kPieces pieces, and (once the

@@ -290,14 +290,9 @@ int sections_finish(qh_ctx *c, const uint8_t *src, const qh_span_in *blocks, siz
                        (const int8_t *)(nh ? L.hverdict : nullptr));
     QH_HIP(hipGetLastError());
   } else if (ns) {
-    const uint64_t grid = (ns + 255) / 256;
-    Timed t(c, "qh_k_sections_post");
-    hipLaunchKernelGGL(qhk::qh_k_sections_post, dim3((unsigned)grid), dim3(256), 0, c->stream,
-                       src, (const qhk::SpanIn *)s->spans, (const uint64_t *)L.aux, ns,
-                       (const qhk::SpanOut *)L.hout, (const uint8_t *)s->dst,
-                       (qhk::SpanOut *)s->strs, s->verdict, s->token, s->status,
-                       (const int8_t *)(nh ? L.hverdict : nullptr));
-    QH_HIP(hipGetLastError());
+    return QH_LAUNCH(c, qh_k_sections_post, ns, 256, src, (const qhk::SpanIn *)s->spans, L.aux, ns,
+                     (const qhk::SpanOut *)L.hout, s->dst, (qhk::SpanOut *)s->strs, s->verdict, s->token, s->status,
+                     (const int8_t *)(nh ? L.hverdict : nullptr));
   }
   return 0;
 }

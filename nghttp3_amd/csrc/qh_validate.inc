@@ -29,15 +29,7 @@ static int check_fields_device(qh_ctx *c, const uint8_t *src, const SpanIn *in, 
                                int8_t *verdict) {
   if (n == 0) return 0;
   const int block = 256;
-  const uint64_t grid = (n + block - 1) / block;
-  if (grid > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
-  {
-    Timed t(c, "qh_k_check_fields");
-    hipLaunchKernelGGL(qhk::qh_k_check_fields, dim3((unsigned)grid), dim3(block), 0, c->stream,
-                       src, in, verdict, n);
-  }
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_check_fields, n, block, src, in, verdict, n);
 }
 
 // Device strings are read in aligned 16-byte chunks that each hold a byte
@@ -103,15 +95,7 @@ static int lookup_tokens_device(qh_ctx *c, const uint8_t *src, const SpanIn *in,
                                 int32_t *token) {
   if (n == 0) return 0;
   const int block = 256;
-  const uint64_t grid = (n + block - 1) / block;
-  if (grid > 0x7fffffffull) return QH_ERR_INVALID_ARGUMENT;
-  {
-    Timed t(c, "qh_k_lookup_tokens");
-    hipLaunchKernelGGL(qhk::qh_k_lookup_tokens, dim3((unsigned)grid), dim3(block), 0, c->stream,
-                       src, in, token, n);
-  }
-  QH_HIP(hipGetLastError());
-  return 0;
+  return QH_LAUNCH(c, qh_k_lookup_tokens, n, block, src, in, token, n);
 }
 
 QH_EXPORT int qh_lookup_tokens_batch(qh_ctx *c, const uint8_t *src, const qh_span_in *in,

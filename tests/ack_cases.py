@@ -450,6 +450,32 @@ class Pair:
         return st.tolist(), co.tolist()
 
 
+def empty_runs_pair(n, dev=None):
+    """n connections of which those at both ends and in the middle
+    (blocked_cases.empty_runs) have no reference: a record call in which they
+    gain nothing, a read, a record call in which only they gain (the others
+    stay: runs of equal offsets everywhere else), the compaction."""
+    from blocked_cases import empty_runs
+    q = empty_runs(n)
+    p = Pair(n, dev=dev)
+    p.set_insert_count(500)
+    p.record([[(4 * i, 10 + i + t, 1 + i) for i in range(L)] for t, L in enumerate(q)])
+    assert p.sets[0].refs_records()[0]["n"].tolist() == q
+    st, _ = p.read([ack(4 * (L - 1)) + incr(2) if L else b"" for L in q])
+    assert not any(st)
+    if n > 1:
+        p.record([[] if L else [(100, 400 + t, 7)] for t, L in enumerate(q)])
+    p.check()
+    before = queues(p.sets[0])
+    for s in p.sets:
+        s.compact_refs(*([dev.codec] if s.device is not None else []))
+    if dev is not None:
+        same_ack_state(p.sets[0], p.sets[1])
+    assert queues(p.sets[0]) == before
+    assert p.sets[0].nrefs == sum(len(x) for x in before)
+    p.check()
+
+
 # ---- the whole loop, host twin and device side by side -----------------------
 
 class Loop:

@@ -493,9 +493,41 @@ def case_compaction(dev=None):
     assert (p.sets[0].nblks, p.sets[0].npend) == (0, 0)
 
 
+def empty_runs(n):
+    """Record counts of n tables with runs of empty ones at the head, in the
+    middle and at the tail (equal offsets after a scan, at its first and last
+    positions too); n = 2: the first is empty, n = 3: both ends are."""
+    if n < 4:
+        return [[3], [0, 2], [0, 2, 0]][n - 1]
+    empty = {0, 1, n // 2, n // 2 + 1, n - 2, n - 1}
+    return [0 if t in empty else 1 + t % 3 for t in range(n)]
+
+
+def case_empty_runs(dev=None):
+    """1, 2, 3, 17 and 65 tables (a group alone, groups 1 and 2 of a wave, a
+    second wave, a second workgroup), the tables at both ends and in the middle
+    without a block: in a push (their runs accept nothing), a release, a
+    cancellation and the compactions."""
+    for n in (1, 2, 3, 17, 65):
+        q = empty_runs(n)
+        p = Pair(n, 100, dev)
+        p.push([B(t, 4 * k, 1 + k, n=3 + (t + k) % 30) for t in range(n) for k in range(q[t])])
+        assert p.sets[0].blocked_records()[0]["n"].tolist() == q
+        # every table has a run; those of the empty tables accept nothing
+        p.push([B(t, 400, 2, n=17, status=BLOCKED if q[t] else 0) for t in range(n)])
+        assert p.sets[0].blocked_records()[0]["n"].tolist() == [x + 1 if x else 0 for x in q]
+        p.set_insert_count(1)
+        o = p.release()
+        assert np.diff(o["start"]).tolist() == [1 if x else 0 for x in q]
+        p.compact()
+        p.cancel([(400, t) for t in range(0, n, 2)])
+        p.compact()
+        assert p.sets[0].nblks == int(p.sets[0].blocked_records()[0]["n"].sum())
+
+
 CASES = [case_duplicate_before_limit, case_max_blocked_zero, case_release_none_some_all,
          case_push_on_top_of_a_release, case_cancel, case_nomem_exact_needs,
-         case_list_errors_write_nothing, case_compaction]
+         case_list_errors_write_nothing, case_compaction, case_empty_runs]
 
 
 # ---- the loop with the encoder streams delivered in two halves ----------------------

@@ -117,6 +117,16 @@ def count_case(n: int):
     return Case("count %d" % n, tables)
 
 
+def empty_runs_case(n: int):
+    """n tables, those at both ends and in the middle without an entry
+    (blocked_cases.empty_runs): runs of views with the same offset in the
+    compaction's scan, at its first and last positions too."""
+    from blocked_cases import empty_runs
+    return Case("empty runs %d" % n,
+                [(4096, [[raw_insert(b"k%d" % k, text((5 * t + k) % 40, t)) for k in range(L)]])
+                 for t, L in enumerate(empty_runs(n))])
+
+
 STRING_LENGTHS = (0, 1, 15, 16, 17, 31, 32, 33)
 
 

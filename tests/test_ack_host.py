@@ -213,6 +213,11 @@ def test_layout_rules():
     p.check()
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 65])
+def test_connections_without_references_at_both_ends_and_in_the_middle(n):
+    ac.empty_runs_pair(n)
+
+
 def test_record_nomem_and_sentinels():
     p = ac.Pair(3)
     p.record([[(4, 5, 2)], [(8, 1, 1)], []])

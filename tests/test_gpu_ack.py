@@ -119,6 +119,14 @@ def test_unequal_queues(dev):
     p.check()
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 65])
+def test_connections_without_references_at_both_ends_and_in_the_middle(dev, n):
+    """Groups 1 and 2 of a wave, a second wave and a second workgroup; the
+    relocation's search over runs of equal offsets at its first and last
+    positions (record and compact)."""
+    ac.empty_runs_pair(n, dev)
+
+
 def test_one_long_queue(dev):
     """1,100 references on 1,000 streams: many rounds of the group's scans and
     several blocks of the flat copy; the last, first and middle streams

@@ -75,6 +75,13 @@ def test_view_counts(codec, n):
     both_compacted(codec, host_state(dc.count_case(n)))
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 65])
+def test_runs_of_empty_views(codec, n):
+    case = dc.empty_runs_case(n)
+    new = both_compacted(codec, host_state(case))
+    assert new["nentries"] == sum(len(calls[0]) for _, calls in case.tables)
+
+
 def empties(counts):
     return dc.Case("records", [(4096, [[dc.raw_insert(b"", b"")] * L]) for L in counts])
 
