@@ -213,17 +213,41 @@ static void put_dec_state(void) {
   put_table(&dec->ctx);
 }
 
-static void dec_section(void) {
-  int64_t sid = (int64_t)number();
-  size_t len, at = 0;
-  uint8_t *src = hexbytes(&len);
+/* Stream contexts that a `hold` step left blocked, with the bytes the library
+ * has not read yet, until a `resume` or `cancel` step names their stream. */
+typedef struct held {
+  int64_t sid;
   nghttp3_qpack_stream_context *sctx;
+  uint8_t *tail;
+  size_t len;
+  struct held *next;
+} held;
+static held *kept;
+
+static held **find_held(int64_t sid) {
+  held **pp;
+  for (pp = &kept; *pp && (*pp)->sid != sid; pp = &(*pp)->next) {
+  }
+  return pp;
+}
+
+static void drop_held(held **pp) {
+  held *h = *pp;
+  *pp = h->next;
+  nghttp3_qpack_stream_context_del(h->sctx);
+  free(h->tail);
+  free(h);
+}
+
+/* read_request with fin set until the section ends, fails or blocks; prints
+ * the step's line (with `left`, the unread bytes, when with_left).  -> the
+ * bytes read when the library reports BLOCKED, -1 otherwise. */
+static ptrdiff_t read_section(const char *op, int64_t sid, nghttp3_qpack_stream_context *sctx,
+                              const uint8_t *src, size_t len, int with_left) {
+  size_t at = 0;
   nghttp3_ssize total = 0;
   int blocked = 0, first = 1;
-  if (nghttp3_qpack_stream_context_new(&sctx, sid, mem) != 0) {
-    die("out of memory");
-  }
-  printf("{\"op\":\"section\",\"sid\":%" PRId64 ",\"fields\":[", sid);
+  printf("{\"op\":\"%s\",\"sid\":%" PRId64 ",\"fields\":[", op, sid);
   for (;;) {
     nghttp3_qpack_nv nv;
     uint8_t flags = 0;
@@ -258,10 +282,89 @@ static void dec_section(void) {
   }
   printf("],\"rv\":%td,\"blocked\":%d,\"ricnt\":%" PRIu64 ",\"base\":%" PRIu64 ",", (ptrdiff_t)total, blocked,
          nghttp3_qpack_stream_context_get_ricnt2(sctx), sctx->base);
+  if (with_left) {
+    printf("\"left\":%zu,", len - at);
+  }
   put_dec_state();
   printf("}\n");
-  nghttp3_qpack_stream_context_del(sctx);
+  return blocked ? (ptrdiff_t)at : -1;
+}
+
+static void dec_section(int hold) {
+  int64_t sid = (int64_t)number();
+  size_t len;
+  uint8_t *src = hexbytes(&len);
+  nghttp3_qpack_stream_context *sctx;
+  ptrdiff_t at;
+  if (hold && *find_held(sid)) {
+    die("the stream is held already");
+  }
+  if (nghttp3_qpack_stream_context_new(&sctx, sid, mem) != 0) {
+    die("out of memory");
+  }
+  at = read_section(hold ? "hold" : "section", sid, sctx, src, len, hold);
+  if (hold && at >= 0) { /* blocked: the context and the unread tail are kept */
+    held *h = calloc(1, sizeof(*h));
+    if (!h) {
+      die("out of memory");
+    }
+    h->sid = sid;
+    h->sctx = sctx;
+    h->len = len - (size_t)at;
+    h->tail = malloc(h->len + 1);
+    if (!h->tail) {
+      die("out of memory");
+    }
+    memcpy(h->tail, src + at, h->len);
+    h->next = kept;
+    kept = h;
+  } else {
+    nghttp3_qpack_stream_context_del(sctx);
+  }
   free(src);
+}
+
+static void dec_resume(void) {
+  int64_t sid = (int64_t)number();
+  held **pp = find_held(sid), *h = *pp;
+  ptrdiff_t at;
+  if (!h) {
+    die("resume of a stream that is not held");
+  }
+  at = read_section("resume", sid, h->sctx, h->tail, h->len, 1);
+  if (at >= 0) { /* still blocked */
+    memmove(h->tail, h->tail + at, h->len - (size_t)at);
+    h->len -= (size_t)at;
+  } else {
+    drop_held(pp);
+  }
+}
+
+static void dec_dwrite(void) {
+  size_t n = nghttp3_qpack_decoder_get_decoder_streamlen2(dec);
+  uint8_t *p = malloc(n ? n : 1);
+  nghttp3_buf b;
+  if (!p) {
+    die("out of memory");
+  }
+  nghttp3_buf_wrap_init(&b, p, n);
+  nghttp3_qpack_decoder_write_decoder(dec, &b);
+  printf("{\"op\":\"dwrite\",\"ds\":");
+  put_hex(b.pos, nghttp3_buf_len(&b));
+  printf(",\"written_icnt\":%" PRIu64 ",", dec->written_icnt);
+  put_dec_state();
+  printf("}\n");
+  free(p);
+}
+
+static void del_both(void) {
+  while (kept) {
+    drop_held(&kept);
+  }
+  nghttp3_qpack_encoder_del(enc);
+  nghttp3_qpack_decoder_del(dec);
+  enc = NULL;
+  dec = NULL;
 }
 
 int main(int argc, char **argv) {
@@ -278,9 +381,7 @@ int main(int argc, char **argv) {
       hard_max = (size_t)number();
       max_blocked = (size_t)number();
       strat = number();
-      nghttp3_qpack_encoder_del(enc);
-      nghttp3_qpack_decoder_del(dec);
-      dec = NULL;
+      del_both();
       if (nghttp3_qpack_encoder_new(&enc, hard_max, mem) != 0) {
         die("out of memory");
       }
@@ -294,9 +395,7 @@ int main(int argc, char **argv) {
       token();
       hard_max = (size_t)number();
       max_blocked = (size_t)number();
-      nghttp3_qpack_encoder_del(enc);
-      nghttp3_qpack_decoder_del(dec);
-      enc = NULL;
+      del_both();
       if (nghttp3_qpack_decoder_new(&dec, hard_max, max_blocked, mem) != 0) {
         die("out of memory");
       }
@@ -334,14 +433,44 @@ int main(int argc, char **argv) {
       put_dec_state();
       printf("}\n");
       free(src);
+    } else if (strcmp(t, "dstream") == 0 && enc) {
+      size_t len;
+      uint8_t *src = hexbytes(&len);
+      nghttp3_ssize n = nghttp3_qpack_encoder_read_decoder(enc, src, len);
+      printf("{\"op\":\"dstream\",\"rv\":%td,\"dlen\":%zu,\"bad\":%d,", (ptrdiff_t)n,
+             enc->uninterrupted_decoderlen, enc->ctx.bad ? 1 : 0);
+      put_enc_state();
+      printf("}\n");
+      free(src);
+    } else if (strcmp(t, "cancel") == 0 && enc) {
+      int64_t sid = (int64_t)number();
+      nghttp3_qpack_encoder_cancel_stream(enc, sid);
+      printf("{\"op\":\"cancel\",\"sid\":%" PRId64 ",", sid);
+      put_enc_state();
+      printf("}\n");
     } else if (strcmp(t, "section") == 0 && dec) {
-      dec_section();
+      dec_section(0);
+    } else if (strcmp(t, "hold") == 0 && dec) {
+      dec_section(1);
+    } else if (strcmp(t, "resume") == 0 && dec) {
+      dec_resume();
+    } else if (strcmp(t, "cancel") == 0 && dec) {
+      int64_t sid = (int64_t)number();
+      int rv = nghttp3_qpack_decoder_cancel_stream(dec, sid);
+      held **pp = find_held(sid);
+      if (*pp) {
+        drop_held(pp);
+      }
+      printf("{\"op\":\"cancel\",\"sid\":%" PRId64 ",\"rv\":%d,", sid, rv);
+      put_dec_state();
+      printf("}\n");
+    } else if (strcmp(t, "dwrite") == 0 && dec) {
+      dec_dwrite();
     } else {
       die("unknown step");
     }
   }
-  nghttp3_qpack_encoder_del(enc);
-  nghttp3_qpack_decoder_del(dec);
+  del_both();
   fclose(in);
   return 0;
 }

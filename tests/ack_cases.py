@@ -10,9 +10,13 @@ Restated here, from the reference's lines (not from csrc/qh_ack_core.h):
 * nghttp3_qpack_decoder_write_section_ack :3813-3839, decoder_cancel_stream
   :3889-3913 and write_decoder :3859-3887 in the batch's fixed order
   (write_decoder_model).
-Section Acknowledgment is also judged by the reference library itself: the
-transcripts under tests/golden/ref_replay/ carry a state digest after every
-ack step, which run_case holds against the state read back from `enc`."""
+Both ends are also judged by the reference library itself, through the
+transcripts under tests/golden/ref_replay/: a state digest after every ack
+step, which run_case holds against the state read back from `enc`; the ds-*
+cases (real encodes, then decoder-stream bytes through the stream parser); the
+writer cases dw-items and, in blocked_cases.py, dw-wire-*; and the closure
+cases loop-17x5*, which record both ends of three rounds.  The restatements
+stay as the second opinion for what a test builds synthetically."""
 import numpy as np
 
 import enc_cases as ec
@@ -274,17 +278,59 @@ class AckModel(ec.Model):
                                case.strat_none) for t in range(case.n)]
 
 
-def run_case(case, dev=None):
+def boundary(data):
+    """The end of the last whole instruction of a decoder stream without errors."""
+    at = 0
+    while at < len(data):
+        r = read_varint(data, at, 7 if data[at] & 0x80 else 6)
+        if r is None or r == "overflow":
+            break
+        at = r[1]
+    return at
+
+
+def check_dstream_step(case, t, s, data, held, status, used, rvrec, direct=0):
+    """One connection's ("dstream", ...) step against the reference's
+    transcript step s: the verdict, the BAD flag and the running length.  The
+    reference reads all it is fed (it buffers a cut instruction: its return
+    value is the length fed, and its length count includes the buffered head);
+    this project's call stops at the last instruction boundary and is handed
+    the tail again (held[t], kept here for the next step).  direct: the bytes
+    this connection was given for steps that the reference took as direct
+    calls (("cancel", ...)), which only this project's count includes."""
+    bad = bool(int(rvrec["flags"]) & qpack.ENC_REFS_BAD)
+    dlen = int(rvrec["dlen"]) - direct
+    assert bad == bool(s["bad"]), (case, t, s)
+    if s["rv"] >= 0:
+        assert (status, s["rv"]) == (0, len(data) - len(held[t])), (case, t, s, status)
+        assert used == boundary(data), (case, t, used)
+        held[t] = data[used:]
+        assert dlen + len(held[t]) == s["dlen"], (case, t, s, dlen)
+    else:
+        assert (status, s["rv"] in (DS_ERR, FATAL)) == (s["rv"], True), (case, t, s, status)
+        if not bad:  # the length rule: nothing read, the whole length counted on both sides
+            assert used == 0 and not held[t] and dlen == s["dlen"], (case, t, s, dlen)
+        held[t] = b""
+
+
+def run_case(case, dev=None, n=None):
     """enc_cases.run_case with the acknowledgement calls in the caller's
     place: the sets are made with refs=True, every encode passes stream ids
     (the library's sec_flags must be the model's, the reference queues after
     it the model's streams) and every ack step is delivered as decoder-stream
     bytes through read_decoder, after which the state read back from the
     records is held against the reference library's transcript digest.
+    A ("dstream", [bytes per connection]) step goes through read_decoder as it
+    is; status, consumed, the running length, the BAD flag and the state
+    digest are held against the transcript's dstream step, then the model.
+    n: the case's first n connections only.
     -> (the model, the number of acknowledgements delivered)."""
+    if n is not None:
+        case = first_conns(case, n)
     model = AckModel(case)
-    cur = rc.Cursor(case.ref, case.n)
+    cur = rc.Cursor(case.ref, case.n, prefix=n is not None)
     asked = [None] * case.n
+    held, direct = [b""] * case.n, [0] * case.n
     sets = make_sets(case.hard_max, case.n, case.max_blocked, case.immediate, case.strat_none, dev)
     nacks = 0
     for step in case.steps:
@@ -311,6 +357,33 @@ def run_case(case, dev=None):
                 if last is not None:
                     ec.check_state_digest(case, t, last, *conn_state(sets[0], t))
             ec.check_state(sets[0], model)
+        elif step[0] == "cancel":
+            # the reference's nghttp3_qpack_encoder_cancel_stream called directly; here as bytes
+            streams = [b"" if sid is None else cancel(sid) for sid in step[1]]
+            want = [model.enc[t].read_decoder(x) for t, x in enumerate(streams)]
+            st, co = read_both(sets, dev, streams)
+            assert list(zip(st.tolist(), co.tolist())) == want == [(0, len(x)) for x in streams], (case, st, co)
+            for t, sid in enumerate(step[1]):
+                direct[t] += len(streams[t])
+                if sid is not None:
+                    s = cur.take(t, "cancel")
+                    assert s["sid"] == sid, (case, t, s)
+                    ec.check_state_digest(case, t, s, *conn_state(sets[0], t))
+            ec.check_state(sets[0], model)
+        elif step[0] == "dstream":
+            streams = [bytes(x) for x in step[1]]
+            want = [model.enc[t].read_decoder(x) for t, x in enumerate(streams)]
+            st, co = read_both(sets, dev, streams)
+            rvrec, _ = sets[0].refs_records()
+            for t, data in enumerate(streams):
+                s = cur.take(t, "dstream")
+                check_dstream_step(case, t, s, data, held, int(st[t]), int(co[t]), rvrec[t], direct[t])
+                ec.check_state_digest(case, t, s, *conn_state(sets[0], t))
+            assert list(zip(st.tolist(), co.tolist())) == want, (case, st, co, want)
+            ec.check_state(sets[0], model)
+            q = queues(sets[0])
+            for t in range(case.n):
+                assert by_stream(q[t]) == model.enc[t].streams, (case, t)
         else:
             call = step[1]
             tsel = None if len(step) < 3 or step[2] is None else np.asarray(step[2], np.uint32)
@@ -333,12 +406,33 @@ def run_case(case, dev=None):
                 assert by_stream(q[t]) == model.enc[t].streams, (case, t)
             listed = range(case.n) if tsel is None else [int(x) for x in tsel]
             for p, t in enumerate(listed):
+                if call[p]:
+                    direct[t] = 0  # (an encode resets the count)
                 for _ in call[p]:
                     cur.take(t, "encode")
                     if case.immediate:
                         cur.take(t, "ackall")
-    cur.done()
+    if n is None:
+        cur.done()
+    else:
+        for t in range(case.n):
+            assert cur.at[t] == len(cur.steps(t)), (case, t)
     return model, nacks
+
+
+def first_conns(case, n):
+    """The case's first n connections (its steps name every connection: no tsel)."""
+    steps = []
+    for step in case.steps:
+        if step[0] == "encode":
+            assert len(step) == 4 and step[2] is None
+            steps.append(("encode", step[1][:n], None, step[3][:n]))
+        else:
+            assert step[0] in ("cap", "dstream", "cancel")
+            steps.append((step[0], step[1] if np.ndim(step[1]) == 0 else list(step[1][:n])))
+    hm = case.hard_max if np.ndim(case.hard_max) == 0 else case.hard_max[:n]
+    return ec.Case("%s[:%d]" % (case.name, n), n, hm, case.max_blocked, case.immediate, case.strat_none,
+                   steps=steps, ref=case.ref)
 
 
 def cases_with_acks():
@@ -772,3 +866,535 @@ def blocked_blocks(dev=None):
     assert enc["krcnt"].tolist() == views["insert_count"].tolist() and min(enc["krcnt"]) > 0
     assert not enc["nstreams"].any() and not enc["nblocked"].any()
     assert (enc["pin_min"] == UINT64_MAX).all()
+
+
+# ---- the decoder stream's reader against the reference library ---------------------
+# Cases on real encodes (the reference cannot be handed (sid, max_cnt, min_cnt)
+# triples): every verdict, the running length, the BAD flag and the state after
+# every ("dstream", ...) step are the reference's (tests/golden/ref_replay/ds-*.json).
+
+def new_fields(base, k):
+    """k fields no table holds yet: each is inserted and referred to."""
+    return [(b"x-f", b"%d" % (base + i), 0) for i in range(k)]
+
+
+def ds_case(name, per_conn, dsteps, tail=()):
+    """per_conn[t]: the (stream id, fields) sections of connection t in order,
+    a call each (a stream may come again); then the dstream steps; then `tail`."""
+    n = len(per_conn)
+    steps = [("cap", 4096)]
+    for k in range(max(len(x) for x in per_conn)):
+        steps.append(("encode", [[x[k][1]] if k < len(x) else [] for x in per_conn], None,
+                      [[x[k][0]] if k < len(x) else [] for x in per_conn]))
+    steps += [("dstream", list(d)) for d in dsteps] + list(tail)
+    return ec.Case(name, n, 4096, 100, False, steps=steps)
+
+
+DS_LATTICE_INSERTS = 70  # Insert Count Increments of 62, 63 and 64 are accepted, the larger ones not
+
+
+def ds_lattice():
+    """One connection per lattice value: a stream id at GROW7 with two sections
+    acknowledged once, a stream id at GROW6 with a section cancelled, an
+    Insert Count Increment at GROW6 against DS_LATTICE_INSERTS inserts."""
+    per = [[(v, new_fields(0, 1)), (v, new_fields(1, 1))] for v in GROW7] + \
+        [[(v, new_fields(0, 2))] for v in GROW6] + [[(4, new_fields(0, DS_LATTICE_INSERTS))] for _ in GROW6]
+    streams = [ack(v) for v in GROW7] + [cancel(v) for v in GROW6] + [incr(v) for v in GROW6]
+    return ds_case("ds-lattice", per, [streams])
+
+
+def ds_errors():
+    """error_pair's nine rules on real encodes, then incr(1) to every connection."""
+    one = [(4, new_fields(0, 3))]
+    per = [one, one, one, one,
+           [(8, new_fields(0, 2)), (8, new_fields(2, 1)), (8, new_fields(3, 2))],
+           one, [(4, new_fields(0, 2)), (12, new_fields(2, 1))],
+           [(12, new_fields(0, 1)), (4, new_fields(1, 4))], one]
+    streams = [incr(0), incr(3), incr(4), ack(5), ack(8) * 4, cancel(77), cancel(4),
+               ack(12) + incr(3) + ack(99) + ack(4), b""]
+    return ds_case("ds-errors", per, [streams, [incr(1)] * 9])
+
+
+DS_ERRORS_WANT = [(DS_ERR, 0), (0, 1), (DS_ERR, 0), (DS_ERR, 0), (DS_ERR, 3), (0, 2), (0, 1), (DS_ERR, 2), (0, 0)]
+
+
+def ds_overflow():
+    s = overflow_streams()
+    return ds_case("ds-overflow", [[(4, new_fields(0, 2))]] * len(s), [s, [incr(1)] * len(s)])
+
+
+def real_refs(nstreams, per_stream, first=0, step=4, filler=40):
+    """nstreams x per_stream one-insert sections (stream ids first, first +
+    step, ...; the streams' k-th sections before their k+1-th), then one
+    section of `filler` inserts on the stream behind them: room for increments."""
+    out, k = [], 0
+    for _ in range(per_stream):
+        for i in range(nstreams):
+            out.append((first + step * i, new_fields(k, 1)))
+            k += 1
+    return out + [(first + step * nstreams, new_fields(k, filler))]
+
+
+def ds_partials():
+    """forty()'s stream against real references on six streams (three sections
+    each), cut at every third byte and one byte before its end: the head, then
+    the tail from where `consumed` stopped."""
+    _, stream, ends = forty()
+    cuts = list(range(0, len(stream), 3)) + [len(stream) - 1]
+    heads = [stream[:c] for c in cuts]
+    tails = [stream[max(e for e in ends if e <= c):] for c in cuts]
+    return ds_case("ds-partials", [real_refs(6, 3)] * len(cuts), [heads, tails])
+
+
+DS_FILL = cancel(1000) * 1365  # 4,095 bytes of valid instructions
+
+
+def ds_limit():
+    """4,096 bytes in one call, 4,097 in one call, 4,000 then 97 in two; after
+    the length rule's -403 an incr(1) (-403 again, and no BAD flag: the rule
+    has no `goto fail`), then an encode (which resets the count) and incr(1)."""
+    per = [[(4, new_fields(0, 3))]] * 3
+    assert len(DS_FILL) == 4095
+    first = [DS_FILL + incr(1), DS_FILL + cancel(63), DS_FILL[:4000]]
+    second = [b"", incr(1), DS_FILL[3999:] + incr(1)]
+    again = ("encode", [[new_fields(3, 1)]] * 3, None, [[8]] * 3)
+    return ds_case("ds-limit", per, [first, second], tail=[again, ("dstream", [incr(1)] * 3)])
+
+
+DS_STAGE_LENS = (511, 512, 513, 1025, 513)
+
+
+def ds_stage():
+    """Streams of 511, 512, 513 and 1,025 bytes, and one of 513 whose last
+    instruction is cut, against 19 references on 19 streams (a second 16-lane
+    round of the reference scan): acknowledgements of real sections (one- and
+    two-byte stream ids), increments, cancellations of a real and of unknown
+    streams (one, four and six bytes).  In the streams longer than 512 bytes a
+    cancellation of four or six bytes begins at byte 509."""
+    refs = real_refs(18, 1, first=100)  # stream ids 100..168, the filler on 172
+    streams = []
+    for k, L in enumerate(DS_STAGE_LENS):
+        head = [ack(100 + 4 * i) for i in range(k, 18, 2)] + [incr(1), cancel(172 if k % 2 else 171), incr(2)]
+        parts, at, j = [], 0, 0
+        body = 509 if L >= 513 else L
+        while at < body - 12:
+            x = head[j] if j < len(head) else (cancel(100000 + j), cancel(j % 60 + 1), cancel((1 << 34) + j))[j % 3]
+            parts.append(x)
+            at += len(x)
+            j += 1
+        parts += [cancel(1 + i % 50) for i in range(body - at)]  # one byte each
+        if L >= 513:  # the instruction that straddles byte 512: four bytes in the whole 513, six otherwise
+            parts.append(cancel(100007) if k == 2 else cancel((1 << 34) + 7))
+            assert len(parts[-1]) == (4 if k == 2 else 6)
+            parts += [cancel(2 + i % 50) for i in range(L - 515)]
+        streams.append(b"".join(parts)[:L])
+        assert len(streams[-1]) == L
+    assert [boundary(x) for x in streams] == [511, 512, 513, 1025, 509]
+    # the cut instruction handed in again, whole
+    second = [b"", b"", b"", b"", cancel((1 << 34) + 7)]
+    assert second[4][:4] == streams[4][509:]
+    return ds_case("ds-stage", [refs] * len(DS_STAGE_LENS), [streams, second])
+
+
+def ds_cancel():
+    """nghttp3_qpack_encoder_cancel_stream by itself (the driver's `cancel`):
+    a blocked stream, a stream with two sections, an unknown stream, a stream
+    that is cancelled and then comes back; an increment after each."""
+    per = [[(4, new_fields(0, 2)), (12, new_fields(2, 1))],
+           [(8, new_fields(0, 1)), (8, new_fields(1, 2))],
+           [(4, new_fields(0, 3))],
+           [(4, new_fields(0, 1))]]
+    case = ds_case("ds-cancel", per, [], tail=[
+        ("cancel", [4, 8, 77, 4]), ("dstream", [incr(1)] * 4),
+        ("encode", [[], [], [], [new_fields(1, 1)]], None, [[], [], [], [4]]),
+        ("cancel", [12, None, 4, 4]), ("dstream", [incr(2), incr(2), incr(2), incr(1)])])
+    return case
+
+
+def ds_cases():
+    return [ds_lattice(), ds_errors(), ds_overflow(), ds_partials(), ds_limit(), ds_stage(), ds_cancel()]
+
+
+# ---- the decoder stream's writer against the reference library ----------------------
+# Decoder connections of kind "decoder stream": per table a list of batches
+# (encoder-stream bytes, [(stream id, section bytes)], [cancelled stream ids]).
+# The case file orders a batch as the batch call defines it: the encoder stream,
+# the sections in list order (`hold`, so that a blocked one stays with the
+# library), the cancellations, then `dwrite`.
+
+DW_DUPLICATES = (1 << 14) + 62  # with the one insert before them an increment of 2^14 + 63:
+# 16,447 bytes of encoder stream, under the reference's limit of 128 KiB (NGHTTP3_QPACK_MAX_ENCODERLEN)
+STATIC_ONLY = [(b":method", b"GET", 0), (b":path", b"/", 0)]  # Required Insert Count 0
+
+
+def dw_items():
+    """-> per table its batches.  Six tables (DESIGN 3.11's writer rules):
+    0  sections with Required Insert Count 0 and above 0, the acknowledged
+       stream ids at GROW7; a second batch with nothing new (writes nothing)
+    1  62 inserts, a section held blocked, cancellations at GROW6 (unknown
+       streams); then the held stream and an unknown one cancelled
+    2  63 inserts; then a section with ricnt below written_icnt (the increment
+       is insert_count - written_icnt); then one with ricnt above it and below
+       insert_count (the increment is the remainder)
+    3  64 inserts and, last, a failing section (a relative index behind Base)
+    4  nothing to say; then a section that refers to no dynamic entry
+    5  one insert and DW_DUPLICATES Duplicate instructions
+    Every dwrite stays far below the 2,000 pending bytes of
+    qpack_decoder_dbuf_overflow, which this project does not restate."""
+    def encoder():
+        e = em.Encoder(4096, 100)
+        e.set_capacity(4096)
+        return e
+
+    tables = []
+    e = encoder()
+    es, secs = b"", []
+    for k, sid in enumerate(GROW7):
+        sec, eb, mx, _ = e.encode(sid, new_fields(k, 1) + (STATIC_ONLY if k % 2 else []))
+        assert mx == k + 1
+        es, secs = es + eb, secs + [(sid, sec)]
+    sec, eb, mx, _ = e.encode(2, STATIC_ONLY)
+    assert mx == 0 and not eb
+    tables.append([(es, secs[:5] + [(2, sec)] + secs[5:], []), (b"", [], [])])
+
+    e = encoder()
+    _, es, _, _ = e.encode(4, new_fields(0, 62))
+    held, _, mx, _ = e.encode(8, new_fields(62, 1))
+    assert mx == 63
+    tables.append([(es, [(8, held)], list(GROW6)), (b"", [], [8, 77])])
+
+    e = encoder()
+    _, es, _, _ = e.encode(4, new_fields(0, 63))
+    _, es5, _, _ = e.encode(6, new_fields(63, 5))
+    old, none, mx, _ = e.encode(12, new_fields(9, 1))  # (the tenth entry again)
+    assert mx == 10 and not none
+    s16, es2, mx16, _ = e.encode(16, new_fields(68, 2))
+    _, es4, mx20, _ = e.encode(20, new_fields(70, 4))
+    assert (mx16, mx20) == (70, 74)
+    tables.append([(es, [], []), (es5, [(12, old)], []), (es2 + es4, [(16, s16)], [])])
+
+    e = encoder()
+    _, es, _, _ = e.encode(4, new_fields(0, 64))
+    # Required Insert Count 64 (encoded 65 of 2 * 128 entries), Base 64, then the dynamic entry 64 behind Base
+    failing = qf.put_varint(65, 8) + qf.put_varint(0, 7, 0) + qf.put_varint(64, 6, 0x80)
+    tables.append([(es, [(GROW7[3], failing)], [])])
+
+    e = encoder()
+    sec, eb, _, _ = e.encode(4, STATIC_ONLY)
+    tables.append([(b"", [], []), (eb, [(4, sec)], [])])
+
+    e = encoder()
+    _, es, _, _ = e.encode(4, new_fields(0, 1))
+    tables.append([(es + bytes(DW_DUPLICATES), [], [])])
+    return tables
+
+
+def dw_script(batches):
+    items = []
+    for es, secs, cancels in batches:
+        if es:
+            items.append(("estream", es))
+        items += [("hold", sid, sec) for sid, sec in secs]
+        items += [("cancel", sid) for sid in cancels]
+        items.append(("dwrite",))
+    return rc.dec_script(4096, items)
+
+
+def dw_transcript(name, tables, note):
+    return rc.record(name, "decoder stream", [dw_script(b) for b in tables], note=note)
+
+
+def ds16(b):
+    import hashlib
+    return hashlib.sha256(bytes(b)).hexdigest()[:16]
+
+
+class DecLoop(Loop):
+    """The decoder's half of Loop: `n` tables, host twin and device side."""
+
+    def __init__(self, n, hard_max, dev=None, max_blocked=None):
+        self.n, self.dev, self.sets = n, dev, []
+        self.ts = [DynamicTableSet(hard_max, n, max_blocked=max_blocked)]
+        if dev is not None:
+            self.ts.append(DynamicTableSet(hard_max, n, dev.codec, max_blocked=max_blocked))
+            self.fsd = qpack.FieldSectionDecoder(codec=dev.codec)
+
+    def apply_bytes(self, streams):
+        src, spans = pack_streams(streams)
+        self.apply({"edst": src, "needs": [0, 0, 0, src.size], "estreams": spans})
+
+    def emit_bytes(self, sections, block_view):
+        src, spans = pack_streams(sections)
+        return self.emit({"dst": src, "needs": [0, 0, src.size, 0], "sections": spans}, block_view)
+
+
+def section_verdict(s):
+    """A transcript's section / hold / resume step -> (this project's emit
+    status, Required Insert Count or None where the reference failed)."""
+    if s["rv"] < 0:
+        return s["rv"], None
+    return (qpack.EMIT_BLOCKED if s["blocked"] else 0), s["ricnt"]
+
+
+def run_dw(name, tables, dev=None, ntables=None):
+    """The writer case through read_encoder, emit and write_decoder, a batch
+    of every table per call; table t of ntables is the case's table t mod
+    len(tables).  Every section's status and Required Insert Count, every
+    table's decoder-stream bytes and its written_icnt after every batch are
+    held against the reference's transcript.  -> the streams of every batch."""
+    tr = rc.load(name)
+    n = ntables or len(tables)
+    which = [t % len(tables) for t in range(n)]
+    steps = [tr["conns"][tr["conn_of"][w]] for w in which]
+    at = [2] * n
+    lp = DecLoop(n, 4096, dev)
+    out = []
+
+    def take(t, op):
+        s = steps[t][at[t]]
+        assert s["op"] == op, (name, t, at[t], s, op)
+        at[t] += 1
+        return s
+
+    for b in range(max(len(x) for x in tables)):
+        batch = [tables[w][b] if b < len(tables[w]) else None for w in which]
+        lp.apply_bytes([x[0] if x else b"" for x in batch])
+        for t, x in enumerate(batch):
+            if x and x[0]:
+                s = take(t, "estream")
+                assert s["rv"] == len(x[0]), (name, t, s)
+                assert int(lp.ts[0].views.view(qpack.VIEW_DTYPE)[t]["insert_count"]) == s["insert_count"]
+        secs = [(t, sid, sec) for t, x in enumerate(batch) if x for sid, sec in x[1]]
+        bv = np.array([t for t, _, _ in secs], np.uint32)
+        e = lp.emit_bytes([sec for _, _, sec in secs], bv) if secs else None
+        for i, (t, sid, _) in enumerate(secs):
+            s = take(t, "hold")
+            st, ricnt = section_verdict(s)
+            assert s["sid"] == sid and int(e[0]["status"][i]) == st, (name, t, s, e[0]["status"][i])
+            if ricnt is not None:
+                assert int(e[0]["ricnt"][i]) == ricnt, (name, t, s)
+        cancels = [(sid, t) for t, x in enumerate(batch) if x for sid in x[2]]
+        for sid, t in cancels:
+            assert take(t, "cancel") == {"op": "cancel", "sid": sid, "rv": 0}
+        w, streams = lp.write(e, [sid for _, sid, _ in secs], bv,
+                              cancel=([c[0] for c in cancels], [c[1] for c in cancels]) if cancels else None)
+        written = lp.written()
+        for t, x in enumerate(batch):
+            if x is None:
+                assert streams[t] == b""
+                continue
+            s = take(t, "dwrite")
+            assert (len(streams[t]), ds16(streams[t]), written[t]) == (s["len"], s["d"], s["written_icnt"]), \
+                (name, b, t, streams[t].hex(), written[t], s)
+        out.append(streams)
+    assert at == [len(s) for s in steps]
+    return out
+
+
+# ---- the closure over rounds: both ends recorded from the reference library --------
+
+LOOP_CONNS, LOOP_SECS, LOOP_ROUNDS = 17, 5, 3  # test_three_rounds_on_the_device's shape
+
+
+def loop_sids(rnd):
+    return [4 * (LOOP_SECS * rnd + k) for k in range(LOOP_SECS)]
+
+
+_loop_scripts = {}
+
+
+def loop_scripts():
+    """-> (encoder case files, decoder case files) of ec.pool_sections(11, 17,
+    5) over three rounds, written a round at a time from what the driver
+    itself printed: the encoder's sections and encoder-stream bytes are the
+    decoder's input, and the decoder's `dwrite` bytes the encoder's next
+    `dstream`.  Needs the driver."""
+    if _loop_scripts:
+        return _loop_scripts["enc"], _loop_scripts["dec"]
+    conns = ec.pool_sections(11, nconns=LOOP_CONNS, nsec=LOOP_SECS)
+    enc, dec = [], []
+    for secs in conns:
+        lines, items = ["enc new 4096 16 1", "cap 4096"], []
+        for rnd in range(LOOP_ROUNDS):
+            for sid, fields in zip(loop_sids(rnd), secs):
+                lines.append("encode %d %d" % (sid, len(fields)))
+                lines += ["%d %s %s" % ((rc.REF_NEVER if f[2] & 1 else 0) | (rc.REF_TRY if f[2] & 2 else 0),
+                                        rc.hx(f[0]), rc.hx(f[1])) for f in fields]
+            steps = rc.run_driver("\n".join(lines) + "\n")[-LOOP_SECS:]
+            assert all(s["op"] == "encode" and s["rv"] == 0 for s in steps)
+            es = b"".join(bytes.fromhex(s["es"]) for s in steps)
+            if es:
+                items.append(("estream", es))
+            items += [("hold", s["sid"], bytes.fromhex(s["sec"])) for s in steps]
+            items.append(("dwrite",))
+            ds = rc.run_driver(rc.dec_script(4096, items, max_blocked=16))[-1]["ds"]
+            lines.append("dstream %s" % (ds or "-"))
+        enc.append("\n".join(lines) + "\n")
+        dec.append(rc.dec_script(4096, items, max_blocked=16))
+    _loop_scripts.update(enc=enc, dec=dec)
+    return enc, dec
+
+
+LOOP_NOTE = "ec.pool_sections(11, 17, 5), three rounds; every section, encoder stream and decoder stream in full"
+
+
+def loop_transcript(side):
+    enc, dec = loop_scripts()
+    if side == "enc":
+        return rc.record("loop-17x5-enc", "encoder", enc, full=True, note=LOOP_NOTE)
+    return rc.record("loop-17x5-dec", "decoder stream", dec, full=True, note=LOOP_NOTE)
+
+
+class LoopRef:
+    """The two transcripts of a closure case (NAME-enc, NAME-dec) walked beside
+    a Loop of n connections; connection t is the recorded t mod 17."""
+
+    def __init__(self, name, n):
+        te, td = rc.load(name + "-enc"), rc.load(name + "-dec")
+        self.name, self.n = name, n
+        self.es = [te["conns"][te["conn_of"][t % LOOP_CONNS]] for t in range(n)]
+        self.ds = [td["conns"][td["conn_of"][t % LOOP_CONNS]] for t in range(n)]
+        self.ea, self.da = [2] * n, [2] * n  # (behind "new" and "cap")
+
+    def enc(self, t, op):
+        s = self.es[t][self.ea[t]]
+        assert s["op"] == op, (self.name, t, self.ea[t], s, op)
+        self.ea[t] += 1
+        return s
+
+    def dec(self, t, op):
+        s = self.ds[t][self.da[t]]
+        assert s["op"] == op, (self.name, t, self.da[t], s, op)
+        self.da[t] += 1
+        return s
+
+    def encode(self, lp, r, sids):
+        """Every section's bytes, every connection's encoder stream and its state."""
+        assert (r["status"] == 0).all() and (r["sec_status"] == 0).all()
+        for t in range(self.n):
+            want_es = b""
+            for k in range(LOOP_SECS):
+                s, b = self.enc(t, "encode"), r["sections"][t * LOOP_SECS + k]
+                assert (s["sid"], s["rv"]) == (sids[t][k], 0)
+                assert bytes(r["dst"][int(b["off"]):int(b["off"]) + int(b["len"])]).hex() == s["sec"], (t, k)
+                want_es += bytes.fromhex(s["es"])
+            ec.check_state_digest(self.name, t, s, *conn_state(lp.sets[0], t))
+            o, ln = int(r["estreams"][t]["off"]), int(r["estreams"][t]["len"])
+            assert bytes(r["edst"][o:o + ln]) == want_es, t
+
+    def estream(self, lp, lens):
+        """The reference read lens[t] bytes (none: no step) and holds as many inserts."""
+        icnt = lp.ts[0].views.view(qpack.VIEW_DTYPE)["insert_count"]
+        for t in range(self.n):
+            if lens[t]:
+                s = self.dec(t, "estream")
+                assert (s["rv"], s["insert_count"]) == (lens[t], int(icnt[t])), (t, s, lens[t], icnt[t])
+
+    def sections(self, op, items):
+        """items: (connection, stream id, status, ricnt) in this project's order."""
+        for t, sid, st, ricnt in items:
+            s = self.dec(t, op)
+            want = section_verdict(s)
+            assert s["sid"] == sid and (st, ricnt if want[1] is not None else None) == want, (t, s, st, ricnt)
+
+    def dwrite(self, streams, written):
+        for t in range(self.n):
+            s = self.dec(t, "dwrite")
+            assert streams[t].hex() == s["ds"], (t, streams[t].hex(), s)
+            assert (len(streams[t]), ds16(streams[t]), written[t]) == (s["len"], s["d"], s["written_icnt"])
+
+    def dstream(self, lp, streams, st, co):
+        """What the reference's decoder wrote is what its encoder read (rv:
+        the closure), and the state after it."""
+        rvrec, _ = lp.sets[0].refs_records()
+        for t in range(self.n):
+            s = self.enc(t, "dstream")
+            assert (s["rv"], s["bad"]) == (len(streams[t]), 0), (t, s, streams[t].hex())
+            assert (int(st[t]), int(co[t]), int(rvrec[t]["dlen"])) == (0, s["rv"], s["dlen"]), (t, s)
+            ec.check_state_digest(self.name, t, s, *conn_state(lp.sets[0], t))
+
+    def done(self):
+        assert self.ea == [len(x) for x in self.es] and self.da == [len(x) for x in self.ds]
+
+
+def loop_conns(n):
+    conns17 = ec.pool_sections(11, nconns=LOOP_CONNS, nsec=LOOP_SECS)
+    return [conns17[t % LOOP_CONNS] for t in range(n)]
+
+
+def loop_against_reference(dev=None, n=LOOP_CONNS):
+    """Loop over n connections (connection t is the recorded t mod 17): at
+    every step the section bytes, the encoder-stream bytes, the decoder-stream
+    bytes and the state after reading them are the reference's, and what the
+    reference's decoder wrote is what its encoder was given to read."""
+    conns, ref = loop_conns(n), LoopRef("loop-17x5", n)
+    lp = Loop(n, 4096, 16, dev)
+    bv = np.repeat(np.arange(n, dtype=np.uint32), LOOP_SECS)
+    for rnd in range(LOOP_ROUNDS):
+        sids = [loop_sids(rnd)] * n
+        flat = [s for ids in sids for s in ids]
+        r = lp.encode(conns, sids)
+        ref.encode(lp, r, sids)
+        lp.apply(r)
+        ref.estream(lp, r["estreams"]["len"].tolist())
+        e = lp.emit(r, bv)
+        ref.sections("hold", [(int(bv[i]), flat[i], int(e[0]["status"][i]), int(e[0]["ricnt"][i]))
+                              for i in range(len(flat))])
+        assert not e[0]["status"].any()
+        w, streams = lp.write(e, flat, bv)
+        ref.dwrite(streams, lp.written())
+        st, co = lp.read(streams)
+        ref.dstream(lp, streams, st, co)
+    ref.done()
+    enc = lp.sets[0].enc_records()
+    assert not enc["nstreams"].any() and enc["krcnt"].min() > 0
+
+
+_halves_scripts = {}
+
+
+def halves_scripts():
+    """loop_scripts with every round's encoder stream fed to the decoder in
+    two halves (the first may end inside an instruction, which the reference
+    buffers): estream, the five sections (`hold`), dwrite, the encoder's
+    dstream; estream, the held sections resumed in (ricnt, arrival) order
+    (this project's release order, which stays restated), dwrite, dstream."""
+    if _halves_scripts:
+        return _halves_scripts["enc"], _halves_scripts["dec"]
+    enc, dec = [], []
+    for secs in loop_conns(LOOP_CONNS):
+        lines, items = ["enc new 4096 16 1", "cap 4096"], []
+        script = lambda: rc.dec_script(4096, items, max_blocked=16)
+        for rnd in range(LOOP_ROUNDS):
+            for sid, fields in zip(loop_sids(rnd), secs):
+                lines.append("encode %d %d" % (sid, len(fields)))
+                lines += ["%d %s %s" % ((rc.REF_NEVER if f[2] & 1 else 0) | (rc.REF_TRY if f[2] & 2 else 0),
+                                        rc.hx(f[0]), rc.hx(f[1])) for f in fields]
+            steps = rc.run_driver("\n".join(lines) + "\n")[-LOOP_SECS:]
+            es = b"".join(bytes.fromhex(s["es"]) for s in steps)
+            if len(es) // 2:
+                items.append(("estream", es[:len(es) // 2]))
+            items += [("hold", s["sid"], bytes.fromhex(s["sec"])) for s in steps]
+            items.append(("dwrite",))
+            out = rc.run_driver(script())
+            lines.append("dstream %s" % (out[-1]["ds"] or "-"))
+            holds = out[-1 - LOOP_SECS:-1]
+            assert [h["op"] for h in holds] == ["hold"] * LOOP_SECS
+            if len(es) - len(es) // 2:
+                items.append(("estream", es[len(es) // 2:]))
+            items += [("resume", h["sid"]) for _, _, h in
+                      sorted((h["ricnt"], k, h) for k, h in enumerate(holds) if h["blocked"])]
+            items.append(("dwrite",))
+            lines.append("dstream %s" % (rc.run_driver(script())[-1]["ds"] or "-"))
+        enc.append("\n".join(lines) + "\n")
+        dec.append(script())
+    _halves_scripts.update(enc=enc, dec=dec)
+    return enc, dec
+
+
+def halves_transcript(side):
+    enc, dec = halves_scripts()
+    note = LOOP_NOTE + "; the encoder streams arrive in two halves"
+    if side == "enc":
+        return rc.record("loop-17x5-halves-enc", "encoder", enc, full=True, note=note)
+    return rc.record("loop-17x5-halves-dec", "decoder stream", dec, full=True, note=note)

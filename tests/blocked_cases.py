@@ -266,13 +266,76 @@ class TooMany(Exception):
         self.record = record
 
 
-def run_wire(data, recs, max_blocked, dev=None, copies=1):
+class WireRef:
+    """run_wire's steps as the reference library's: without a name it collects
+    the decoder connection's case-file items (`hold` for a request record,
+    `resume` per released section in the order this project releases,
+    `dwrite` after every record); with a transcript's name it holds every
+    step against it: the insert count, a section's status, Required Insert
+    Count and field digest (blocked, emitted at once or released), and every
+    connection's decoder-stream bytes and written_icnt."""
+
+    def __init__(self, name=None):
+        import ref_cases as rc
+        self.rc, self.items, self.at = rc, [], 2
+        self.steps = None if name is None else rc.load(name)["conns"][0]
+
+    def take(self, op):
+        s = self.steps[self.at]
+        assert s["op"] == op, (self.at, s, op)
+        self.at += 1
+        return s
+
+    def estream(self, data, insert_counts):
+        if self.steps is None:
+            self.items.append(("estream", bytes(data)))
+            return
+        s = self.take("estream")
+        assert s["rv"] == len(data) and set(insert_counts) == {s["insert_count"]}, (s, insert_counts)
+
+    def section(self, op, sid, data, status, ricnt, text):
+        """A request record (`hold`) or a released section (`resume`) of connection 0."""
+        if self.steps is None:
+            self.items.append((op, int(sid), bytes(data)) if op == "hold" else (op, int(sid)))
+            return
+        s = self.take(op)
+        assert s["sid"] == sid and ac.section_verdict(s) == (status, ricnt), (s, sid, status, ricnt)
+        if status == 0:
+            fields = [tuple(line.split(b"\t")) for line in text.split(b"\n") if line]
+            want = self.rc.fields_digest([(k, v, qpack.lookup_token(k), 0) for k, v in fields])
+            assert (s["n"], s["d"], s["left"]) == (want["n"], want["sha256"][:16], 0), (s, fields)
+
+    def dwrite(self, streams, written):
+        if self.steps is None:
+            self.items.append(("dwrite",))
+            return
+        s = self.take("dwrite")
+        assert len(set(streams)) == 1 and set(written) == {s["written_icnt"]}, (s, written)
+        assert (len(streams[0]), ac.ds16(streams[0])) == (s["len"], s["d"]), (s, streams[0].hex())
+
+    def done(self):
+        assert self.steps is None or self.at == len(self.steps)
+
+
+def wire_script(behind, max_blocked=100):
+    """The case file of dw-wire-<behind>: the corpus connection with its
+    encoder-stream records delayed, as the host twin's run_wire steps through
+    it.  A dwrite follows every record, so none comes near the 2,000 pending
+    bytes of qpack_decoder_dbuf_overflow, which this project does not restate."""
+    data, recs = corpus()
+    ref = WireRef()
+    run_wire(data, delayed(recs, behind), max_blocked, ref=ref)
+    return ref.rc.dec_script(256, ref.items, max_blocked=max_blocked)
+
+
+def run_wire(data, recs, max_blocked, dev=None, copies=1, ref=None):
     """The records through apply -> release -> sections -> emit (released
     blocks) and sections -> emit -> push (request records) for `copies`
     connections that all get the same bytes; on the host, or with dev on the
     device.  -> (the QIF text of connection 0, pushes, largest depth); every
     connection's text is asserted equal.  Raises TooMany at the record whose
-    push says -401."""
+    push says -401.  With ref (a WireRef) the decoder stream is written after
+    every record and every step goes to ref."""
     n = copies
     ts = DynamicTableSet(256, n, None if dev is None else dev.codec, max_blocked=max_blocked)
     fsd = None if dev is None else qpack.FieldSectionDecoder(codec=dev.codec)
@@ -301,9 +364,31 @@ def run_wire(data, recs, max_blocked, dev=None, copies=1):
              "out_blocks": de["out_blocks"].cpu().numpy()[:nb].reshape(-1).view(qpack.SPAN_IN_DTYPE)}
         return e, de
 
-    def write(e, p, t):
+    def block_text(e, p):
         ob = e["out_blocks"][p]
-        text[t] += bytes(e["out"][int(ob["off"]):int(ob["off"]) + int(ob["len"])])
+        return bytes(e["out"][int(ob["off"]):int(ob["off"]) + int(ob["len"])])
+
+    def write(e, p, t):
+        text[t] += block_text(e, p)
+
+    def dwrite(raw, sids, view):
+        """write_decoder over the record's blocks -> ref."""
+        if ref is None:
+            return
+        raw = raw if raw is not None else {"status": None, "ricnt": None}
+        if dev is None:
+            w = ts.write_decoder(raw, np.zeros(0, np.uint64) if sids is None else sids,
+                                 np.zeros(0, np.uint32) if view is None else view)
+            dst, spans, written = w["dst"], w["dstreams"], ts.written_icnt.view(np.uint64)
+        else:
+            w = ts.write_decoder_dev(raw, sids, view)
+            dst, spans = w["dst"].cpu().numpy(), w["dstreams"].cpu().numpy().view(qpack.SPAN_IN_DTYPE)
+            written = ts.written_icnt.cpu().numpy().view(np.uint64)
+        ref.dwrite([bytes(dst[int(x["off"]):int(x["off"]) + int(x["len"])]) for x in spans], written.tolist())
+
+    def insert_counts():
+        v = ts.views if dev is None else ts.views.cpu().numpy()
+        return v.view(qpack.VIEW_DTYPE)["insert_count"].tolist()
 
     for j, (sid, off, ln) in enumerate(recs):
         if sid == 0:
@@ -315,8 +400,11 @@ def run_wire(data, recs, max_blocked, dev=None, copies=1):
                 st, co = ts.read_encoder_dev(d_src, dev.spans(streams))
                 st, co = st.cpu().numpy(), co.cpu().numpy()
             assert not st.any() and (co == ln).all()
+            if ref is not None:
+                ref.estream(data[off:off + ln], insert_counts())
             rel = ts.release_blocked() if dev is None else ts.release_blocked_dev()
             if rel["nreleased"] == 0:
+                dwrite(None, None, None)
                 continue
             pend = ts.pend
             e, raw = emit(pend[:ts.npend] if dev is None else None, pend, rel["blocks"], rel["view"])
@@ -326,6 +414,12 @@ def run_wire(data, recs, max_blocked, dev=None, copies=1):
             view = rel["view"] if dev is None else rel["view"].cpu().numpy()
             for p, t in enumerate(view):
                 write(e, p, int(t))
+                if ref is not None and t == 0:
+                    rsid = rel["sid"] if dev is None else rel["sid"].cpu().numpy()
+                    ref.section("resume", int(rsid[p]), None, int(st[p]), int(e["ricnt"][p]), block_text(e, p))
+            if ref is not None:
+                stt = st if dev is None else dev.t(st)
+                dwrite({"status": stt, "ricnt": raw["ricnt"]}, rel["sid"], rel["view"])
             continue
         blocks = np.zeros(n, qpack.SPAN_IN_DTYPE)
         blocks["off"], blocks["len"] = off, ln
@@ -342,6 +436,12 @@ def run_wire(data, recs, max_blocked, dev=None, copies=1):
         assert (v == v[0]).all()
         if v[0] == TOO_MANY:
             raise TooMany(j)
+        if ref is not None:
+            ref.section("hold", sid, data[off:off + ln], int(v[0]), int(e["ricnt"][0]), block_text(e, 0))
+            if dev is None:
+                dwrite(raw, sids, view)
+            else:
+                dwrite(raw, dev.t(sids, np.int64), dev.t(view, np.int32))
         if v[0] == BLOCKED:
             pushes += 1
             depth = max(depth, int(ts.blocked_records()[0]["n"].max()))
@@ -351,6 +451,8 @@ def run_wire(data, recs, max_blocked, dev=None, copies=1):
             write(e, t, t)
     assert not ts.blocked_records()[0]["n"].any()
     assert all(t == text[0] for t in text)
+    if ref is not None:
+        ref.done()
     return bytes(text[0]), pushes, depth
 
 
@@ -632,3 +734,150 @@ def delayed_loop(dev=None, nconns=17, nsec=5, rounds=3, max_blocked=16):
         enc, penc = lp.sets[0].enc_records(), plain.sets[0].enc_records()
         assert not enc["nstreams"].any() and enc["krcnt"].tolist() == penc["krcnt"].tolist()
     return pushes, inside
+
+
+# ---- a released block's Required Insert Count: kept (the reference) or reconstructed again ----
+
+KEPT_RICNT, KEPT_SID = 20, 4
+
+
+def kept_ricnt_items():
+    """-> (first encoder stream, the section, second encoder stream).  One
+    table of hard maximum 4096 (128 entries at most, Required Insert Counts
+    encoded modulo 256): ten inserts; a section that names Required Insert
+    Count 20 and refers to static entries only; then 140 Duplicates, so that
+    with 150 inserts the encoded value 21 reconstructs to 276 instead of 20.
+    Only a non-conformant encoder can get here (RFC 9204 4.5.1.1: the Required
+    Insert Count of a section without dynamic references is 0, and one that
+    has them pins their entries, so at most 127 inserts can follow it)."""
+    import enc_model as em
+    e = em.Encoder(4096, 100)
+    e.set_capacity(4096)
+    _, es1, _, _ = e.encode(0, ac.new_fields(0, 10))
+    section = qf.put_varint(KEPT_RICNT + 1, 8) + qf.put_varint(0, 7, 0) + bytes([0xC0 | 17, 0xC0 | 1])
+    return es1, section, bytes(140)
+
+
+def kept_ricnt_script():
+    import ref_cases as rc
+    es1, section, es2 = kept_ricnt_items()
+    return rc.dec_script(4096, [("estream", es1), ("hold", KEPT_SID, section), ("estream", es2),
+                                ("resume", KEPT_SID), ("dwrite",)])
+
+
+def kept_ricnt(dev=None):
+    """The case through emit, push, read_encoder, release and emit again.
+    -> (the transcript's steps, the released block's status, the decoder
+    stream written for it)."""
+    import ref_cases as rc
+    tr = rc.load("blk-kept-ricnt")
+    steps = {s["op"]: s for s in tr["conns"][0]}
+    es1, section, es2 = kept_ricnt_items()
+    lp = ac.DecLoop(1, 4096, dev, max_blocked=16)
+    lp.apply_bytes([es1])
+    src, spans = ac.pack_streams([section])
+    sid, bv = np.array([KEPT_SID], np.uint64), np.array([0], np.uint32)
+    e = lp.emit({"dst": src, "needs": [0, 0, src.size, 0], "sections": spans}, bv)
+    h = steps["hold"]
+    assert (int(e[0]["status"][0]), int(e[0]["ricnt"][0])) == (BLOCKED, h["ricnt"]) and h["blocked"] == 1
+    assert h["left"] == len(section) - 2  # (the reference has read the prefix)
+    v = lp.ts[0].push_blocked(src, spans, sid, bv, e[0])["verdict"]
+    assert v.tolist() == [BLOCKED]
+    if dev is not None:
+        dv = lp.ts[1].push_blocked_dev(dev.t(src), dev.spans(spans), dev.t(sid, np.int64),
+                                       dev.t(bv, np.int32), e[1])["verdict"]
+        assert dv.cpu().numpy().tolist() == [BLOCKED]
+    lp.apply_bytes([es2])
+    rel = lp.ts[0].release_blocked()
+    assert (rel["sid"].tolist(), rel["ricnt"].tolist()) == ([KEPT_SID], [KEPT_RICNT])
+    ts = lp.ts[0]
+    e2 = lp.emit({"dst": ts.pend, "needs": [0, 0, ts.npend, 0], "sections": rel["blocks"]}, rel["view"])
+    st = DynamicTableSet.released_status(e2[0], rel)
+    if dev is not None:
+        drel = lp.ts[1].release_blocked_dev()
+        for k in ("blocks", "sid", "view", "ricnt", "start"):
+            assert drel[k].cpu().numpy().tobytes() == rel[k].tobytes(), k
+        assert DynamicTableSet.released_status(e2[1], drel).cpu().numpy().tolist() == st.tolist()
+    e2[0]["status"][:1] = st
+    if dev is not None:
+        e2[1]["status"][:1] = dev.t(st)
+    _, streams = lp.write(e2, rel["sid"], rel["view"])
+    return steps, st.tolist(), streams[0]
+
+
+def delayed_loop_against_reference(dev=None, n=17):
+    """delayed_loop's steps over n connections (connection t is the recorded t
+    mod 17) beside the reference's two transcripts of them
+    (loop-17x5-halves-enc / -dec): the section bytes, the encoder-stream
+    bytes, what is blocked and with which Required Insert Count, both
+    decoder streams of a round and the encoder's state after reading each.
+    -> the number of sections that were queued."""
+    conns, ref = ac.loop_conns(n), ac.LoopRef("loop-17x5-halves", n)
+    lp = ac.Loop(n, 4096, 16, dev)
+    lp.ts = [DynamicTableSet(4096, n, max_blocked=16)]
+    if dev is not None:
+        lp.ts.append(DynamicTableSet(4096, n, dev.codec, max_blocked=16))
+    bv = np.repeat(np.arange(n, dtype=np.uint32), ac.LOOP_SECS)
+    pushes = 0
+
+    def apply(src, streams):
+        st, co = lp.ts[0].read_encoder(src, streams)
+        assert not st.any()
+        if dev is not None:
+            dst, dco = lp.ts[1].read_encoder_dev(dev.t(src), dev.spans(streams))
+            dev.codec.sync()
+            assert not dst.cpu().numpy().any() and dco.cpu().numpy().tolist() == co.tolist()
+            assert lp.ts[1].views.cpu().numpy().tobytes() == lp.ts[0].views.tobytes()
+        return co
+
+    for rnd in range(ac.LOOP_ROUNDS):
+        sids = [ac.loop_sids(rnd)] * n
+        flat = np.array([s for ids in sids for s in ids], np.uint64)
+        r = lp.encode(conns, sids)
+        ref.encode(lp, r, sids)
+        src = r["edst"][:max(r["needs"][3], 1)]
+        half = r["estreams"].copy()
+        half["len"] = r["estreams"]["len"] // 2
+        co = apply(src, half)
+        ref.estream(lp, half["len"].tolist())
+        e = lp.emit(r, bv)
+        data, blocks = np.frombuffer(bytes(r["dst"][:r["needs"][2]]), np.uint8), r["sections"]
+        v = lp.ts[0].push_blocked(data, blocks, flat, bv, e[0])["verdict"]
+        if dev is not None:
+            dv = lp.ts[1].push_blocked_dev(dev.t(data), dev.spans(blocks), dev.t(flat, np.int64),
+                                           dev.t(bv, np.int32), e[1])["verdict"]
+            assert dv.cpu().numpy().tobytes() == v.tobytes()
+        assert (v == e[0]["status"]).all()
+        pushes += int((v == BLOCKED).sum())
+        ref.sections("hold", [(int(bv[i]), int(flat[i]), int(v[i]), int(e[0]["ricnt"][i]))
+                              for i in range(flat.size)])
+        _, streams = lp.write(e, flat, bv)
+        ref.dwrite(streams, lp.written())
+        st, cod = lp.read(streams)
+        ref.dstream(lp, streams, st, cod)
+        rest = r["estreams"].copy()
+        rest["off"] = r["estreams"]["off"] + co
+        rest["len"] = r["estreams"]["len"] - co
+        assert apply(src, rest).tolist() == rest["len"].tolist()
+        ref.estream(lp, (r["estreams"]["len"] - half["len"]).tolist())
+        rel = lp.ts[0].release_blocked()
+        if dev is not None:
+            drel = lp.ts[1].release_blocked_dev()
+            for k in ("blocks", "sid", "view", "ricnt", "start"):
+                assert drel[k].cpu().numpy().tobytes() == rel[k].tobytes(), k
+        assert not lp.ts[0].blocked_records()[0]["n"].any()
+        e2 = None
+        if rel["nreleased"]:
+            ts = lp.ts[0]
+            e2 = lp.emit({"dst": ts.pend, "needs": [0, 0, ts.npend, 0], "sections": rel["blocks"]}, rel["view"])
+            st2 = DynamicTableSet.released_status(e2[0], rel)
+            assert not st2.any()
+            ref.sections("resume", [(int(rel["view"][i]), int(rel["sid"][i]), int(st2[i]), int(e2[0]["ricnt"][i]))
+                                    for i in range(rel["nreleased"])])
+        _, streams = lp.write(e2, rel["sid"], rel["view"])
+        ref.dwrite(streams, lp.written())
+        st, cod = lp.read(streams)
+        ref.dstream(lp, streams, st, cod)
+        assert not lp.sets[0].enc_records()["nstreams"].any()
+    ref.done()
+    return pushes

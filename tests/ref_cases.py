@@ -75,6 +75,10 @@ def enc_script(case):
     shows in the transcript."""
     import enc_cases as ec
     model = ec.Model(case)
+    if any(step[0] in ("dstream", "cancel") for step in case.steps):
+        import ack_cases as ac
+        model = ac.AckModel(case)
+    held = [b""] * case.n
     hm = np.broadcast_to(case.hard_max, (case.n,))
     lines = [["enc new %d %d %d" % (int(hm[t]), case.max_blocked, 0 if case.strat_none else 1)]
              for t in range(case.n)]
@@ -91,6 +95,14 @@ def enc_script(case):
             for t, sids in enumerate(model.ack_ids(step[1])):
                 lines[t] += ["ack %d" % sid for sid in sids]
             model.ack(step[1])
+        elif step[0] == "dstream":
+            for t, data in enumerate(step[1]):
+                lines[t].append("dstream %s" % hx(dstream_feed(model.enc[t], held, t, data)))
+        elif step[0] == "cancel":  # nghttp3_qpack_encoder_cancel_stream called directly (None: not this connection)
+            for t, sid in enumerate(step[1]):
+                if sid is not None:
+                    lines[t].append("cancel %d" % sid)
+                    model.enc[t].cancel(sid)
         else:
             call = step[1]
             tsel = None if len(step) < 3 or step[2] is None else step[2]
@@ -108,9 +120,27 @@ def enc_script(case):
     return ["\n".join(l) + "\n" for l in lines]
 
 
+def dstream_feed(enc, held, t, data):
+    """What the reference is fed of a ("dstream", ...) step's bytes for
+    connection t (dtset_feeds, for the decoder stream): it buffers a partial
+    instruction where this project's call stops before it and is handed the
+    tail again, so the head it already holds (held[t]) is taken off the front.
+    enc: the connection's ack_cases.AckEncoder, which says where the
+    instruction boundaries are; the verdicts are the reference's."""
+    assert bytes(data[:len(held[t])]) == held[t], (t, held[t], data)
+    fed = bytes(data[len(held[t]):])
+    status, used = enc.read_decoder(bytes(data))
+    if status == 0:
+        held[t] = bytes(data[used:])
+    else:  # (after the length rule nothing was looked at; after an error nothing is read again)
+        assert not held[t]
+    return fed
+
+
 def dec_script(hard_max, items, max_blocked=100):
-    """A decoder connection: items are ("estream", bytes) or ("section", sid,
-    bytes).  nghttp3_qpack_decoder_new leaves the capacity at 0; this
+    """A decoder connection: items are ("estream", bytes), ("section", sid,
+    bytes), ("hold", sid, bytes), ("resume", sid), ("cancel", sid) or
+    ("dwrite",).  nghttp3_qpack_decoder_new leaves the capacity at 0; this
     project's tables start at their hard maximum, as the reference's own
     qpack_decode sets it right after creating the decoder, so the case file
     asks for that first."""
@@ -118,8 +148,13 @@ def dec_script(hard_max, items, max_blocked=100):
     for it in items:
         if it[0] == "estream":
             lines.append("estream %s" % hx(it[1]))
+        elif it[0] in ("section", "hold"):
+            lines.append("%s %d %s" % (it[0], it[1], hx(it[2])))
+        elif it[0] in ("resume", "cancel"):
+            lines.append("%s %d" % (it[0], it[1]))
         else:
-            lines.append("section %d %s" % (it[1], hx(it[2])))
+            assert it == ("dwrite",), it
+            lines.append("dwrite")
     return "\n".join(lines) + "\n"
 
 
@@ -181,7 +216,7 @@ def _fold_encoder(steps, full):
     for i, s in enumerate(steps):
         last = i == len(steps) - 1
         d = {"op": s["op"]}
-        for k in ("sid", "rv"):
+        for k in ("sid", "rv", "dlen", "bad"):
             if k in s:
                 d[k] = s[k]
         if s["op"] == "encode":
@@ -199,15 +234,21 @@ def _fold_encoder(steps, full):
     return out
 
 
-def _fold_decoder(steps):
+def _fold_decoder(steps, full=False):
     out = []
     for s in steps:
-        d = {k: s[k] for k in ("op", "rv", "blocked", "ricnt", "base") if k in s}
+        d = {k: s[k] for k in ("op", "sid", "rv", "blocked", "ricnt", "base", "left", "written_icnt")
+             if k in s and (k != "sid" or s["op"] in ("hold", "resume", "cancel"))}
+        if s["op"] == "dwrite":
+            ds = bytes.fromhex(s["ds"])
+            d["len"], d["d"] = len(ds), hashlib.sha256(ds).hexdigest()[:16]
+            if full:
+                d["ds"] = s["ds"]
         if s["op"] == "estream":
             d.update({k: s[k] for k in ("insert_count", "size", "cap")})
             t = table_digest([(bytes.fromhex(n), bytes.fromhex(v)) for n, v in s["tab"]])
             d["n"], d["d"] = t["n"], t["sha256"][:16]
-        elif s["op"] == "section":
+        elif s["op"] in ("section", "hold", "resume"):
             f = fields_digest([(bytes.fromhex(n), bytes.fromhex(v), tok, nv) for n, v, tok, nv in s["fields"]])
             d["n"], d["d"] = f["n"], f["sha256"][:16]
         out.append(d)
@@ -221,18 +262,23 @@ def record(name, kind, scripts, full=False, note="", copies=False):
         if s not in uniq:
             uniq.append(s)
         conn_of.append(uniq.index(s))
-    conns = [_fold_encoder(run_driver(s), full) if kind == "encoder" else _fold_decoder(run_driver(s))
+    conns = [_fold_encoder(run_driver(s), full) if kind == "encoder" else _fold_decoder(run_driver(s), full)
              for s in uniq]
     return {"case": name, "kind": kind, "note": note, "copies": copies, "conn_of": conn_of, "conns": conns}
 
 
 # On disk a step is a list: the operation's letter, then the values of its
 # keys in this order, trailing absent ones left off.
-LETTER = {"new": "n", "cap": "c", "ack": "a", "ackall": "A", "encode": "e", "estream": "s", "section": "q"}
+LETTER = {"new": "n", "cap": "c", "ack": "a", "ackall": "A", "encode": "e", "estream": "s", "section": "q",
+          "dstream": "d", "cancel": "x", "hold": "h", "resume": "r", "dwrite": "w"}
 KEYS = {"encoder": {"new": (), "cap": ("st",), "ack": ("sid", "rv", "st"), "ackall": ("st",),
-                    "encode": ("sid", "rv", "eslen", "out", "st", "sec", "es")},
+                    "encode": ("sid", "rv", "eslen", "out", "st", "sec", "es"),
+                    "dstream": ("rv", "dlen", "bad", "st"), "cancel": ("sid", "st")},
         "decoder": {"new": (), "cap": ("rv",), "estream": ("rv", "insert_count", "size", "cap", "n", "d"),
-                    "section": ("rv", "blocked", "ricnt", "base", "n", "d")}}
+                    "section": ("rv", "blocked", "ricnt", "base", "n", "d"),
+                    "hold": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
+                    "resume": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
+                    "cancel": ("sid", "rv"), "dwrite": ("len", "d", "written_icnt", "ds")}}
 
 
 def _pack(kind, d):
@@ -405,11 +451,37 @@ def emit_transcript(name):
                        "fields as count and SHA-256 (ref_cases.fields_digest)")
 
 
+def _wire_transcript(behind):
+    import blocked_cases as bc
+    return record("dw-wire-%d" % behind, "decoder stream", [bc.wire_script(behind)], copies=True,
+                  note="the corpus connection, encoder-stream records delayed by %d: hold per request "
+                       "record, resume per released section, dwrite after every record (far below the "
+                       "2,000 pending bytes of qpack_decoder_dbuf_overflow)" % behind)
+
+
+def _kept_ricnt_transcript():
+    import blocked_cases as bc
+    return record("blk-kept-ricnt", "decoder stream", [bc.kept_ricnt_script()],
+                  note="a held section resumed after inserts that move its reconstruction; "
+                       "hold and resume as a section step plus the unread bytes")
+
+
 def registry():
     """-> {transcript name: function that records it (needs the driver)}."""
     reg = {}
     for case in encoder_cases():
         reg[case.ref] = (lambda c=case: encoder_transcript(c))
+    import ack_cases as ac
+    for case in ac.ds_cases():
+        reg[case.ref] = (lambda c=case: encoder_transcript(c))
+    reg["dw-items"] = lambda: ac.dw_transcript(
+        "dw-items", ac.dw_items(), "one connection per table; a dwrite step as length, SHA-256 and written_icnt")
+    for side in ("enc", "dec"):
+        reg["loop-17x5-" + side] = (lambda x=side: ac.loop_transcript(x))
+        reg["loop-17x5-halves-" + side] = (lambda x=side: ac.halves_transcript(x))
+    for k in (1, 2):
+        reg["dw-wire-%d" % k] = (lambda x=k: _wire_transcript(x))
+    reg["blk-kept-ricnt"] = lambda: _kept_ricnt_transcript()
     for case in dtset_cases_all():
         reg[dtset_ref_name(case)] = (lambda c=case: dtset_transcript(c))
     for name in ("emit-verdict", "emit-sweep"):

@@ -2,12 +2,15 @@
 qh_qpack_enc_refs_record, qh_qpack_enc_refs_compact,
 qh_qpack_enc_read_decoder, qh_qpack_dec_write_decoder), CPU only.
 
-Section Acknowledgment is judged by the reference library: every encoder case
-with an ack step is replayed with the step delivered as decoder-stream bytes,
-and the state read back is held against the transcript's digest.  Increment,
-Cancellation and the writer are judged by the reference's own unit test
-(test_nghttp3_qpack_decoder_feedback, restated as data in ack_cases.FEEDBACK).
-Everything else rests on the Python restatement in ack_cases.py.  The host
+Judged by the reference library (transcripts of oracle/ref_replay.c under
+tests/golden/ref_replay/): every encoder case with an ack step, replayed with
+the step delivered as decoder-stream bytes; the reader's rules, limits, partial
+instructions and the 512-byte stage edge (ds-*); the writer's bytes and
+written_icnt (dw-items); three rounds of the whole loop with both ends
+recorded (loop-17x5).  The reference's own unit test
+(test_nghttp3_qpack_decoder_feedback, restated as data in ack_cases.FEEDBACK)
+and the Python restatement in ack_cases.py judge what the tests build
+synthetically: NOMEM, the layout, tables lists in error.  The host
 twins also run under AddressSanitizer and UBSan in a process of their own
 (tests/c/ack_host.c)."""
 import os
@@ -19,6 +22,7 @@ import pytest
 
 import ack_cases as ac
 import enc_cases as ec
+import ref_cases as rc
 from conftest import ROOT
 from nghttp3_amd import DynamicTableSet, EncoderSet, _lib, qpack
 
@@ -287,6 +291,103 @@ def test_writer_needs_consecutive_tables():
 
 def test_blocked_blocks_are_not_acknowledged():
     ac.blocked_blocks()
+
+
+# ---- 9. the reader against the reference library's transcripts --------------------
+
+DS_CASES = ac.ds_cases()
+
+
+@pytest.mark.parametrize("case", DS_CASES, ids=repr)
+def test_decoder_stream_case_against_the_reference(case):
+    """Every ("dstream", ...) step's status, consumed, running length, BAD flag
+    and state digest are the reference library's (run_case)."""
+    ac.run_case(case)
+
+
+def test_decoder_stream_cases_reach_their_rules():
+    """What the ds-* cases must contain, read from their transcripts and from
+    the state after them, so that none passes vacuously."""
+    by = {c.name: c for c in DS_CASES}
+    last = lambda name, k=-1: [[s for s in steps if s["op"] == "dstream"][k]
+                               for steps in (rc.load(name)["conns"][c] for c in rc.load(name)["conn_of"])]
+    # ds-lattice: the acknowledgements and cancellations pass; increments up to 64 pass, the larger give -403
+    n7, n6 = len(ac.GROW7), len(ac.GROW6)
+    rvs = [s["rv"] for s in last("ds-lattice")]
+    streams = by["ds-lattice"].steps[-1][1]
+    assert rvs[:n7 + n6] == [len(x) for x in streams[:n7 + n6]]
+    assert rvs[n7 + n6:] == [len(x) if v <= 64 else DS_ERR for v, x in zip(ac.GROW6, streams[n7 + n6:])]
+    assert sorted(rvs[n7 + n6:])[-3:] == [1, 2, 2]
+    assert sorted({len(x) for x in streams}) == [1, 2, 3, 4, 10]
+    model, _ = ac.run_case(by["ds-lattice"])
+    assert [len(e.streams) for e in model.enc[:n7 + n6]] == [1] * n7 + [0] * n6
+    assert [e.next_absidx for e in model.enc[n7 + n6:]] == [ac.DS_LATTICE_INSERTS] * n6
+    # ds-errors: the nine verdicts, then -108 where the first call failed
+    first, second = last("ds-errors", 0), last("ds-errors", 1)
+    assert [s["rv"] for s in first] == [st if st else len(x) for (st, _), x in
+                                        zip(ac.DS_ERRORS_WANT, by["ds-errors"].steps[-2][1])]
+    assert [s["bad"] for s in first] == [int(st != 0) for st, _ in ac.DS_ERRORS_WANT]
+    assert [s["rv"] for s in second] == [FATAL if b["bad"] else (DS_ERR if t == 1 else 1)
+                                         for t, b in enumerate(first)]
+    model, _ = ac.run_case(by["ds-errors"])
+    assert model.enc[1].krcnt == model.enc[1].next_absidx == 3  # (exactly insert_count - krcnt)
+    assert [m.nblocked() for m in (ac.AckModel(by["ds-errors"]).enc[6], model.enc[6])] == [0, 1]
+    # ds-overflow: -403 and BAD, then -108
+    assert [(s["rv"], s["bad"]) for s in last("ds-overflow", 0)] == [(DS_ERR, 1)] * 5
+    assert [s["rv"] for s in last("ds-overflow", 1)] == [FATAL] * 5
+    # ds-limit: the length rule gives -403 without BAD, again -403 (not -108), and an encode clears it
+    a, b, c = last("ds-limit", 0), last("ds-limit", 1), last("ds-limit", 2)
+    assert [(s["rv"], s["dlen"], s["bad"]) for s in a] == [(4096, 4096, 0), (DS_ERR, 4097, 0), (4000, 4000, 0)]
+    assert [(s["rv"], s["dlen"], s["bad"]) for s in b] == [(0, 4096, 0), (DS_ERR, 4098, 0), (96, 4096, 0)]
+    assert [(s["rv"], s["dlen"], s["bad"]) for s in c] == [(1, 1, 0)] * 3
+    # ds-stage: at least 17 references, every stream read to its end, the cut one to byte 509
+    assert len(by["ds-stage"].steps) - 3 >= 17
+    assert [s["rv"] for s in last("ds-stage", 0)] == list(ac.DS_STAGE_LENS)
+    assert not any(s["bad"] for s in last("ds-stage"))
+    # ds-partials: a cut at every third byte; every tail ends the stream with the whole stream's state
+    sts = {s["st"] for s in last("ds-partials")}
+    assert len(sts) == 1 and len(last("ds-partials")) >= 40
+
+
+PREFIXES = [(c, n) for c in DS_CASES for n in (1, 3, 4, 5, 17) if n < c.n]
+
+
+@pytest.mark.parametrize("case, n", PREFIXES, ids=lambda x: repr(x))
+def test_decoder_stream_case_first_connections(case, n):
+    ac.run_case(case, n=n)
+
+
+# ---- 10. the writer against the reference library's transcripts --------------------
+
+def test_writer_items_against_the_reference():
+    """dw-items: every table's decoder-stream bytes and written_icnt after
+    every batch are the reference library's; and what the case must contain."""
+    tables = ac.dw_items()
+    out = ac.run_dw("dw-items", tables)
+    assert out[0][0] == b"".join(ac.ack(v) for v in ac.GROW7)  # (ricnt 0: stream 2 is not acknowledged)
+    assert out[1][0] == b"" and out[0][4] == b"" and out[1][4] == b""
+    assert out[0][1] == b"".join(ac.cancel(v) for v in ac.GROW6) + ac.incr(62)  # (the held section: no ack)
+    assert out[1][1] == ac.cancel(8) + ac.cancel(77)
+    assert [out[b][2] for b in range(3)] == [ac.incr(63), ac.ack(12) + ac.incr(5), ac.ack(16) + ac.incr(4)]
+    assert out[0][3] == ac.incr(64)  # (the failing section: the reference writes the increment alone)
+    assert out[0][5] == ac.incr((1 << 14) + 63) and len(out[0][5]) == 4
+    tr = rc.load("dw-items")
+    assert [s["rv"] for s in tr["conns"][3] if s["op"] == "hold"] == [-401]
+    assert [s["blocked"] for s in tr["conns"][1] if s["op"] == "hold"] == [1]
+
+
+@pytest.mark.parametrize("ntables", [65, 257])
+def test_writer_items_replicated(ntables):
+    ac.run_dw("dw-items", ac.dw_items(), ntables=ntables)
+
+
+# ---- 11. the closure over rounds, both ends the reference's -------------------------
+
+@pytest.mark.parametrize("n", [1, 17, 65])
+def test_three_rounds_against_the_reference(n):
+    """loop-17x5: sections, encoder streams, decoder streams and the state
+    after every read are the reference's own, round after round."""
+    ac.loop_against_reference(n=n)
 
 
 # ---- the host twins under the sanitizers ------------------------------------------

@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import ack_cases as ac
 import blocked_cases as bc
 from oracle import qpack_qif as oq
 
@@ -86,3 +87,39 @@ def test_loop_with_encoder_streams_in_two_halves():
     the encoder ends every round with no stream outstanding."""
     pushes, inside = bc.delayed_loop()
     assert pushes > 0 and inside > 0, (pushes, inside)
+
+
+def test_a_released_block_keeps_its_required_insert_count_in_the_reference():
+    """blk-kept-ricnt: the reference keeps the Required Insert Count a held
+    section was blocked with and emits its fields when resumed, where this
+    project reconstructs it again from the encoded value and gives -401
+    (DESIGN 3.12).  The transcript records the first outcome; the second is
+    pinned beside it.  Only a non-conformant encoder gets here (see
+    blocked_cases.kept_ricnt_items)."""
+    steps, status, stream = bc.kept_ricnt()
+    r = steps["resume"]
+    assert (r["rv"], r["blocked"], r["ricnt"], r["n"], r["left"]) == (2, 0, bc.KEPT_RICNT, 2, 0)
+    assert status == [bc.TOO_MANY]  # (-401)
+    # the reference acknowledges the section and adds the rest; this project adds all 150
+    w = steps["dwrite"]
+    assert (w["len"], w["d"], w["written_icnt"]) == (3, ac.ds16(ac.ack(bc.KEPT_SID) + ac.incr(130)), 150)
+    assert stream == ac.incr(150)
+
+
+@pytest.mark.parametrize("behind", [1, 2])
+def test_corpus_decoder_streams_against_the_reference(behind):
+    """dw-wire-1, dw-wire-2: after every record of the delayed corpus wire the
+    decoder-stream bytes and written_icnt, and every section's verdict and
+    field digest (held, emitted at once or released), are the reference's."""
+    data, recs = bc.corpus()
+    text, pushes, depth = bc.run_wire(data, bc.delayed(recs, behind), 100, ref=bc.WireRef("dw-wire-%d" % behind))
+    assert (pushes, depth) == (18, behind)
+    tr = bc.WireRef("dw-wire-%d" % behind).steps
+    assert sum(s["op"] == "resume" for s in tr) == 18 == sum(s["op"] == "hold" and s["blocked"] for s in tr)
+    assert max(s["len"] for s in tr if s["op"] == "dwrite") < 2000  # (qpack_decoder_dbuf_overflow is not restated)
+
+
+@pytest.mark.parametrize("n", [1, 17, 65])
+def test_loop_in_two_halves_against_the_reference(n):
+    pushes = bc.delayed_loop_against_reference(n=n)
+    assert pushes > 0

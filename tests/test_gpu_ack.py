@@ -234,3 +234,32 @@ def test_three_rounds_on_the_device(dev):
         enc = lp.sets[0].enc_records()
         assert enc["krcnt"].tolist() == [m.krcnt for m in models] and not enc["nstreams"].any()
     assert inserts[0] > 0 and inserts[2] < inserts[0] and indexed[2] > indexed[0], (inserts, indexed)
+
+
+# ---- 7. the reference library's transcripts: reader, writer, closure -----------------------
+
+DS_CASES = ac.ds_cases()
+# (qh_k_ack_read: 64 threads, 16 lanes per stream, four streams per workgroup:
+# a partial workgroup, a full one, one over, and a second 16-stream wave group)
+PREFIXES = [(c, n) for c in DS_CASES for n in (1, 3, 4, 5, 17) if n < c.n]
+
+
+@pytest.mark.parametrize("case", DS_CASES, ids=repr)
+def test_decoder_stream_case_against_the_reference(dev, case):
+    ac.run_case(case, dev)
+
+
+@pytest.mark.parametrize("case, n", PREFIXES, ids=lambda x: repr(x))
+def test_decoder_stream_case_first_connections(dev, case, n):
+    ac.run_case(case, dev, n=n)
+
+
+@pytest.mark.parametrize("ntables", [None, 65, 257])
+def test_writer_items_against_the_reference(dev, ntables):
+    """(lane per item, 256 threads per workgroup: 6 tables, 65, 257)"""
+    ac.run_dw("dw-items", ac.dw_items(), dev, ntables)
+
+
+@pytest.mark.parametrize("n", [1, 17, 65])
+def test_three_rounds_against_the_reference(dev, n):
+    ac.loop_against_reference(dev, n)

@@ -152,3 +152,24 @@ def test_loop_with_encoder_streams_in_two_halves(dev):
     every round with nstreams == 0 (asserted inside delayed_loop)."""
     pushes, inside = bc.delayed_loop(dev)
     assert pushes > 0 and inside > 0, (pushes, inside)
+
+
+# ---- 6. the reference library's transcripts -----------------------------------------------------
+
+@pytest.mark.parametrize("behind", [1, 2])
+@pytest.mark.parametrize("copies", [1, 17, 65])
+def test_corpus_decoder_streams_against_the_reference(dev, copies, behind):
+    data, recs = bc.corpus()
+    text, pushes, depth = bc.run_wire(data, bc.delayed(recs, behind), 100, dev, copies,
+                                      ref=bc.WireRef("dw-wire-%d" % behind))
+    assert (pushes, depth) == (18, behind)
+
+
+def test_a_released_block_keeps_its_required_insert_count_in_the_reference(dev):
+    steps, status, stream = bc.kept_ricnt(dev)
+    assert steps["resume"]["rv"] == 2 and status == [bc.TOO_MANY] and stream == ac.incr(150)
+
+
+@pytest.mark.parametrize("n", [1, 17, 65])
+def test_loop_in_two_halves_against_the_reference(dev, n):
+    assert bc.delayed_loop_against_reference(dev, n) > 0
