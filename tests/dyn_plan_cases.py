@@ -13,7 +13,13 @@ back in one entry / byte log (a later table's views have ent_base != 0);
 section_view, ref_limit (or None), fields [(name, value, never)],
 field_start; `bad` describes a deliberate damage to the library's arrays
 that the planner must handle (never a fault: the entry just does not
-match); `edge` packs the strings against 4 KiB page edges."""
+match); `edge` packs the strings against 4 KiB page edges.
+
+A case whose table holds what the reference's own encoder never inserts (an
+exact static entry, a second copy of a live entry, authorization, a short
+cookie) is listed a second time as <name>-ref with the table that encoder
+would hold (reference_form): the form in which the reference library itself
+judges the plan (tests/plan_ref_cases.py)."""
 import functools
 import json
 import os
@@ -442,11 +448,66 @@ def _mixed():
     return Case("mixed-corpus", [(32768, steps_of(tab) + [("view",)])], None, None, fields, fs)
 
 
+def step_entry(step):
+    """The (name, value) an "ins" or "sins" step inserts."""
+    return (step[1], step[2]) if step[0] == "ins" else (oq.static_table()[0][step[1]][0], step[2])
+
+
+def reference_tables(tables):
+    """The tables the reference's own encoder (eager, every field flagged
+    try-index) holds when it is given the tables' entries as fields, one
+    after the other: it inserts no exact static entry (:1483-1486), no field
+    equal to a live entry (it refers to that entry, :1517-1540; a Duplicate
+    arises only from draining) and none in NEVER mode (authorization, a
+    cookie shorter than 20 bytes, :1315-1320).  -> (tables without those
+    steps, [(table, step index, why)] for what was dropped)."""
+    out, dropped = [], []
+    for t, (hard_max, steps) in enumerate(tables):
+        live, size, kept = [], 0, []  # live: oldest first
+        for j, s in enumerate(steps):
+            if s[0] == "view":
+                kept.append(s)
+                continue
+            if s[0] == "dup":
+                dropped.append((t, j, "duplicate"))
+                continue
+            name, value = step_entry(s)
+            if name == b"authorization" or (name == b"cookie" and len(value) < 20):
+                dropped.append((t, j, "never-index name"))
+            elif oq.plan_field(name, value)[0] == qf.FL_INDEXED:
+                dropped.append((t, j, "static entry"))
+            elif (name, value) in live:
+                dropped.append((t, j, "equal to a live entry"))
+            else:
+                need = len(name) + len(value) + 32
+                assert need <= hard_max
+                while size + need > hard_max:
+                    old = live.pop(0)
+                    size -= len(old[0]) + len(old[1]) + 32
+                live.append((name, value))
+                size += need
+                kept.append(s)
+        out.append((hard_max, kept))
+    return out, dropped
+
+
+def reference_form(case):
+    """The case against the table the reference's encoder would hold
+    (reference_tables), named <name>-ref, with the same fields and sections;
+    None where that is the case's own table, and for a `bad` case (its damage
+    is placed by the table as written)."""
+    if case.bad:
+        return None
+    tables, dropped = reference_tables(case.tables)
+    return case._replace(name=case.name + "-ref", tables=tables) if dropped else None
+
+
 @functools.lru_cache(maxsize=None)
 def cases():
     out = _size_cases() + [_eviction(), _two_logs(), _two_views(), _bad_view(), _selection(),
                            _ref_limit(), _never(), _strings(), _page_edges(), _index_widths(),
                            _prefix_wrap()] + _counts() + _bad() + [_mixed()]
+    out += [r for r in map(reference_form, out) if r is not None]
     assert len({c.name for c in out}) == len(out)
     return tuple(out)
 

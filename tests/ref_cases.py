@@ -16,7 +16,9 @@ _fold_decoder, KEYS): an encoder's encode step the rolling digest of sections,
 encoder-stream bytes and counts so far (chain) and a digest of scalars and
 table (enc_state_digest); a decoder's step its numbers and a digest of the
 table or of the decoded fields.  A digest is the first 16 hex digits of a
-SHA-256.  The walk case of the closure test also keeps its bytes.  What a
+SHA-256.  The walk case of the closure test also keeps its bytes.  The
+planners' transcripts (kind "planner": a fill step and probe steps) are
+written and compared by tests/plan_ref_cases.py.  What a
 digest stands for is printed by the driver: a mismatch is looked into by
 running it on the case file (enc_script, dec_script)."""
 import hashlib
@@ -270,7 +272,7 @@ def record(name, kind, scripts, full=False, note="", copies=False):
 # On disk a step is a list: the operation's letter, then the values of its
 # keys in this order, trailing absent ones left off.
 LETTER = {"new": "n", "cap": "c", "ack": "a", "ackall": "A", "encode": "e", "estream": "s", "section": "q",
-          "dstream": "d", "cancel": "x", "hold": "h", "resume": "r", "dwrite": "w"}
+          "dstream": "d", "cancel": "x", "hold": "h", "resume": "r", "dwrite": "w", "fill": "f", "probe": "p"}
 KEYS = {"encoder": {"new": (), "cap": ("st",), "ack": ("sid", "rv", "st"), "ackall": ("st",),
                     "encode": ("sid", "rv", "eslen", "out", "st", "sec", "es"),
                     "dstream": ("rv", "dlen", "bad", "st"), "cancel": ("sid", "st")},
@@ -278,7 +280,8 @@ KEYS = {"encoder": {"new": (), "cap": ("st",), "ack": ("sid", "rv", "st"), "acka
                     "section": ("rv", "blocked", "ricnt", "base", "n", "d"),
                     "hold": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
                     "resume": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
-                    "cancel": ("sid", "rv"), "dwrite": ("len", "d", "written_icnt", "ds")}}
+                    "cancel": ("sid", "rv"), "dwrite": ("len", "d", "written_icnt", "ds")},
+        "planner": {"new": (), "fill": ("insert_count", "krcnt", "cap", "n", "d"), "probe": ("k", "rv", "out")}}
 
 
 def _pack(kind, d):
@@ -486,4 +489,7 @@ def registry():
         reg[dtset_ref_name(case)] = (lambda c=case: dtset_transcript(c))
     for name in ("emit-verdict", "emit-sweep"):
         reg[name] = (lambda n=name: emit_transcript(n))
+    import plan_ref_cases as pr
+    for name in pr.names():
+        reg[name] = (lambda n=name: pr.record(n))
     return reg

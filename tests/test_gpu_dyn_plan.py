@@ -15,6 +15,7 @@ import pytest
 
 import dyn_plan_cases as dc
 import plan_cases as pc
+import plan_ref_cases as pr
 from nghttp3_amd import _lib, qpack
 from nghttp3_amd.qpack_huffman import SPAN_IN_DTYPE
 
@@ -213,6 +214,25 @@ def test_encode_fields_against_a_table(enc, name):
     assert h_dst.tobytes() == want_dst.tobytes() and h_sec.tobytes() == want_sec.tobytes()
     assert h_mx.tobytes() == h["plan"]["max_cnt"].tobytes()
     assert h_mn.tobytes() == h["plan"]["min_cnt"].tobytes()
+
+
+@pytest.mark.parametrize("name", pr.replayed())
+def test_encode_fields_against_a_table_equals_the_reference_s_sections(enc, name):
+    """The sections qh_encode_fields_dyn_batch writes on the device, and the
+    device's max_cnt / min_cnt, against the reference encoder's own for the
+    same fields and table (tests/golden/ref_replay/plan-dyn-*.json), not by
+    way of the host planner."""
+    d = Dev(name)
+    h = d.h
+    cap = 4 * d.nsec + sum(len(n) + len(v) + 24 for n, v, _ in dc.by_name(name).fields)  # (any literal fits)
+    rv, need, dst, sec, mx, mn = encode_dev(enc, d, _cuda(fields_of(h["strs"], h["never"])), cap)
+    assert rv == 0 and need <= cap and (dst[need:] == PATTERN).all()
+    assert int(sec["len"].sum()) == need
+    dst = dst.tobytes()
+    mx, mn = np.frombuffer(mx, np.uint64), np.frombuffer(mn, np.uint64)
+    pr.check(pr.transcript_name(name),
+             lambda b: (dst[int(sec["off"][b]):int(sec["off"][b]) + int(sec["len"][b])], mx[b], mn[b]),
+             "qh_encode_fields_dyn_batch on the device")
 
 
 @pytest.mark.parametrize("name", [n for n in CASES if dc.by_name(n).bad is None])

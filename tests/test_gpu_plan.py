@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import plan_cases as pc
+import plan_ref_cases as pr
 from nghttp3_amd import _lib, qpack
 from nghttp3_amd.qpack_huffman import SPAN_IN_DTYPE
 
@@ -151,6 +152,23 @@ def test_encode_fields_on_the_device(enc, shape):
     # and through host memory
     h_dst, h_sec = enc.encode_fields(plain, fields_of(strs, never), fs)
     assert h_dst.tobytes() == want_dst.tobytes() and h_sec.tobytes() == want_sec.tobytes()
+
+
+@pytest.mark.parametrize("run", sorted(pr.STATIC_RUNS))
+def test_encode_fields_on_the_device_equals_the_reference_s_sections(enc, run):
+    """The sections qh_encode_fields_batch writes on the device against the
+    reference encoder's own (tests/golden/ref_replay/plan-static-*.json),
+    not by way of the host planner."""
+    fields, never, fs = pr.static_run(run)
+    plain, strs = pc.pack(fields)
+    cap = 2 * fs.size + sum(len(n) + len(v) + 24 for n, v, _ in fields)  # (any literal fits its field's share)
+    rv, need, dst, sec = encode_dev(enc, _cuda(plain), _cuda(fields_of(strs, never)), len(fields),
+                                    _i32(fs), cap, fill=PATTERN)
+    assert rv == 0 and need <= cap and (dst[need:] == PATTERN).all()
+    dst = dst.tobytes()
+    assert int(sec["len"].sum()) == need and len(sec) == fs.size - 1
+    pr.check(run, lambda b: (dst[int(sec["off"][b]):int(sec["off"][b]) + int(sec["len"][b])], 0,
+                             pr.UINT64_MAX), "qh_encode_fields_batch on the device")
 
 
 def test_encode_fields_without_fields_or_sections(enc):

@@ -24,12 +24,13 @@ def test_every_case_has_a_transcript_and_every_transcript_a_case():
         path = os.path.join(rc.DIR, f)
         tr = rc.load(name)
         assert tr["case"] == name and tr["kind"] in ("encoder", "decoder tables", "decoder sections",
-                                                      "decoder stream")
+                                                      "decoder stream", "planner")
         assert tr["conns"] and all(0 <= c < len(tr["conns"]) for c in tr["conn_of"])
         for steps in tr["conns"]:
             assert steps[0]["op"] == "new" and len(steps) > 1
             # every connection ends on a step that carries what is compared
-            assert any(k in steps[-1] for k in ("st", "d")), (f, steps[-1])
+            carried = ("out",) if tr["kind"] == "planner" else ("st", "d")
+            assert any(k in steps[-1] for k in carried), (f, steps[-1])
         size = os.path.getsize(path)
         assert size < os.path.getsize(os.path.join(GOLDEN, "corpus.npz")), f
         total += size
