@@ -22,6 +22,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._arrays import Backend, cap_for, grow
 from .qpack_huffman import SPAN_IN_DTYPE, SPAN_OUT_DTYPE, HuffmanBatchCodec
 
 QH_ERR_QPACK_HEADER_TOO_LARGE = -109
@@ -111,6 +112,14 @@ class qh_sections(ctypes.Structure):
 _L = None
 
 
+def _pair(lib, stem, args):
+    """A host twin qh_qpack_<stem>(args) and its batch form
+    qh_<stem>_batch(ctx, args, where), declared together."""
+    host, batch = getattr(lib, "qh_qpack_" + stem), getattr(lib, "qh_%s_batch" % stem)
+    host.argtypes, batch.argtypes = args, [ctypes.c_void_p] + args + [ctypes.c_int]
+    host.restype = batch.restype = ctypes.c_int
+
+
 def _load():
     global _L
     if _L is None:
@@ -158,24 +167,15 @@ def _load():
         lib.qh_qpack_static_entry.argtypes = [sz, c.POINTER(vp), c.POINTER(sz), c.POINTER(vp),
                                               c.POINTER(sz)]
         lib.qh_qpack_static_entry.restype = i32
-        lib.qh_qpack_plan_fields.argtypes = [vp, vp, sz, vp, vp]
-        lib.qh_qpack_plan_fields.restype = i32
+        _pair(lib, "plan_fields", [vp, vp, sz, vp, vp])
         lib.qh_encode_sections_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, u64, vp,
                                                  c.POINTER(u64), i32]
         lib.qh_encode_sections_batch.restype = i32
-        lib.qh_plan_fields_batch.argtypes = [vp, vp, vp, sz, vp, vp, i32]
-        lib.qh_plan_fields_batch.restype = i32
         lib.qh_encode_fields_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, u64, vp, c.POINTER(u64), i32]
         lib.qh_encode_fields_batch.restype = i32
-        lib.qh_qpack_dyn_keys.argtypes = [vp, sz, vp, u64, sz, sz, vp]
-        lib.qh_qpack_dyn_keys.restype = i32
-        lib.qh_dyn_keys_batch.argtypes = [vp, vp, sz, vp, u64, sz, sz, vp, i32]
-        lib.qh_dyn_keys_batch.restype = i32
+        _pair(lib, "dyn_keys", [vp, sz, vp, u64, sz, sz, vp])
         dynp = c.POINTER(qh_plan_dyn)
-        lib.qh_qpack_plan_fields_dyn.argtypes = [vp, vp, sz, vp, vp, sz, dynp, vp, vp, vp, vp]
-        lib.qh_qpack_plan_fields_dyn.restype = i32
-        lib.qh_plan_fields_dyn_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz, dynp, vp, vp, vp, vp, i32]
-        lib.qh_plan_fields_dyn_batch.restype = i32
+        _pair(lib, "plan_fields_dyn", [vp, vp, sz, vp, vp, sz, dynp, vp, vp, vp, vp])
         lib.qh_encode_fields_dyn_batch.argtypes = [vp, vp, vp, sz, vp, sz, dynp, vp, u64, vp,
                                                    c.POINTER(u64), vp, vp, i32]
         lib.qh_encode_fields_dyn_batch.restype = i32
@@ -191,85 +191,33 @@ def _load():
         lib.qh_dtable_entries.restype = vp
         lib.qh_dtable_bytes.argtypes = [vp, c.POINTER(sz)]
         lib.qh_dtable_bytes.restype = vp
-        emit_args = [vp, vp, sz, c.POINTER(qh_sections), vp, vp, vp, vp, vp, sz, c.c_uint32,
-                     c.POINTER(_lib.qh_emit)]
-        lib.qh_qpack_emit_fields.argtypes = emit_args
-        lib.qh_qpack_emit_fields.restype = i32
-        lib.qh_emit_fields_batch.argtypes = [vp] + emit_args + [i32]
-        lib.qh_emit_fields_batch.restype = i32
+        _pair(lib, "emit_fields", [vp, vp, sz, c.POINTER(qh_sections), vp, vp, vp, vp, vp, sz, c.c_uint32,
+                                   c.POINTER(_lib.qh_emit)])
         lib.qh_dtable_state_init.argtypes = [u64, vp, vp]
         lib.qh_dtable_state_init.restype = None
-        dts_args = [vp, vp, vp, sz, sz, vp, vp, vp, c.POINTER(u64), u64, vp, c.POINTER(u64), u64,
-                    vp, vp]
-        lib.qh_qpack_dtables_apply.argtypes = dts_args
-        lib.qh_qpack_dtables_apply.restype = i32
-        lib.qh_dtables_apply_batch.argtypes = [vp] + dts_args + [i32]
-        lib.qh_dtables_apply_batch.restype = i32
-        dtc_args = [sz, vp, vp, u64, vp, u64, vp, c.POINTER(u64), u64, vp, c.POINTER(u64), u64, vp]
-        lib.qh_qpack_dtables_compact.argtypes = dtc_args
-        lib.qh_qpack_dtables_compact.restype = i32
-        lib.qh_dtables_compact_batch.argtypes = [vp] + dtc_args + [i32]
-        lib.qh_dtables_compact_batch.restype = i32
+        pu64 = c.POINTER(u64)
+        _pair(lib, "dtables_apply", [vp, vp, vp, sz, sz, vp, vp, vp, pu64, u64, vp, pu64, u64, vp, vp])
+        _pair(lib, "dtables_compact", [sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64, vp])
         lib.qh_enc_state_init.argtypes = [u64, u64, u64, vp, vp, vp]
         lib.qh_enc_state_init.restype = None
         lib.qh_enc_state_set_capacity.argtypes = [vp, vp, u64]
         lib.qh_enc_state_set_capacity.restype = None
-        pu64 = c.POINTER(u64)
-        encc_args = [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, pu64, u64, vp, pu64,
-                     u64, vp, vp, vp, vp, vp, vp, u64, vp, pu64, vp, u64, vp, pu64, vp]
-        lib.qh_qpack_encode_conns.argtypes = encc_args
-        lib.qh_qpack_encode_conns.restype = i32
-        lib.qh_encode_conns_batch.argtypes = [vp] + encc_args + [i32]
-        lib.qh_encode_conns_batch.restype = i32
+        _pair(lib, "encode_conns", [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, pu64, u64,
+                                    vp, pu64, u64, vp, vp, vp, vp, vp, vp, u64, vp, pu64, vp, u64, vp, pu64,
+                                    vp])
         lib.qh_enc_refs_init.argtypes = [vp]
         lib.qh_enc_refs_init.restype = None
-        sf_args = [vp, sz, vp, sz, vp, sz, vp, vp, vp, u64, vp, vp]
-        lib.qh_qpack_enc_sec_flags.argtypes = sf_args
-        lib.qh_qpack_enc_sec_flags.restype = i32
-        lib.qh_enc_sec_flags_batch.argtypes = [vp] + sf_args + [i32]
-        lib.qh_enc_sec_flags_batch.restype = i32
-        rec_args = [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, pu64, u64]
-        lib.qh_qpack_enc_refs_record.argtypes = rec_args
-        lib.qh_qpack_enc_refs_record.restype = i32
-        lib.qh_enc_refs_record_batch.argtypes = [vp] + rec_args + [i32]
-        lib.qh_enc_refs_record_batch.restype = i32
-        cmp_args = [vp, sz, sz, vp, vp, u64, vp, pu64, u64]
-        lib.qh_qpack_enc_refs_compact.argtypes = cmp_args
-        lib.qh_qpack_enc_refs_compact.restype = i32
-        lib.qh_enc_refs_compact_batch.argtypes = [vp] + cmp_args + [i32]
-        lib.qh_enc_refs_compact_batch.restype = i32
-        rd_args = [vp, vp, vp, sz, sz, vp, vp, vp, vp, u64, vp, vp]
-        lib.qh_qpack_enc_read_decoder.argtypes = rd_args
-        lib.qh_qpack_enc_read_decoder.restype = i32
-        lib.qh_enc_read_decoder_batch.argtypes = [vp] + rd_args + [i32]
-        lib.qh_enc_read_decoder_batch.restype = i32
-        wd_args = [vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, u64, vp, pu64]
-        lib.qh_qpack_dec_write_decoder.argtypes = wd_args
-        lib.qh_qpack_dec_write_decoder.restype = i32
-        lib.qh_dec_write_decoder_batch.argtypes = [vp] + wd_args + [i32]
-        lib.qh_dec_write_decoder_batch.restype = i32
+        _pair(lib, "enc_sec_flags", [vp, sz, vp, sz, vp, sz, vp, vp, vp, u64, vp, vp])
+        _pair(lib, "enc_refs_record", [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, pu64, u64])
+        _pair(lib, "enc_refs_compact", [vp, sz, sz, vp, vp, u64, vp, pu64, u64])
+        _pair(lib, "enc_read_decoder", [vp, vp, vp, sz, sz, vp, vp, vp, vp, u64, vp, vp])
+        _pair(lib, "dec_write_decoder", [vp, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, u64, vp, pu64])
         lib.qh_dec_blks_init.argtypes = [u64, vp]
         lib.qh_dec_blks_init.restype = None
-        bp_args = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, pu64, u64, vp, pu64, u64, vp]
-        lib.qh_qpack_dec_blocked_push.argtypes = bp_args
-        lib.qh_qpack_dec_blocked_push.restype = i32
-        lib.qh_dec_blocked_push_batch.argtypes = [vp] + bp_args + [i32]
-        lib.qh_dec_blocked_push_batch.restype = i32
-        br_args = [vp, sz, sz, vp, vp, vp, u64, vp, vp, vp, vp, vp, pu64, u64]
-        lib.qh_qpack_dec_blocked_release.argtypes = br_args
-        lib.qh_qpack_dec_blocked_release.restype = i32
-        lib.qh_dec_blocked_release_batch.argtypes = [vp] + br_args + [i32]
-        lib.qh_dec_blocked_release_batch.restype = i32
-        bc_args = [vp, vp, sz, sz, vp, vp, u64, vp]
-        lib.qh_qpack_dec_blocked_cancel.argtypes = bc_args
-        lib.qh_qpack_dec_blocked_cancel.restype = i32
-        lib.qh_dec_blocked_cancel_batch.argtypes = [vp] + bc_args + [i32]
-        lib.qh_dec_blocked_cancel_batch.restype = i32
-        bk_args = [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64]
-        lib.qh_qpack_dec_blocked_compact.argtypes = bk_args
-        lib.qh_qpack_dec_blocked_compact.restype = i32
-        lib.qh_dec_blocked_compact_batch.argtypes = [vp] + bk_args + [i32]
-        lib.qh_dec_blocked_compact_batch.restype = i32
+        _pair(lib, "dec_blocked_push", [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, pu64, u64, vp, pu64, u64, vp])
+        _pair(lib, "dec_blocked_release", [vp, sz, sz, vp, vp, vp, u64, vp, vp, vp, vp, vp, pu64, u64])
+        _pair(lib, "dec_blocked_cancel", [vp, vp, sz, sz, vp, vp, u64, vp])
+        _pair(lib, "dec_blocked_compact", [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64])
         _L = lib
     return _L
 
@@ -284,6 +232,18 @@ def _u8(data):
 
 def _vp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _plain(x):
+    """Plaintext as a uint8 array; an empty one becomes one zero byte (the
+    batch calls take no NULL plain)."""
+    a = _u8(x)
+    return a if a.size else np.zeros(1, dtype=np.uint8)
+
+
+def _as(x, dtype):
+    """None, or a contiguous array of dtype."""
+    return None if x is None else np.ascontiguousarray(x, dtype=dtype)
 
 
 def scan_field_section(buf, base_off: int = 0):
@@ -401,7 +361,7 @@ def write_sections(plain, strs, lines, line_start, prefixes=None):
     cap = int(strs["len"].sum(dtype=np.uint64)) + 20 * lines.size + 20 * nsec + 1
     dst = np.zeros(cap, dtype=np.uint8)
     sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
-    pf = None if prefixes is None else np.ascontiguousarray(prefixes, dtype=PREFIX_DTYPE)
+    pf = _as(prefixes, PREFIX_DTYPE)
     _lib.check(lib.qh_qpack_write_sections(_vp(plain), _vp(strs), _vp(lines), _vp(line_start), nsec,
                                            None if pf is None else _vp(pf), _vp(dst), cap,
                                            _vp(sections)),
@@ -727,6 +687,23 @@ class FieldSectionDecoder:
                            int(res["nhuff"]), int(res["dst_need"]))
 
     @staticmethod
+    def _emit(be, addr, what, o, nl, materialise, call):
+        """The emit call over the outputs `o` (room for nl fields), made once
+        more with an ``out`` of out_need bytes when that was short -> qh_emit."""
+        for _ in range(2):
+            out = o["out"] if materialise else None
+            e = _lib.qh_emit(addr(o["fields"]), nl, addr(o["field_start"]), addr(o["status"]),
+                             addr(o["ricnt"]), addr(out) if materialise else None, be.size(out),
+                             addr(o["out_blocks"]), 0, 0, 0)
+            rv = call(ctypes.byref(e))
+            if rv == _lib.QH_ERR_NOMEM and materialise and e.out_need > be.size(out):
+                o["out"] = be.empty(int(e.out_need))
+                continue
+            _lib.check(rv, what)
+            break
+        return e
+
+    @staticmethod
     def emit_fields(res, src, blocks, table=None, views=None, block_view=None, sel=None,
                     qif=False, materialise=True, entries=None, dyn_bytes=None):
         """Host arrays: the header list of every selected block of `res` (a
@@ -745,10 +722,10 @@ class FieldSectionDecoder:
         if table is not None:
             views = table.view() if views is None else views
             entries, dyn_bytes = table.entries(), table.bytes()
-        vw = None if views is None else np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
-        bv = None if block_view is None else np.ascontiguousarray(block_view, dtype=np.uint32)
-        sl = None if sel is None else np.ascontiguousarray(sel, dtype=np.uint32)
-        ents = None if entries is None else np.ascontiguousarray(entries, dtype=DYN_ENTRY_DTYPE)
+        vw = None if views is None else _as(views, VIEW_DTYPE).reshape(-1)
+        bv = _as(block_view, np.uint32)
+        sl = _as(sel, np.uint32)
+        ents = _as(entries, DYN_ENTRY_DTYPE)
         dbytes = None if dyn_bytes is None else _u8(dyn_bytes)
         nsel = blocks.size if sl is None else sl.size
         st = FieldSectionDecoder._sections_struct(res, lambda a: a.ctypes.data)
@@ -759,19 +736,11 @@ class FieldSectionDecoder:
              "out_blocks": np.zeros(max(nsel, 1), dtype=SPAN_IN_DTYPE),
              "out": np.zeros(1, dtype=np.uint8) if materialise else None}
         opt = lambda a: None if a is None else _vp(a)
-        for _ in range(2):  # a second try once out_need is known
-            e = _lib.qh_emit(o["fields"].ctypes.data, o["fields"].size, o["field_start"].ctypes.data,
-                             o["status"].ctypes.data, o["ricnt"].ctypes.data,
-                             o["out"].ctypes.data if materialise else None,
-                             o["out"].size if materialise else 0, o["out_blocks"].ctypes.data, 0, 0, 0)
-            rv = lib.qh_qpack_emit_fields(_vp(src), _vp(blocks), blocks.size, ctypes.byref(st),
-                                          opt(vw), opt(bv), opt(ents), opt(dbytes), opt(sl), nsel,
-                                          EMIT_QIF if qif else 0, ctypes.byref(e))
-            if rv == _lib.QH_ERR_NOMEM and materialise and e.out_need > o["out"].size:
-                o["out"] = np.zeros(int(e.out_need), dtype=np.uint8)
-                continue
-            _lib.check(rv, "qh_qpack_emit_fields")
-            break
+        e = FieldSectionDecoder._emit(
+            Backend(), lambda a: a.ctypes.data, "qh_qpack_emit_fields", o, o["fields"].size, materialise,
+            lambda pe: lib.qh_qpack_emit_fields(_vp(src), _vp(blocks), blocks.size, ctypes.byref(st),
+                                                opt(vw), opt(bv), opt(ents), opt(dbytes), opt(sl), nsel,
+                                                EMIT_QIF if qif else 0, pe))
         return {"fields": o["fields"][:e.nfields], "field_start": o["field_start"],
                 "status": o["status"][:nsel], "ricnt": o["ricnt"][:nsel],
                 "out_blocks": o["out_blocks"][:nsel],
@@ -811,21 +780,12 @@ class FieldSectionDecoder:
                  "out": torch.empty(64, dtype=torch.uint8, device=dev)}
         p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         st = self._sections_struct(res, lambda t: t.data_ptr())
-        for _ in range(2):  # a second try once out_need is known
-            e = _lib.qh_emit(b["fields"].data_ptr(), b["nl"], b["field_start"].data_ptr(),
-                             b["status"].data_ptr(), b["ricnt"].data_ptr(),
-                             b["out"].data_ptr() if materialise else None,
-                             b["out"].numel() if materialise else 0, b["out_blocks"].data_ptr(),
-                             0, 0, 0)
-            rv = lib.qh_emit_fields_batch(self.codec._ctx, p(src), p(blocks), n, ctypes.byref(st),
-                                          p(views), p(block_view), p(entries), p(dyn_bytes), p(sel),
-                                          nsel, EMIT_QIF if qif else 0, ctypes.byref(e),
-                                          _lib.QH_WHERE_DEVICE)
-            if rv == _lib.QH_ERR_NOMEM and materialise and e.out_need > b["out"].numel():
-                b["out"] = torch.empty(int(e.out_need), dtype=torch.uint8, device=dev)
-                continue
-            _lib.check(rv, "qh_emit_fields_batch")
-            break
+        e = self._emit(
+            Backend(dev), lambda t: t.data_ptr(), "qh_emit_fields_batch", b, b["nl"], materialise,
+            lambda pe: lib.qh_emit_fields_batch(self.codec._ctx, p(src), p(blocks), n, ctypes.byref(st),
+                                                p(views), p(block_view), p(entries), p(dyn_bytes),
+                                                p(sel), nsel, EMIT_QIF if qif else 0, pe,
+                                                _lib.QH_WHERE_DEVICE))
         b.update({"nfields": int(e.nfields), "out_need": int(e.out_need),
                   "nblocked": int(e.nblocked)})
         return b
@@ -970,6 +930,11 @@ class DynamicTableSet:
         self._lib = _load()
         self.codec = codec
         self.ntables = int(ntables)
+        if codec is None:
+            be = self._be = Backend()
+        else:
+            be = self._be = Backend("cuda:%d" % codec.device if hasattr(codec, "device") else "cuda",
+                                    codec)
         hm = np.broadcast_to(np.asarray(hard_max, dtype=np.uint64), (self.ntables,))
         views = np.zeros(max(self.ntables, 1), dtype=VIEW_DTYPE)[:self.ntables]
         acct = np.zeros(max(self.ntables, 1), dtype=ACCT_DTYPE)[:self.ntables]
@@ -980,19 +945,8 @@ class DynamicTableSet:
         self.nentries = 0
         self.nbytes = 0
         self._nkeys = 0
-        if codec is None:
-            self.views, self.acct = views.view(np.uint8).copy(), acct.view(np.uint8).copy()
-            self.entries = np.zeros(0, dtype=np.uint8)
-            self.dyn_bytes = np.zeros(0, dtype=np.uint8)
-            self._keys = np.zeros(0, dtype=DYN_KEY_DTYPE)
-        else:
-            import torch
-            self._dev = torch.device("cuda", codec.device) if hasattr(codec, "device") else torch.device("cuda")
-            self.views = torch.from_numpy(views.view(np.uint8).copy()).to(self._dev)
-            self.acct = torch.from_numpy(acct.view(np.uint8).copy()).to(self._dev)
-            self.entries = torch.empty(0, dtype=torch.uint8, device=self._dev)
-            self.dyn_bytes = torch.empty(0, dtype=torch.uint8, device=self._dev)
-            self._keys = torch.empty(0, dtype=torch.uint8, device=self._dev)
+        self.views, self.acct = be.put(views.view(np.uint8).copy()), be.put(acct.view(np.uint8).copy())
+        self.entries, self.dyn_bytes, self._keys = be.empty(0), be.empty(0), be.empty(0)
         self.max_blocked = max_blocked
         if max_blocked is not None:
             mb = np.broadcast_to(np.asarray(max_blocked, dtype=np.uint64), (self.ntables,))
@@ -1003,49 +957,34 @@ class DynamicTableSet:
                 bq[t] = b1[0]
             self.nblks = 0
             self.npend = 0
-            if codec is None:
-                self.bq = bq.view(np.uint8).copy()
-                self.blks = np.zeros(0, dtype=np.uint8)
-                self.pend = np.zeros(0, dtype=np.uint8)
-            else:
-                self.bq = torch.from_numpy(bq.view(np.uint8).copy()).to(self._dev)
-                self.blks = torch.empty(0, dtype=torch.uint8, device=self._dev)
-                self.pend = torch.empty(0, dtype=torch.uint8, device=self._dev)
+            self.bq = be.put(bq.view(np.uint8).copy())
+            self.blks, self.pend = be.empty(0), be.empty(0)
 
-    # -- capacity: the arrays grow by doubling, the log's prefix kept
+    # -- capacity: the arrays grow by cap_for, the log's prefix kept
 
-    def _grow(self, name, have: int, need: int, minimum: int):
-        old = getattr(self, name)
-        size = old.size if isinstance(old, np.ndarray) else old.numel()
-        if need <= size:
-            return
-        cap = max(minimum, size)
-        while cap < need:
-            cap *= 2
-        if isinstance(old, np.ndarray):
-            new = np.zeros(cap, dtype=np.uint8)
-        else:
-            import torch
-            new = torch.empty(cap, dtype=torch.uint8, device=old.device)
-        new[:have] = old[:have]
-        setattr(self, name, new)
+    _grow = grow
 
     def _reserve(self, nentries: int, nbytes: int):
         self._grow("entries", self.nentries * 32, nentries * 32, 4096)
         self._grow("dyn_bytes", self.nbytes, nbytes, 4096)
 
-    def _apply(self, call, what: str):
-        # QH_ERR_NOMEM names the exact need: the arrays grow (by doubling, so
-        # that most calls find room) and the call is made once more
-        for _ in range(2):
+    def _read_encoder(self, src, streams, tsel):
+        be = self._be
+        ptr = be.ptr
+        nsel = self.ntables if tsel is None else be.size(tsel)
+        status = be.empty(max(nsel, 1), np.int32)
+        consumed = be.empty(max(nsel, 1), np.int32)
+
+        def attempt():
             ne, nb = ctypes.c_uint64(self.nentries), ctypes.c_uint64(self.nbytes)
-            rv = call(ne, nb)
-            if rv == _lib.QH_ERR_NOMEM:
-                self._reserve(int(ne.value), int(nb.value))
-                continue
-            break
-        _lib.check(rv, what)
-        self.nentries, self.nbytes = int(ne.value), int(nb.value)
+            rv = be.call(self._lib, "dtables_apply", ptr(src), ptr(streams), be.list_ptr(tsel), nsel,
+                         self.ntables, ptr(self.views), ptr(self.acct), ptr(self.entries),
+                         ctypes.byref(ne), be.size(self.entries) // 32, ptr(self.dyn_bytes),
+                         ctypes.byref(nb), be.size(self.dyn_bytes), ptr(status), ptr(consumed))
+            return rv, (int(ne.value), int(nb.value))
+        _, (self.nentries, self.nbytes) = be.retry("dtables_apply", attempt,
+                                                   lambda needs: self._reserve(*needs))
+        return status[:nsel], consumed[:nsel]
 
     def read_encoder_dev(self, src, streams, tsel=None):
         """Applies encoder-stream bytes on the device: stream p is
@@ -1056,83 +995,43 @@ class DynamicTableSet:
         failing instruction's error (-402, -109), and the bytes of complete,
         applied instructions.  Asynchronous on the codec stream after the
         call's host waits."""
-        import torch
-        nsel = self.ntables if tsel is None else int(tsel.shape[0])
-        status = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
-        consumed = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        # (an empty tensor has no address: an empty table list still has to
-        # be a list, not tsel = NULL's "stream p -> table p")
-        p_tsel = p(status) if tsel is not None and nsel == 0 else p(tsel)
-
-        def call(ne, nb):
-            return self._lib.qh_dtables_apply_batch(
-                self.codec._ctx, p(src), p(streams), p_tsel, nsel, self.ntables, p(self.views),
-                p(self.acct), p(self.entries), ctypes.byref(ne), self.entries.numel() // 32,
-                p(self.dyn_bytes), ctypes.byref(nb), self.dyn_bytes.numel(), p(status), p(consumed),
-                _lib.QH_WHERE_DEVICE)
-        self._apply(call, "qh_dtables_apply_batch")
-        return status[:nsel], consumed[:nsel]
+        assert self.codec is not None
+        return self._read_encoder(src, streams, tsel)
 
     def read_encoder(self, src, streams, tsel=None):
         """The host twin (qh_qpack_dtables_apply) over numpy arrays: src
         uint8, streams SPAN_IN_DTYPE, tsel uint32 or None.  -> (status int32,
         consumed uint32)."""
-        src = _u8(src)
-        streams = np.ascontiguousarray(streams, dtype=SPAN_IN_DTYPE)
-        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
-        nsel = self.ntables if sel is None else sel.size
-        status = np.zeros(max(nsel, 1), dtype=np.int32)
-        consumed = np.zeros(max(nsel, 1), dtype=np.uint32)
+        assert self.codec is None
+        status, consumed = self._read_encoder(_u8(src), _as(streams, SPAN_IN_DTYPE),
+                                              _as(tsel, np.uint32))
+        return status, consumed.view(np.uint32)
 
-        def call(ne, nb):
-            return self._lib.qh_qpack_dtables_apply(
-                _vp(src), _vp(streams), None if sel is None else _vp(sel), nsel, self.ntables,
-                _vp(self.views), _vp(self.acct), _vp(self.entries), ctypes.byref(ne),
-                self.entries.size // 32, _vp(self.dyn_bytes), ctypes.byref(nb), self.dyn_bytes.size,
-                _vp(status), _vp(consumed))
-        self._apply(call, "qh_qpack_dtables_apply")
-        return status[:nsel], consumed[:nsel]
-
-    def _write_decoder(self, dev, emit_result, block_sid, block_view, cancel, dst_cap):
-        if dev:
-            import torch
-            new = lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev)
-            ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-            size = lambda t: 0 if t is None else t.numel()
-            fn, what = self._lib.qh_dec_write_decoder_batch, "qh_dec_write_decoder_batch"
-            head, tail = (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,)
-        else:
-            new = lambda n: np.zeros(n, dtype=np.uint8)
-            ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
-            size = lambda a: 0 if a is None else a.size
-            fn, what = self._lib.qh_qpack_dec_write_decoder, "qh_qpack_dec_write_decoder"
-            head, tail = (), ()
+    def _write_decoder(self, emit_result, block_sid, block_view, cancel, dst_cap):
+        be = self._be
+        ptr = be.ptr
         if getattr(self, "written_icnt", None) is None:
-            self.written_icnt = new(max(self.ntables, 1) * 8)
-        nblocks = size(block_sid)
+            self.written_icnt = be.zeros(max(self.ntables, 1) * 8)
         csid, cview = (None, None) if cancel is None else cancel
-        dstreams = new(max(self.ntables, 1) * 16)
-        cap = getattr(self, "_wd_cap", 256) if dst_cap is None else dst_cap
-        pad = 0 if dst_cap is None else 64  # (tests: sentinel bytes behind a fixed capacity)
-        for _ in range(2):
-            dst = new(cap + pad)
-            if pad:
-                dst[cap:] = 0xA5
+        dstreams = be.zeros(max(self.ntables, 1) * 16)
+        fixed = dst_cap is not None
+        cap, dst = dst_cap if fixed else getattr(self, "_wd_cap", 256), None
+
+        def attempt():
+            nonlocal dst
+            dst = be.room(cap, 64 if fixed else 0)  # (tests: sentinel bytes behind a fixed capacity)
             need = ctypes.c_uint64(0)
-            rv = fn(*head, ptr(block_sid), ptr(block_view), ptr(emit_result["status"]),
-                    ptr(emit_result["ricnt"]), nblocks, ptr(csid), ptr(cview), size(csid),
-                    ptr(self.views), self.ntables, ptr(self.written_icnt), ptr(dst), cap,
-                    ptr(dstreams), ctypes.byref(need), *tail)
-            if rv != _lib.QH_ERR_NOMEM or dst_cap is not None:
-                break
-            while cap < int(need.value):
-                cap *= 2
-            self._wd_cap = cap
-        if dst_cap is None:
-            _lib.check(rv, what)
-        return {"rv": rv, "dst": dst, "dstreams": dstreams[:self.ntables * 16],
-                "dst_need": int(need.value)}
+            rv = be.call(self._lib, "dec_write_decoder", ptr(block_sid), ptr(block_view),
+                         ptr(emit_result["status"]), ptr(emit_result["ricnt"]), be.size(block_sid),
+                         ptr(csid), ptr(cview), be.size(csid), ptr(self.views), self.ntables,
+                         ptr(self.written_icnt), ptr(dst), cap, ptr(dstreams), ctypes.byref(need))
+            return rv, int(need.value)
+
+        def enlarge(need):
+            nonlocal cap
+            cap = self._wd_cap = cap_for(need, cap)
+        rv, need = be.retry("dec_write_decoder", attempt, enlarge, fixed)
+        return {"rv": rv, "dst": dst, "dstreams": dstreams[:self.ntables * 16], "dst_need": need}
 
     def write_decoder(self, emit_result, block_sid, block_view, cancel=None, dst_cap=None):
         """The decoder streams after an ``emit_fields`` call (host form,
@@ -1145,10 +1044,9 @@ class DynamicTableSet:
         dst_cap: a fixed capacity instead of growing (the call's return value
         is then handed back in ``rv``)."""
         assert self.codec is None
-        a = lambda x, d: None if x is None else np.ascontiguousarray(x, dtype=d)
-        er = {"status": a(emit_result["status"], np.int32), "ricnt": a(emit_result["ricnt"], np.uint64)}
-        c = None if cancel is None else (a(cancel[0], np.uint64), a(cancel[1], np.uint32))
-        r = self._write_decoder(False, er, a(block_sid, np.uint64), a(block_view, np.uint32), c, dst_cap)
+        er = {"status": _as(emit_result["status"], np.int32), "ricnt": _as(emit_result["ricnt"], np.uint64)}
+        c = None if cancel is None else (_as(cancel[0], np.uint64), _as(cancel[1], np.uint32))
+        r = self._write_decoder(er, _as(block_sid, np.uint64), _as(block_view, np.uint32), c, dst_cap)
         r["dstreams"] = r["dstreams"].view(SPAN_IN_DTYPE)
         return r
 
@@ -1158,53 +1056,37 @@ class DynamicTableSet:
         = (int64, int32) tensors).  -> dict of tensors (dstreams as bytes).
         One host wait, for the total."""
         assert self.codec is not None
-        return self._write_decoder(True, emit_result, block_sid, block_view, cancel, dst_cap)
+        return self._write_decoder(emit_result, block_sid, block_view, cancel, dst_cap)
 
     # -- blocked sections (max_blocked given): qh_dec_blocked_* / qh_qpack_dec_blocked_*
 
-    def _blk_io(self):
-        """-> (new, ptr, size, head, tail, suffix) of the form the set is in."""
+    def _blocked(self):
         if self.max_blocked is None:
             raise ValueError("the set was made without max_blocked")
-        if self.codec is not None:
-            import torch
-            new = lambda n, d=torch.uint8: torch.zeros(n, dtype=d, device=self._dev)
-            ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-            size = lambda t: 0 if t is None else t.numel()
-            return new, ptr, size, (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,), "_batch"
-        new = lambda n, d=np.uint8: np.zeros(n, dtype=d)
-        ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
-        size = lambda a: 0 if a is None else a.size
-        return new, ptr, size, (), (), ""
+        return self._be
 
     def _push_blocked(self, src, blocks, block_sid, block_view, emit_result, caps):
-        new, ptr, size, head, tail, sfx = self._blk_io()
-        dev = self.codec is not None
-        fn = getattr(self._lib, "qh_dec_blocked_push_batch" if dev else "qh_qpack_dec_blocked_push")
-        nblocks = size(block_sid)
-        if dev:
-            import torch
-            verdict = new(max(nblocks, 1), torch.int32)
-        else:
-            verdict = new(max(nblocks, 1), np.int32)
-        for _ in range(2):
+        be = self._blocked()
+        ptr = be.ptr
+        nblocks = be.size(block_sid)
+        verdict = be.zeros(max(nblocks, 1), np.int32)
+
+        def attempt():
             nr, nb = ctypes.c_uint64(self.nblks), ctypes.c_uint64(self.npend)
-            rcap, bcap = (size(self.blks) // 32, size(self.pend)) if caps is None else caps
-            rv = fn(*head, ptr(src), ptr(blocks), ptr(block_sid), ptr(block_view),
-                    ptr(emit_result["status"]), ptr(emit_result["ricnt"]), nblocks, self.ntables,
-                    ptr(self.bq), ptr(self.blks), ctypes.byref(nr), rcap, ptr(self.pend),
-                    ctypes.byref(nb), bcap, ptr(verdict), *tail)
-            if rv != _lib.QH_ERR_NOMEM or caps is not None:
-                break
-            # the exact needs are known: the arrays grow by doubling, the logs kept
-            self._grow("blks", self.nblks * 32, int(nr.value) * 32, 4096)
-            self._grow("pend", self.npend, int(nb.value), 4096)
-        if caps is None:
-            _lib.check(rv, "qh_dec_blocked_push" + sfx)
+            rcap, bcap = (be.size(self.blks) // 32, be.size(self.pend)) if caps is None else caps
+            rv = be.call(self._lib, "dec_blocked_push", ptr(src), ptr(blocks), ptr(block_sid),
+                         ptr(block_view), ptr(emit_result["status"]), ptr(emit_result["ricnt"]),
+                         nblocks, self.ntables, ptr(self.bq), ptr(self.blks), ctypes.byref(nr), rcap,
+                         ptr(self.pend), ctypes.byref(nb), bcap, ptr(verdict))
+            return rv, (int(nr.value), int(nb.value))
+
+        def enlarge(needs):
+            self._grow("blks", self.nblks * 32, needs[0] * 32, 4096)
+            self._grow("pend", self.npend, needs[1], 4096)
+        rv, (nr, nb) = be.retry("dec_blocked_push", attempt, enlarge, caps is not None)
         if rv == 0:
-            self.nblks, self.npend = int(nr.value), int(nb.value)
-        return {"rv": rv, "verdict": verdict[:nblocks], "nblks": int(nr.value),
-                "npend": int(nb.value)}
+            self.nblks, self.npend = nr, nb
+        return {"rv": rv, "verdict": verdict[:nblocks], "nblks": nr, "npend": nb}
 
     def push_blocked(self, src, blocks, block_sid, block_view, emit_result, caps=None):
         """After ``emit_fields`` (host form, qh_qpack_dec_blocked_push): queues
@@ -1217,10 +1099,9 @@ class DynamicTableSet:
         The logs grow as needed; caps = (records, bytes) fixes the
         capacities instead and hands the call's return value back in rv."""
         assert self.codec is None
-        a = lambda x, d: None if x is None else np.ascontiguousarray(x, dtype=d)
-        er = {"status": a(emit_result["status"], np.int32), "ricnt": a(emit_result["ricnt"], np.uint64)}
-        return self._push_blocked(_u8(src), a(blocks, SPAN_IN_DTYPE), a(block_sid, np.uint64),
-                                  a(block_view, np.uint32), er, caps)
+        er = {"status": _as(emit_result["status"], np.int32), "ricnt": _as(emit_result["ricnt"], np.uint64)}
+        return self._push_blocked(_u8(src), _as(blocks, SPAN_IN_DTYPE), _as(block_sid, np.uint64),
+                                  _as(block_view, np.uint32), er, caps)
 
     def push_blocked_dev(self, src, blocks, block_sid, block_view, emit_result, caps=None):
         """qh_dec_blocked_push_batch: the same over torch tensors in HBM (src
@@ -1229,34 +1110,38 @@ class DynamicTableSet:
         assert self.codec is not None
         return self._push_blocked(src, blocks, block_sid, block_view, emit_result, caps)
 
-    def _release_blocked(self, tsel, rel_cap):
-        new, ptr, size, head, tail, sfx = self._blk_io()
-        dev = self.codec is not None
-        fn = getattr(self._lib,
-                     "qh_dec_blocked_release_batch" if dev else "qh_qpack_dec_blocked_release")
-        nsel = self.ntables if tsel is None else size(tsel)
-        cap = getattr(self, "_rel_cap", 64) if rel_cap is None else rel_cap
-        pad = 0 if rel_cap is None else 4  # (tests: sentinel records behind a fixed capacity)
-        start = new((nsel + 1) * 4)
-        # (an empty list still has to be a list, not tsel = NULL's "all tables")
-        p_tsel = ptr(start) if tsel is not None and nsel == 0 else ptr(tsel)
-        for _ in range(2):
-            o = {"blocks": new((cap + pad) * 16), "sid": new((cap + pad) * 8),
-                 "view": new((cap + pad) * 4), "ricnt": new((cap + pad) * 8)}
-            for a in o.values():  # (sentinel bytes behind a fixed capacity)
-                a[a.shape[0] // (cap + pad) * cap:] = 0xA5
+    _RELEASED = (("blocks", 16), ("sid", 8), ("view", 4), ("ricnt", 8))  # (bytes per record)
+
+    def _release_blocked(self, tsel, rel_cap, dtypes):
+        """-> the result dict: blocks, sid, view, ricnt and start viewed in
+        `dtypes`, the whole byte arrays kept as <name>_raw."""
+        be = self._blocked()
+        ptr = be.ptr
+        nsel = self.ntables if tsel is None else be.size(tsel)
+        fixed = rel_cap is not None
+        cap = rel_cap if fixed else getattr(self, "_rel_cap", 64)
+        start = be.zeros((nsel + 1) * 4)
+        o = {}
+
+        def attempt():
+            # (tests: sentinel records behind a fixed capacity)
+            o.update({k: be.room(cap, 4 if fixed else 0, w) for k, w in self._RELEASED})
             need = ctypes.c_uint64(0)
-            rv = fn(*head, p_tsel, nsel, self.ntables, ptr(self.views), ptr(self.bq), ptr(self.blks),
-                    self.nblks, ptr(o["blocks"]), ptr(o["sid"]), ptr(o["view"]), ptr(o["ricnt"]),
-                    ptr(start), ctypes.byref(need), cap, *tail)
-            if rv != _lib.QH_ERR_NOMEM or rel_cap is not None:
-                break
-            while cap < int(need.value):
-                cap *= 2
-            self._rel_cap = cap
-        if rel_cap is None:
-            _lib.check(rv, "qh_dec_blocked_release" + sfx)
-        o.update({"rv": rv, "start": start, "nreleased": int(need.value), "cap": cap})
+            rv = be.call(self._lib, "dec_blocked_release", be.list_ptr(tsel), nsel, self.ntables,
+                         ptr(self.views), ptr(self.bq), ptr(self.blks), self.nblks, ptr(o["blocks"]),
+                         ptr(o["sid"]), ptr(o["view"]), ptr(o["ricnt"]), ptr(start),
+                         ctypes.byref(need), cap)
+            return rv, int(need.value)
+
+        def enlarge(need):
+            nonlocal cap
+            cap = self._rel_cap = cap_for(need, cap)
+        rv, need = be.retry("dec_blocked_release", attempt, enlarge, fixed)
+        n = need if rv == 0 else 0
+        for (k, w), d in zip(self._RELEASED, dtypes):
+            o[k + "_raw"] = o[k]
+            o[k] = o[k][:n * w].view(d)
+        o.update({"rv": rv, "start": start.view(dtypes[-1]), "nreleased": need, "cap": cap})
         return o
 
     def release_blocked(self, tsel=None, rel_cap=None):
@@ -1270,15 +1155,8 @@ class DynamicTableSet:
         ``pend``, sid / view into write_decoder.  rel_cap: a fixed capacity
         instead of growing."""
         assert self.codec is None
-        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
-        o = self._release_blocked(sel, rel_cap)
-        n = o["nreleased"] if o["rv"] == 0 else 0
-        for k, d in (("blocks", SPAN_IN_DTYPE), ("sid", np.uint64), ("view", np.uint32),
-                     ("ricnt", np.uint64)):
-            o[k + "_raw"] = o[k]
-            o[k] = o[k].view(d)[:n]
-        o["start"] = o["start"].view(np.uint32)
-        return o
+        return self._release_blocked(_as(tsel, np.uint32), rel_cap,
+                                     (SPAN_IN_DTYPE, np.uint64, np.uint32, np.uint64, np.uint32))
 
     def release_blocked_dev(self, tsel=None, rel_cap=None):
         """qh_dec_blocked_release_batch: the same on the device (tsel int32 or
@@ -1286,14 +1164,9 @@ class DynamicTableSet:
         ricnt int64, start int32 [nsel + 1]; nreleased, rv.  One host wait."""
         import torch
         assert self.codec is not None
-        o = self._release_blocked(tsel, rel_cap)
-        n = o["nreleased"] if o["rv"] == 0 else 0
-        for k, d in (("blocks", torch.int64), ("sid", torch.int64), ("view", torch.int32),
-                     ("ricnt", torch.int64)):
-            o[k + "_raw"] = o[k]
-            o[k] = o[k].view(d)[:n * (2 if k == "blocks" else 1)]
+        o = self._release_blocked(tsel, rel_cap,
+                                  (torch.int64, torch.int64, torch.int32, torch.int64, torch.int32))
         o["blocks"] = o["blocks"].reshape(-1, 2)
-        o["start"] = o["start"].view(torch.int32)
         return o
 
     @staticmethod
@@ -1313,13 +1186,12 @@ class DynamicTableSet:
         return torch.where(bad, torch.full_like(st, QH_ERR_QPACK_DECOMPRESSION_FAILED), st)
 
     def _cancel_blocked(self, sid, view):
-        new, ptr, size, head, tail, sfx = self._blk_io()
-        dev = self.codec is not None
-        fn = getattr(self._lib, "qh_dec_blocked_cancel_batch" if dev else "qh_qpack_dec_blocked_cancel")
-        n = size(sid)
-        removed = new(max(n, 1))
-        rv = fn(*head, ptr(sid), ptr(view), n, self.ntables, ptr(self.bq), ptr(self.blks), self.nblks,
-                ptr(removed), *tail)
+        be = self._blocked()
+        ptr = be.ptr
+        n = be.size(sid)
+        removed = be.zeros(max(n, 1))
+        rv = be.call(self._lib, "dec_blocked_cancel", ptr(sid), ptr(view), n, self.ntables, ptr(self.bq),
+                     ptr(self.blks), self.nblks, ptr(removed))
         return rv, removed[:n]
 
     def cancel_blocked(self, cancel_sid, cancel_view, check=True):
@@ -1330,7 +1202,7 @@ class DynamicTableSet:
         rv, removed = self._cancel_blocked(np.ascontiguousarray(cancel_sid, dtype=np.uint64),
                                            np.ascontiguousarray(cancel_view, dtype=np.uint32))
         if check:
-            _lib.check(rv, "qh_qpack_dec_blocked_cancel")
+            self._be.check(rv, "dec_blocked_cancel")
             return removed
         return rv, removed
 
@@ -1340,45 +1212,35 @@ class DynamicTableSet:
         out of range, which remove nothing."""
         assert self.codec is not None
         rv, removed = self._cancel_blocked(cancel_sid, cancel_view)
-        _lib.check(rv, "qh_dec_blocked_cancel_batch")
+        self._be.check(rv, "dec_blocked_cancel")
         return removed
+
+    _LOG_ROOMS = ((32, 128), (1, 4096))  # (records of 32 bytes, bytes: 4096 bytes at the least)
 
     def compact_blocked(self):
         """Replaces ``blks`` and ``pend`` by logs that hold the queued records
         of every table alone, back to back in table order, ``bq`` rebased.
         When to call is the caller's decision: compare ``nblks`` and ``npend``
         with what is queued.  A failed call leaves the object as it was."""
-        new, ptr, size, head, tail, sfx = self._blk_io()
-        dev = self.codec is not None
-        fn = getattr(self._lib,
-                     "qh_dec_blocked_compact_batch" if dev else "qh_qpack_dec_blocked_compact")
-        bq = self.bq.clone() if dev else self.bq.copy()
+        be = self._blocked()
+        ptr = be.ptr
+        bq = be.own(self.bq)
 
-        def call(q, recs, byts):
+        def call(outs):
+            recs, byts = outs
             nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            rv = fn(*head, None, self.ntables, self.ntables, ptr(q), ptr(self.blks), self.nblks,
-                    ptr(self.pend), self.npend, ptr(recs), ctypes.byref(nr), size(recs) // 32,
-                    ptr(byts), ctypes.byref(nb), size(byts), *tail)
-            return rv, int(nr.value), int(nb.value)
-        rv, nr, nb = call(bq, None, None)  # the sizing call
-        if rv != _lib.QH_ERR_NOMEM:
-            _lib.check(rv, "qh_dec_blocked_compact" + sfx)
-        caps = []
-        for need in (nr * 32, nb):
-            cap = 4096
-            while cap < need:
-                cap *= 2
-            caps.append(cap)
-        recs, byts = new(caps[0]), new(caps[1])
-        rv, nr, nb = call(bq, recs, byts)
-        _lib.check(rv, "qh_dec_blocked_compact" + sfx)
+            rv = be.call(self._lib, "dec_blocked_compact", None, self.ntables, self.ntables, ptr(bq),
+                         ptr(self.blks), self.nblks, ptr(self.pend), self.npend, ptr(recs),
+                         ctypes.byref(nr), be.size(recs) // 32, ptr(byts), ctypes.byref(nb),
+                         be.size(byts))
+            return rv, (int(nr.value), int(nb.value))
+        (recs, byts), (nr, nb) = be.sized("dec_blocked_compact", call, self._LOG_ROOMS, be.zeros)
         self.bq, self.blks, self.pend, self.nblks, self.npend = bq, recs, byts, nr, nb
 
     def blocked_records(self):
         """-> (bq DEC_BLKS_DTYPE [ntables], blks DEC_BLK_DTYPE [nblks], pend
         uint8 [npend]): host copies of the queue state."""
-        self._blk_io()
-        h = (lambda a: a.copy()) if self.codec is None else (lambda t: t.cpu().numpy())
+        h = self._blocked().host
         return (h(self.bq).view(DEC_BLKS_DTYPE), h(self.blks[:self.nblks * 32]).view(DEC_BLK_DTYPE),
                 h(self.pend[:self.npend]))
 
@@ -1395,78 +1257,47 @@ class DynamicTableSet:
         arrays taken before the call stay valid together.  When to call is the
         caller's decision: compare ``nentries`` and ``nbytes`` with what the
         tables can hold.  A failed call leaves the object as it was."""
-        nt = self.ntables
-        dev = self.codec is not None
-        if dev:
-            import torch
-            parts = [self.views] if extra_views is None else \
-                [self.views, extra_views.reshape(-1).view(torch.uint8)]
-            views = torch.cat(parts) if len(parts) > 1 else self.views.clone()
-            nv = views.numel() // VIEW_DTYPE.itemsize
-            status = torch.empty(max(nv, 1), dtype=torch.int32, device=self._dev)
-            new = lambda n: torch.empty(n, dtype=torch.uint8, device=self._dev)
-            size = lambda t: t.numel()
-            p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-            fn, what = self._lib.qh_dtables_compact_batch, "qh_dtables_compact_batch"
-            head, tail = (self.codec._ctx,), (_lib.QH_WHERE_DEVICE,)
+        be = self._be
+        ptr = be.ptr
+        if extra_views is None:
+            views = be.own(self.views)
+        elif be.dev:
+            views = be.torch.cat([self.views, extra_views.reshape(-1).view(be.torch.uint8)])
         else:
-            extra = None if extra_views is None else \
-                np.ascontiguousarray(extra_views).view(np.uint8).reshape(-1)
-            views = self.views.copy() if extra is None else np.concatenate([self.views, extra])
-            nv = views.size // VIEW_DTYPE.itemsize
-            status = np.zeros(max(nv, 1), dtype=np.int32)
-            new = lambda n: np.zeros(n, dtype=np.uint8)
-            size = lambda a: a.size
-            p = lambda a: None if a is None or a.size == 0 else _vp(a)
-            fn, what = self._lib.qh_qpack_dtables_compact, "qh_qpack_dtables_compact"
-            head, tail = (), ()
+            views = np.concatenate([self.views,
+                                    np.ascontiguousarray(extra_views).view(np.uint8).reshape(-1)])
+        nv = be.size(views) // VIEW_DTYPE.itemsize
+        status = be.empty(max(nv, 1), np.int32)
 
-        def call(ents, byts):
+        def call(outs):
+            ents, byts = outs
             ne, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            rv = fn(*head, nv, p(views), p(self.entries), self.nentries, p(self.dyn_bytes), self.nbytes,
-                    p(ents), ctypes.byref(ne), 0 if ents is None else size(ents) // 32,
-                    p(byts), ctypes.byref(nb), 0 if byts is None else size(byts), p(status), *tail)
-            return rv, int(ne.value), int(nb.value)
-        rv, ne, nb = call(None, None)  # the sizing call
-        if rv != _lib.QH_ERR_NOMEM:
-            _lib.check(rv, what)  # (0: nothing is live; the arrays are still replaced)
-        # fresh arrays by the growth rule of _grow, so that the next
-        # read_encoder finds room
-        caps = []
-        for need in (ne * 32, nb):
-            cap = 4096
-            while cap < need:
-                cap *= 2
-            caps.append(cap)
-        ents, byts = new(caps[0]), new(caps[1])
-        rv, ne, nb = call(ents, byts)
-        _lib.check(rv, what)
-        own = lambda a: a.clone() if dev else a.copy()
-        self.views = views if extra_views is None else own(views[:nt * VIEW_DTYPE.itemsize])
+            rv = be.call(self._lib, "dtables_compact", nv, ptr(views), ptr(self.entries), self.nentries,
+                         ptr(self.dyn_bytes), self.nbytes, ptr(ents), ctypes.byref(ne),
+                         be.size(ents) // 32, ptr(byts), ctypes.byref(nb), be.size(byts), ptr(status))
+            return rv, (int(ne.value), int(nb.value))
+        (ents, byts), (ne, nb) = be.sized("dtables_compact", call, self._LOG_ROOMS, be.empty)
+        own = self.ntables * VIEW_DTYPE.itemsize
+        self.views = views if extra_views is None else be.own(views[:own])
         self.entries, self.dyn_bytes, self.nentries, self.nbytes = ents, byts, ne, nb
         self._nkeys = 0  # (keys depend on content alone: keys() computes them over the new log)
-        if not dev:
-            self._keys = np.zeros(0, dtype=DYN_KEY_DTYPE)
-        return None if extra_views is None else own(views[nt * VIEW_DTYPE.itemsize:])
+        if not be.dev:
+            self._keys = be.empty(0)  # (an array handed out by keys() before stays as it was)
+        return None if extra_views is None else be.own(views[own:])
 
     def keys(self):
         """The log's keys (DYN_KEY_DTYPE records; a uint8 tensor of nentries *
         16 bytes on the device), extended over the tail appended since the
         last call (qh_dyn_keys_batch / qh_qpack_dyn_keys)."""
-        n = self.nentries
-        if self.codec is None:
-            if n > self._nkeys:
-                ents = self.entries[:n * 32].view(DYN_ENTRY_DTYPE)
-                self._keys = dyn_keys(ents, self.dyn_bytes[:self.nbytes], first=self._nkeys,
-                                      keys=self._keys)
-                self._nkeys = n
-            return self._keys
+        n, be = self.nentries, self._be
+        ptr = be.ptr
         self._grow("_keys", self._nkeys * 16, n * 16, 4096)
         if n > self._nkeys:
-            dyn_keys_dev(self.codec, self.entries, n, self.dyn_bytes, self.nbytes, self._nkeys,
-                         n - self._nkeys, self._keys)
+            be.check(be.call(self._lib, "dyn_keys", ptr(self.entries), n, ptr(self.dyn_bytes),
+                             self.nbytes, self._nkeys, n - self._nkeys, ptr(self._keys)), "dyn_keys")
             self._nkeys = n
-        return self._keys[:n * 16]
+        keys = self._keys[:n * 16]
+        return keys if be.dev else keys.view(DYN_KEY_DTYPE)
 
 
 class EncoderSet:
@@ -1510,37 +1341,23 @@ class EncoderSet:
         self.nentries = 0
         self.nbytes = 0
         self.device = device
+        be = self._be = Backend(None if device is None else "cuda:%d" % int(device))
         arrays = {"views": views, "acct": acct, "enc": enc}
         if refs:  # (a fresh connection's record is all zeros: qh_enc_refs_init)
             arrays["rv"] = np.zeros(max(self.n, 1), dtype=ENC_REFS_DTYPE)[:self.n]
             arrays["refs"] = np.zeros(0, dtype=ENC_REF_DTYPE)
-        if device is None:
-            for k, a in arrays.items():
-                setattr(self, k, a.view(np.uint8).copy())
-            for k in ("entries", "dyn_bytes", "keys"):
-                setattr(self, k, np.zeros(0, dtype=np.uint8))
-        else:
-            import torch
-            self._dev = torch.device("cuda", int(device))
-            for k, a in arrays.items():
-                setattr(self, k, torch.from_numpy(a.view(np.uint8).copy()).to(self._dev))
-            for k in ("entries", "dyn_bytes", "keys"):
-                setattr(self, k, torch.empty(0, dtype=torch.uint8, device=self._dev))
+        for k, a in arrays.items():
+            setattr(self, k, be.put(a.view(np.uint8).copy()))
+        for k in ("entries", "dyn_bytes", "keys"):
+            setattr(self, k, be.empty(0))
 
     # -- state access (numpy copies; the device form copies through the host)
 
     def _host(self, name, dtype):
-        a = getattr(self, name)
-        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        return a.view(dtype).copy()
+        return self._be.host(getattr(self, name)).view(dtype)
 
     def _store(self, name, recs):
-        raw = np.ascontiguousarray(recs).view(np.uint8).reshape(-1).copy()
-        if self.device is None:
-            setattr(self, name, raw)
-        else:
-            import torch
-            setattr(self, name, torch.from_numpy(raw).to(self._dev))
+        setattr(self, name, self._be.put(np.ascontiguousarray(recs).view(np.uint8).reshape(-1).copy()))
 
     def view_records(self):
         return self._host("views", VIEW_DTYPE)
@@ -1574,13 +1391,15 @@ class EncoderSet:
         self._store("acct", acct)
         self._store("enc", enc)
 
-    _grow = DynamicTableSet._grow
+    _grow = grow
 
-    def _call(self, fn, head, tail, ptr, size, new, plain, strs, nfields, nvflags, field_start,
-              nsections, sec_flags, conn_start, nconns, tsel, caps=None):
+    def _call(self, codec, plain, strs, nfields, nvflags, field_start, nsections, sec_flags,
+              conn_start, nconns, tsel, caps=None):
         """One call, grown and repeated on QH_ERR_NOMEM (`caps`: fixed
         (entries, bytes, dst, edst) capacities instead, for tests; the call is
         then made once and its return value and needs handed back)."""
+        be = self._be
+        ptr, new = be.ptr, be.zeros
         lines = new(max(nfields, 1) * 24)
         prefixes = new(max(nsections, 1) * 24)
         mx, mn = new(max(nsections, 1) * 8), new(max(nsections, 1) * 8)
@@ -1589,10 +1408,10 @@ class EncoderSet:
         status = new(max(nconns, 1) * 4)
         # (the output buffers start at the sizes the last call needed)
         dst_cap, edst_cap = getattr(self, "_out_caps", (4096, 4096))
-        pad = 0
-        if caps is not None:
+        fixed = caps is not None
+        pad = 64 if fixed else 0
+        if fixed:
             # exactly the given room, with 64 sentinel bytes (0xA5) behind it
-            pad = 64
             for name, have, cap in (("entries", self.nentries * 32, caps[0] * 32),
                                     ("keys", self.nentries * 16, caps[0] * 16),
                                     ("dyn_bytes", self.nbytes, caps[1])):
@@ -1601,112 +1420,86 @@ class EncoderSet:
                 a[:have] = getattr(self, name)[:have]
                 setattr(self, name, a)
             dst_cap, edst_cap = caps[2], caps[3]
-        for _ in range(3):
-            dst, edst = new(dst_cap + pad), new(edst_cap + pad)
-            if pad:
-                dst[:] = 0xA5
-                edst[:] = 0xA5
+        dst = edst = None
+
+        def attempt():
+            nonlocal dst, edst
+            dst, edst = be.room(dst_cap, pad), be.room(edst_cap, pad)
             ne, nb = ctypes.c_uint64(self.nentries), ctypes.c_uint64(self.nbytes)
             dn, en = ctypes.c_uint64(0), ctypes.c_uint64(0)
-            ecap = min(size(self.entries) // 32, size(self.keys) // 16) if caps is None else caps[0]
-            bcap = size(self.dyn_bytes) if caps is None else caps[1]
-            rv = fn(*head, ptr(plain), ptr(strs), nfields, ptr(nvflags), ptr(field_start), nsections,
-                    ptr(sec_flags), ptr(conn_start), nconns, ptr(tsel), self.n, ptr(self.views),
-                    ptr(self.acct), ptr(self.enc), ptr(self.entries), ctypes.byref(ne), ecap,
-                    ptr(self.dyn_bytes), ctypes.byref(nb), bcap, ptr(self.keys), ptr(lines),
-                    ptr(prefixes), ptr(mx), ptr(mn), ptr(dst), dst_cap, ptr(sections),
-                    ctypes.byref(dn), ptr(edst), edst_cap, ptr(estreams), ctypes.byref(en),
-                    ptr(status), *tail)
-            needs = (int(ne.value), int(nb.value), int(dn.value), int(en.value))
-            if rv != _lib.QH_ERR_NOMEM or caps is not None:
-                break
+            ecap = caps[0] if fixed else min(be.size(self.entries) // 32, be.size(self.keys) // 16)
+            bcap = caps[1] if fixed else be.size(self.dyn_bytes)
+            rv = be.call(self._lib, "encode_conns", ptr(plain), ptr(strs), nfields, ptr(nvflags),
+                         ptr(field_start), nsections, ptr(sec_flags), ptr(conn_start), nconns,
+                         be.list_ptr(tsel), self.n, ptr(self.views), ptr(self.acct), ptr(self.enc),
+                         ptr(self.entries), ctypes.byref(ne), ecap, ptr(self.dyn_bytes),
+                         ctypes.byref(nb), bcap, ptr(self.keys), ptr(lines), ptr(prefixes), ptr(mx),
+                         ptr(mn), ptr(dst), dst_cap, ptr(sections), ctypes.byref(dn), ptr(edst),
+                         edst_cap, ptr(estreams), ctypes.byref(en), ptr(status), codec=codec)
+            return rv, (int(ne.value), int(nb.value), int(dn.value), int(en.value))
+
+        def enlarge(needs):
+            nonlocal dst_cap, edst_cap
             self._grow("entries", self.nentries * 32, needs[0] * 32, 4096)
             self._grow("keys", self.nentries * 16, needs[0] * 16, 2048)
             self._grow("dyn_bytes", self.nbytes, needs[1], 4096)
-            while dst_cap < needs[2]:
-                dst_cap *= 2
-            while edst_cap < needs[3]:
-                edst_cap *= 2
+            dst_cap, edst_cap = cap_for(needs[2], dst_cap), cap_for(needs[3], edst_cap)
             self._out_caps = (dst_cap, edst_cap)
-        res = {"rv": rv, "needs": needs, "lines": lines, "prefixes": prefixes, "max_cnt": mx,
-               "min_cnt": mn, "dst": dst, "sections": sections, "edst": edst, "estreams": estreams,
-               "status": status, "nfields": nfields, "nsections": nsections, "nconns": nconns}
-        if caps is not None:
-            if rv == 0:
-                self.nentries, self.nbytes = needs[0], needs[1]
-            return res
-        _lib.check(rv, fn.__name__)
-        self.nentries, self.nbytes = needs[0], needs[1]
-        return res
+        rv, needs = be.retry("encode_conns", attempt, enlarge, fixed, tries=3)
+        if rv == 0:
+            self.nentries, self.nbytes = needs[0], needs[1]
+        return {"rv": rv, "needs": needs, "lines": lines, "prefixes": prefixes, "max_cnt": mx,
+                "min_cnt": mn, "dst": dst, "sections": sections, "edst": edst, "estreams": estreams,
+                "status": status, "nfields": nfields, "nsections": nsections, "nconns": nconns}
 
     # -- acknowledgements (refs=True): the calls of csrc/qh_ack.c / qh_ack.inc
-
-    def _ack_fns(self, codec):
-        """-> (prefix args, suffix args, pointer of, new byte array) of the
-        host twins (codec None) or the device calls."""
-        if codec is None:
-            assert self.device is None
-            return (), (), (lambda a: None if a is None or a.size == 0 else _vp(a)), \
-                (lambda n: np.zeros(n, dtype=np.uint8))
-        import torch
-        assert self.device is not None
-        return (codec._ctx,), (_lib.QH_WHERE_DEVICE,), \
-            (lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())), \
-            (lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev))
-
-    @staticmethod
-    def _size(a):
-        return a.size if isinstance(a, np.ndarray) else a.numel()
 
     def _sec_flags(self, codec, sids, conn_start, nsections, nconns, tsel):
         """qh_qpack_enc_sec_flags / qh_enc_sec_flags_batch -> (sec_flags uint8,
         status int32 as bytes), arrays of the object's kind."""
-        head, tail, ptr, new = self._ack_fns(codec)
-        fn = self._lib.qh_qpack_enc_sec_flags if codec is None else self._lib.qh_enc_sec_flags_batch
-        flags, status = new(max(nsections, 1)), new(max(nconns, 1) * 4)
-        rv = fn(*head, ptr(sids), nsections, ptr(conn_start), nconns, ptr(tsel), self.n,
-                ptr(self.enc), ptr(self.rv), ptr(self.refs), self.nrefs, ptr(flags), ptr(status),
-                *tail)
-        _lib.check(rv, "qh_enc_sec_flags")
+        be = self._be
+        ptr = be.ptr
+        flags, status = be.zeros(max(nsections, 1)), be.zeros(max(nconns, 1) * 4)
+        rv = be.call(self._lib, "enc_sec_flags", ptr(sids), nsections, ptr(conn_start), nconns,
+                     be.list_ptr(tsel), self.n, ptr(self.enc), ptr(self.rv), ptr(self.refs),
+                     self.nrefs, ptr(flags), ptr(status), codec=codec)
+        be.check(rv, "enc_sec_flags")
         return flags[:nsections], status
 
     def _record(self, codec, sids, conn_start, nsections, nconns, tsel, r, refs_cap=None):
         """qh_qpack_enc_refs_record / qh_enc_refs_record_batch after an encode
         call with result r; the log grows on QH_ERR_NOMEM (refs_cap: a fixed
-        capacity instead, for tests: -> the call's return value)."""
-        head, tail, ptr, _ = self._ack_fns(codec)
-        fn = self._lib.qh_qpack_enc_refs_record if codec is None else \
-            self._lib.qh_enc_refs_record_batch
-        for _ in range(2):
-            nr = ctypes.c_uint64(self.nrefs)
-            cap = self._size(self.refs) // 32 if refs_cap is None else refs_cap
-            rv = fn(*head, ptr(sids), nsections, ptr(conn_start), nconns, ptr(tsel), self.n,
-                    ptr(r["max_cnt"]), ptr(r["min_cnt"]), ptr(r["status"]), ptr(self.enc),
-                    ptr(self.rv), ptr(self.refs), ctypes.byref(nr), cap, *tail)
-            if rv != _lib.QH_ERR_NOMEM or refs_cap is not None:
-                break
-            self._grow("refs", self.nrefs * 32, int(nr.value) * 32, 4096)
-        if refs_cap is not None:
-            if rv == 0:
-                self.nrefs = int(nr.value)
-            return rv, int(nr.value)
-        _lib.check(rv, "qh_enc_refs_record")
-        self.nrefs = int(nr.value)
-        return rv, self.nrefs
+        capacity instead, for tests).  -> (the call's return value, nrefs)."""
+        be = self._be
+        ptr = be.ptr
 
-    def _with_stream_ids(self, codec, call, sids, conn_start, nsections, nconns, tsel, sec_flags):
-        if sids is None:
-            return call(sec_flags)
-        if sec_flags is not None:
-            raise ValueError("pass stream_ids or sec_flags, not both")
-        if not self.has_refs:
-            raise ValueError("stream_ids needs an EncoderSet made with refs=True")
-        flags, st = self._sec_flags(codec, sids, conn_start, nsections, nconns, tsel)
-        r = call(flags)
-        r["sec_flags"], r["sec_status"] = flags, st
-        if r["rv"] == 0:
-            self._record(codec, sids, conn_start, nsections, nconns, tsel, r)
-        return r
+        def attempt():
+            nr = ctypes.c_uint64(self.nrefs)
+            cap = be.size(self.refs) // 32 if refs_cap is None else refs_cap
+            rv = be.call(self._lib, "enc_refs_record", ptr(sids), nsections, ptr(conn_start), nconns,
+                         be.list_ptr(tsel), self.n, ptr(r["max_cnt"]), ptr(r["min_cnt"]),
+                         ptr(r["status"]), ptr(self.enc), ptr(self.rv), ptr(self.refs),
+                         ctypes.byref(nr), cap, codec=codec)
+            return rv, int(nr.value)
+        rv, nr = be.retry("enc_refs_record", attempt,
+                          lambda need: self._grow("refs", self.nrefs * 32, need * 32, 4096),
+                          refs_cap is not None)
+        if rv == 0:
+            self.nrefs = nr
+        return rv, nr
+
+    def _read_decoder(self, codec, src, streams, tsel):
+        assert self.has_refs
+        be = self._be
+        ptr = be.ptr
+        nsel = self.n if tsel is None else be.size(tsel)
+        status = be.empty(max(nsel, 1), np.int32)
+        consumed = be.empty(max(nsel, 1), np.int32)
+        rv = be.call(self._lib, "enc_read_decoder", ptr(src), ptr(streams), be.list_ptr(tsel), nsel,
+                     self.n, ptr(self.views), ptr(self.enc), ptr(self.rv), ptr(self.refs), self.nrefs,
+                     ptr(status), ptr(consumed), codec=codec)
+        be.check(rv, "enc_read_decoder")
+        return status[:nsel], consumed[:nsel]
 
     def read_decoder(self, src, streams, tsel=None):
         """Decoder-stream bytes applied on the host (qh_qpack_enc_read_decoder):
@@ -1715,38 +1508,16 @@ class EncoderSet:
         -> (status int32, consumed uint32): per stream 0 or the first failing
         instruction's error (-403; -108 once the connection is bad), and the
         bytes of complete, applied instructions."""
-        assert self.device is None and self.has_refs
-        src = _u8(src)
-        streams = np.ascontiguousarray(streams, dtype=SPAN_IN_DTYPE)
-        sel = None if tsel is None else np.ascontiguousarray(tsel, dtype=np.uint32)
-        nsel = self.n if sel is None else sel.size
-        status = np.zeros(max(nsel, 1), dtype=np.int32)
-        consumed = np.zeros(max(nsel, 1), dtype=np.uint32)
-        p_sel = None if sel is None else _vp(sel if sel.size else np.zeros(1, np.uint32))
-        ptr = lambda a: None if a.size == 0 else _vp(a)
-        rv = self._lib.qh_qpack_enc_read_decoder(
-            _vp(src), _vp(streams), p_sel, nsel, self.n, ptr(self.views), ptr(self.enc),
-            ptr(self.rv), ptr(self.refs), self.nrefs, _vp(status), _vp(consumed))
-        _lib.check(rv, "qh_qpack_enc_read_decoder")
-        return status[:nsel], consumed[:nsel]
+        status, consumed = self._read_decoder(None, _u8(src), _as(streams, SPAN_IN_DTYPE),
+                                              _as(tsel, np.uint32))
+        return status, consumed.view(np.uint32)
 
     def read_decoder_dev(self, codec: HuffmanBatchCodec, src, streams, tsel=None):
         """qh_enc_read_decoder_batch: the same over torch tensors in HBM (src
         uint8, streams int64 [nsel, 2] as SPAN_IN_DTYPE records, tsel int32).
         -> (status int32, consumed int32) tensors.  Asynchronous on the codec
         stream, no host wait."""
-        import torch
-        assert self.device is not None and self.has_refs
-        nsel = self.n if tsel is None else int(tsel.shape[0])
-        status = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
-        consumed = torch.empty(max(nsel, 1), dtype=torch.int32, device=self._dev)
-        p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-        p_tsel = p(status) if tsel is not None and nsel == 0 else p(tsel)
-        rv = self._lib.qh_enc_read_decoder_batch(
-            codec._ctx, p(src), p(streams), p_tsel, nsel, self.n, p(self.views), p(self.enc),
-            p(self.rv), p(self.refs), self.nrefs, p(status), p(consumed), _lib.QH_WHERE_DEVICE)
-        _lib.check(rv, "qh_enc_read_decoder_batch")
-        return status[:nsel], consumed[:nsel]
+        return self._read_decoder(codec, src, streams, tsel)
 
     def refs_records(self):
         """-> (rv ENC_REFS_DTYPE [n], refs ENC_REF_DTYPE [nrefs]), numpy copies:
@@ -1761,22 +1532,36 @@ class EncoderSet:
         (qh_qpack_enc_refs_compact; with the device form's codec
         qh_enc_refs_compact_batch)."""
         assert self.has_refs
-        head, tail, ptr, new = self._ack_fns(codec)
-        fn = self._lib.qh_qpack_enc_refs_compact if codec is None else \
-            self._lib.qh_enc_refs_compact_batch
-        nr = ctypes.c_uint64(0)
-        rv = fn(*head, None, self.n, self.n, ptr(self.rv), ptr(self.refs), self.nrefs, None,
-                ctypes.byref(nr), 0, *tail)  # the sizing call
-        if rv != _lib.QH_ERR_NOMEM:
-            _lib.check(rv, "qh_enc_refs_compact")
-        cap = 128
-        while cap < int(nr.value):
-            cap *= 2
-        out = new(cap * 32)
-        rv = fn(*head, None, self.n, self.n, ptr(self.rv), ptr(self.refs), self.nrefs, ptr(out),
-                ctypes.byref(nr), cap, *tail)
-        _lib.check(rv, "qh_enc_refs_compact")
-        self.refs, self.nrefs = out, int(nr.value)
+        be = self._be
+        ptr = be.ptr
+
+        def call(outs):
+            nr = ctypes.c_uint64(0)
+            rv = be.call(self._lib, "enc_refs_compact", None, self.n, self.n, ptr(self.rv),
+                         ptr(self.refs), self.nrefs, ptr(outs[0]), ctypes.byref(nr),
+                         be.size(outs[0]) // 32, codec=codec)
+            return rv, (int(nr.value),)
+        (self.refs,), (self.nrefs,) = be.sized("enc_refs_compact", call, ((32, 128),), be.zeros)
+
+    def _encode(self, codec, plain, strs, field_start, conn_start, nvflags, sec_flags, tsel, caps, sids):
+        """sec-flags -> encode -> record with stream ids, the encode call alone
+        without; arrays of the object's kind in and out."""
+        nfields, nsections = int(strs.shape[0]) // 2, int(field_start.shape[0]) - 1
+        nconns = int(conn_start.shape[0]) - 1
+        call = lambda flags: self._call(codec, plain, strs, nfields, nvflags, field_start, nsections,
+                                        flags, conn_start, nconns, tsel, caps)
+        if sids is None:
+            return call(sec_flags)
+        if sec_flags is not None:
+            raise ValueError("pass stream_ids or sec_flags, not both")
+        if not self.has_refs:
+            raise ValueError("stream_ids needs an EncoderSet made with refs=True")
+        flags, st = self._sec_flags(codec, sids, conn_start, nsections, nconns, tsel)
+        r = call(flags)
+        r["sec_flags"], r["sec_status"] = flags, st
+        if r["rv"] == 0:
+            self._record(codec, sids, conn_start, nsections, nconns, tsel, r)
+        return r
 
     def encode(self, plain, strs, field_start, conn_start, nvflags=None, sec_flags=None, tsel=None,
                caps=None, stream_ids=None):
@@ -1792,25 +1577,9 @@ class EncoderSet:
         result gains sec_flags and sec_status) and the call's references are
         recorded after it (qh_qpack_enc_refs_record)."""
         assert self.device is None
-        plain = _u8(plain)
-        strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
-        fs = np.ascontiguousarray(field_start, dtype=np.uint32)
-        cs = np.ascontiguousarray(conn_start, dtype=np.uint32)
-        opt = lambda a, d: None if a is None else np.ascontiguousarray(a, dtype=d)
-        nv, sf, sel = opt(nvflags, np.uint8), opt(sec_flags, np.uint8), opt(tsel, np.uint32)
-        nfields, nsections = strs.size // 2, fs.size - 1
-        nconns = cs.size - 1
-        ptr = lambda a: None if a is None or a.size == 0 else _vp(a)
-        if sel is not None and sel.size == 0:  # (an empty list is still a list)
-            ptr_sel = np.zeros(1, dtype=np.uint32)
-        else:
-            ptr_sel = sel
-        sids = opt(stream_ids, np.uint64)
-        call = lambda flags: self._call(
-            self._lib.qh_qpack_encode_conns, (), (), ptr, lambda a: a.size,
-            lambda n: np.zeros(n, dtype=np.uint8), plain, strs, nfields, nv, fs, nsections, flags,
-            cs, nconns, ptr_sel, caps)
-        r = self._with_stream_ids(None, call, sids, cs, nsections, nconns, ptr_sel, sf)
+        r = self._encode(None, _u8(plain), _as(strs, SPAN_IN_DTYPE), _as(field_start, np.uint32),
+                         _as(conn_start, np.uint32), _as(nvflags, np.uint8), _as(sec_flags, np.uint8),
+                         _as(tsel, np.uint32), caps, _as(stream_ids, np.uint64))
         return self._unpack(r, lambda a: a)
 
     def encode_dev(self, codec: HuffmanBatchCodec, plain, strs, field_start, conn_start,
@@ -1821,20 +1590,9 @@ class EncoderSet:
         stream_ids int64: qh_enc_sec_flags_batch before the call and
         qh_enc_refs_record_batch after it).
         -> the same dict, of tensors viewed as bytes (``to_host`` converts)."""
-        import torch
         assert self.device is not None
-        nfields, nsections = int(strs.shape[0]) // 2, int(field_start.shape[0]) - 1
-        nconns = int(conn_start.shape[0]) - 1
-        ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-        if tsel is not None and tsel.numel() == 0:
-            tsel = torch.zeros(1, dtype=torch.int32, device=self._dev)
-        call = lambda flags: self._call(
-            self._lib.qh_encode_conns_batch, (codec._ctx,), (_lib.QH_WHERE_DEVICE,), ptr,
-            lambda t: t.numel(), lambda n: torch.zeros(n, dtype=torch.uint8, device=self._dev),
-            plain, strs, nfields, nvflags, field_start, nsections, flags, conn_start, nconns, tsel,
-            caps)
-        return self._with_stream_ids(codec, call, stream_ids, conn_start, nsections, nconns, tsel,
-                                     sec_flags)
+        return self._encode(codec, plain, strs, field_start, conn_start, nvflags, sec_flags, tsel, caps,
+                            stream_ids)
 
     @staticmethod
     def _unpack(r, host):
@@ -1896,8 +1654,8 @@ def _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_byt
             raise ValueError("section_view without views")
         return None, ()
     vw = np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
-    sv = None if section_view is None else np.ascontiguousarray(section_view, dtype=np.uint32)
-    rl = None if ref_limit is None else np.ascontiguousarray(ref_limit, dtype=np.uint64)
+    sv = _as(section_view, np.uint32)
+    rl = _as(ref_limit, np.uint64)
     ents = np.zeros(0, DYN_ENTRY_DTYPE) if entries is None else \
         np.ascontiguousarray(entries, dtype=DYN_ENTRY_DTYPE)
     byts = _u8(b"" if dyn_bytes is None else dyn_bytes)
@@ -1942,14 +1700,12 @@ def plan_fields_dyn(plain, strs, never, field_start, table=None, views=None, sec
     With `codec` the same on the GPU over the host arrays
     (qh_plan_fields_dyn_batch, staged)."""
     lib = _load()
-    plain = _u8(plain)
-    if plain.size == 0:
-        plain = np.zeros(1, dtype=np.uint8)
+    plain = _plain(plain)
     strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
     nf = strs.size // 2
     fs = np.ascontiguousarray(field_start, dtype=np.uint32)
     nsec = fs.size - 1
-    nv = None if never is None else np.ascontiguousarray(never, dtype=np.uint8)
+    nv = _as(never, np.uint8)
     d, keep = _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_bytes)
     lines = np.zeros(max(nf, 1), dtype=FIELD_LINE_DTYPE)
     pfx = np.zeros(max(nsec, 1), dtype=PREFIX_DTYPE)
@@ -2001,13 +1757,11 @@ def plan_fields(plain, strs, never=None):
     """qh_qpack_plan_fields: fields (strs[2i], strs[2i+1]) of plain -> the
     field lines the reference encoder writes at dynamic table capacity 0."""
     lib = _load()
-    plain = _u8(plain)
-    if plain.size == 0:
-        plain = np.zeros(1, dtype=np.uint8)
+    plain = _plain(plain)
     strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
     nf = strs.size // 2
     lines = np.zeros(max(nf, 1), dtype=FIELD_LINE_DTYPE)
-    nv = None if never is None else np.ascontiguousarray(never, dtype=np.uint8)
+    nv = _as(never, np.uint8)
     _lib.check(lib.qh_qpack_plan_fields(_vp(plain), _vp(strs), nf, None if nv is None else _vp(nv),
                                         _vp(lines)), "qh_qpack_plan_fields")
     return lines[:nf]
@@ -2017,13 +1771,11 @@ def plan_fields_host(codec: HuffmanBatchCodec, plain, strs, never=None):
     """plan_fields on the GPU over host arrays (qh_plan_fields_batch,
     staged): the same lines, byte for byte."""
     lib = _load()
-    plain = _u8(plain)
-    if plain.size == 0:
-        plain = np.zeros(1, dtype=np.uint8)
+    plain = _plain(plain)
     strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
     nf = strs.size // 2
     lines = np.zeros(max(nf, 1), dtype=FIELD_LINE_DTYPE)
-    nv = None if never is None else np.ascontiguousarray(never, dtype=np.uint8)
+    nv = _as(never, np.uint8)
     _lib.check(lib.qh_plan_fields_batch(codec._ctx, _vp(plain), _vp(strs), nf,
                                         None if nv is None else _vp(nv), _vp(lines),
                                         _lib.QH_WHERE_HOST), "qh_plan_fields_batch")
@@ -2051,33 +1803,37 @@ class FieldSectionEncoder:
     def __init__(self, device: int = 0, codec: HuffmanBatchCodec | None = None):
         self.codec = codec or HuffmanBatchCodec(device)
 
+    @staticmethod
+    def _with_dst(what, call):
+        """call(dst, dst_cap, need) over a dst of 64 bytes, made once more
+        with one of the need when that was short -> dst's written bytes."""
+        need = ctypes.c_uint64(0)
+        dst = np.zeros(64, dtype=np.uint8)
+        for _ in range(2):
+            rv = call(_vp(dst), dst.size, ctypes.byref(need))
+            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
+                dst = np.zeros(int(need.value), dtype=np.uint8)
+                continue
+            _lib.check(rv, what)
+            break
+        return dst[:need.value]
+
     def encode_sections(self, plain, strs, lines, line_start, prefixes=None):
         """Host arrays -> (dst uint8, sections SPAN_IN_DTYPE)."""
         lib = _load()
-        plain = _u8(plain)
-        if plain.size == 0:
-            plain = np.zeros(1, dtype=np.uint8)
+        plain = _plain(plain)
         strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
         lines = np.ascontiguousarray(lines, dtype=FIELD_LINE_DTYPE)
         if lines.size == 0:
             lines = np.zeros(1, dtype=FIELD_LINE_DTYPE)[:0]
         line_start = np.ascontiguousarray(line_start, dtype=np.uint32)
         nsec = line_start.size - 1
-        pf = None if prefixes is None else np.ascontiguousarray(prefixes, dtype=PREFIX_DTYPE)
+        pf = _as(prefixes, PREFIX_DTYPE)
         sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
-        need = ctypes.c_uint64(0)
-        dst = np.zeros(64, dtype=np.uint8)
-        for _ in range(2):
-            rv = lib.qh_encode_sections_batch(
-                self.codec._ctx, _vp(plain), _vp(strs), strs.size, _vp(lines), _vp(line_start),
-                nsec, None if pf is None else _vp(pf), _vp(dst), dst.size, _vp(sections),
-                ctypes.byref(need), _lib.QH_WHERE_HOST)
-            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
-                dst = np.zeros(int(need.value), dtype=np.uint8)
-                continue
-            _lib.check(rv, "qh_encode_sections_batch")
-            break
-        return dst[:need.value], sections[:nsec]
+        dst = self._with_dst("qh_encode_sections_batch", lambda dst, cap, need: lib.qh_encode_sections_batch(
+            self.codec._ctx, _vp(plain), _vp(strs), strs.size, _vp(lines), _vp(line_start), nsec,
+            None if pf is None else _vp(pf), dst, cap, _vp(sections), need, _lib.QH_WHERE_HOST))
+        return dst, sections[:nsec]
 
     def encode_sections_dev(self, plain, strs, lines, line_start, dst, sections, prefixes=None):
         """Device-resident form over torch tensors (plain uint8, strs int64
@@ -2107,34 +1863,22 @@ class FieldSectionEncoder:
         if table is not None or views is not None:
             return self._encode_fields_dyn(plain, fields, field_start, table, views, section_view,
                                            ref_limit, entries, keys, dyn_bytes)
-        plain = _u8(plain)
-        if plain.size == 0:
-            plain = np.zeros(1, dtype=np.uint8)
+        plain = _plain(plain)
         fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
         if fields.size == 0:
             fields = np.zeros(1, dtype=FIELD_DTYPE)[:0]
         field_start = np.ascontiguousarray(field_start, dtype=np.uint32)
         nsec = field_start.size - 1
         sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
-        need = ctypes.c_uint64(0)
-        dst = np.zeros(64, dtype=np.uint8)
-        for _ in range(2):
-            rv = lib.qh_encode_fields_batch(self.codec._ctx, _vp(plain), _vp(fields), fields.size,
-                                            _vp(field_start), nsec, _vp(dst), dst.size, _vp(sections),
-                                            ctypes.byref(need), _lib.QH_WHERE_HOST)
-            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
-                dst = np.zeros(int(need.value), dtype=np.uint8)
-                continue
-            _lib.check(rv, "qh_encode_fields_batch")
-            break
-        return dst[:need.value], sections[:nsec]
+        dst = self._with_dst("qh_encode_fields_batch", lambda dst, cap, need: lib.qh_encode_fields_batch(
+            self.codec._ctx, _vp(plain), _vp(fields), fields.size, _vp(field_start), nsec, dst, cap,
+            _vp(sections), need, _lib.QH_WHERE_HOST))
+        return dst, sections[:nsec]
 
     def _encode_fields_dyn(self, plain, fields, field_start, table, views, section_view, ref_limit,
                            entries, keys, dyn_bytes):
         lib = _load()
-        plain = _u8(plain)
-        if plain.size == 0:
-            plain = np.zeros(1, dtype=np.uint8)
+        plain = _plain(plain)
         fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
         if fields.size == 0:
             fields = np.zeros(1, dtype=FIELD_DTYPE)[:0]
@@ -2144,20 +1888,13 @@ class FieldSectionEncoder:
         sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
         mx = np.zeros(max(nsec, 1), dtype=np.uint64)
         mn = np.zeros(max(nsec, 1), dtype=np.uint64)
-        need = ctypes.c_uint64(0)
-        dst = np.zeros(64, dtype=np.uint8)
-        for _ in range(2):
-            rv = lib.qh_encode_fields_dyn_batch(
-                self.codec._ctx, _vp(plain), _vp(fields), fields.size, _vp(field_start), nsec,
-                None if d is None else ctypes.byref(d), _vp(dst), dst.size, _vp(sections),
-                ctypes.byref(need), _vp(mx), _vp(mn), _lib.QH_WHERE_HOST)
-            if rv == _lib.QH_ERR_NOMEM and need.value > dst.size:
-                dst = np.zeros(int(need.value), dtype=np.uint8)
-                continue
-            _lib.check(rv, "qh_encode_fields_dyn_batch")
-            break
+        fn = lib.qh_encode_fields_dyn_batch
+        dst = self._with_dst("qh_encode_fields_dyn_batch", lambda dst, cap, need: fn(
+            self.codec._ctx, _vp(plain), _vp(fields), fields.size, _vp(field_start), nsec,
+            None if d is None else ctypes.byref(d), dst, cap, _vp(sections), need, _vp(mx), _vp(mn),
+            _lib.QH_WHERE_HOST))
         del keep
-        return dst[:need.value], sections[:nsec], mx[:nsec], mn[:nsec]
+        return dst, sections[:nsec], mx[:nsec], mn[:nsec]
 
     def encode_fields_dev(self, plain, fields, nfields, field_start, dst, sections, table=None,
                           views=None, section_view=None, ref_limit=None, max_cnt=None, min_cnt=None,
