@@ -1491,6 +1491,131 @@ QH_EXPORT int qh_dec_blocked_compact_batch(
     qh_dec_blk *blks_out, uint64_t *nblks_out, uint64_t blks_out_cap, uint8_t *pend_out,
     uint64_t *npend_out, uint64_t pend_out_cap, int where);
 
+/* ---- Field sections in pieces: reassembled per batch ----------------------
+ *
+ * Every decoder call above takes complete field sections.  The reference
+ * reads a request stream as it arrives: nghttp3_conn hands
+ * nghttp3_qpack_decoder_read_request whatever part of a HEADERS frame is there,
+ * fin = 0 until the last part (lib/nghttp3_conn.c:1880-1883), the stream
+ * context keeps the parse between calls (lib/nghttp3_qpack.c:3347-3805).  Here
+ * a section's bytes are held until its last piece arrives and are then decoded
+ * whole, by the calls above; nothing is parsed before.  Table t's unfinished
+ * sections are parts[pq[t].base, + pq[t].n), in the order their first pieces
+ * arrived, in one caller-owned log parts[0, *nparts); a section's bytes so far
+ * are held[off, + len), contiguous, in one caller-owned, append-only byte log
+ * held[0, *nheld).  pq[] lies beside views, acct and bq.  Each call has a host
+ * form over host pointers and a device form over pointers in HBM (where must
+ * be QH_WHERE_DEVICE; counts are host scalars), asynchronous on the context
+ * stream after its one host wait.
+ *
+ * push: piece p is src[pieces[p].off, + len) of stream piece_sid[p] of table
+ * piece_view[p]; piece_fin[p] != 0: the section ends with it.  The pieces of
+ * one table must be consecutive; a second run of a table or an index >=
+ * ntables gives QH_ERR_INVALID_ARGUMENT, nothing written.  Per table the
+ * pieces are examined in list order:
+ *   1. the stream id appeared earlier in the table's run: verdict
+ *      QH_ERR_INVALID_ARGUMENT, the piece is ignored and the earlier one
+ *      stands (a caller joins what it received for one stream before the
+ *      call, as its QUIC stream buffer already does);
+ *   2. else the held length + the piece's length > max_bytes: verdict
+ *      QH_ERR_QPACK_HEADER_TOO_LARGE, the stream's record, if it has one, is
+ *      removed, nothing is kept or handed on.  The limit is this project's
+ *      own (and at most 2^32 - 1): it stands where nghttp3_conn bounds a
+ *      HEADERS frame by its announced length before a byte reaches QPACK;
+ *   3. else fin: verdict QH_PART_DONE, the held bytes followed by the piece
+ *      are written to done at its cursor, the record is removed.  A section
+ *      that arrives whole takes this path with nothing held; an empty result
+ *      is handed on as an empty block, to which the sections call gives the
+ *      status it gives any empty block;
+ *   4. else verdict QH_PART_KEPT.  A piece of length 0 changes nothing (and
+ *      makes no record).  Otherwise the record's old bytes followed by the
+ *      piece are written at the byte cursor of held and off / len are
+ *      rewritten (no reserved room, no append in place); a stream without a
+ *      record gains one.
+ * Finished section j (in list order of the fin pieces) is done[done_blocks[j]
+ * .off, + len) of stream done_sid[j] of table done_view[j]; the three arrays
+ * have room for npieces entries, *ndone is their count, *done_need the bytes.
+ * They go as they are into qh_decode_sections_batch (src = done, blocks =
+ * done_blocks), qh_emit_fields_batch (block_view), qh_dec_write_decoder_batch
+ * and qh_dec_blocked_push_batch (block_sid, block_view, src = done).  Layout
+ * rules, the same on host and device, so that both logs are equal byte for
+ * byte, dead regions included:
+ *   - a table that gains a record moves: its surviving records (off / len as
+ *     rewritten) are copied in order to the record cursor, the new ones
+ *     follow in list order, the old region is left as it was; the cursor
+ *     starts at *nparts and passes each moved table in order of first
+ *     appearance in the list;
+ *   - a table that only loses records, or whose records only change off /
+ *     len, is compacted in place, order kept (the records past the new n are
+ *     left as they are);
+ *   - new held bytes go back to back in list order of the pieces that cause
+ *     them, older bytes are never touched; done is filled back to back;
+ *   - when a capacity is short the call returns QH_ERR_NOMEM with the exact
+ *     needs in *nparts, *nheld, *done_need and *ndone and nothing else
+ *     written;
+ *   - nothing is read outside src[pieces[p].off, + len): src needs no padding.
+ * A record whose bytes are needed and lie outside held[0, *nheld) gives
+ * QH_ERR_INVALID_ARGUMENT.  done must not overlap held.  Device: runs, a count
+ * pass (a 16-lane group per table), one scan over four segments, one host
+ * wait (the totals and the list's errors), then verdicts and copy items, the
+ * byte copies (two sources per output section: the old bytes, then the
+ * piece), the records.
+ *
+ * cancel (a stream reset): exactly qh_dec_blocked_cancel's semantics, host and
+ * device (0xFF for a later run on the device).  nghttp3_qpack_decoder_
+ * cancel_stream has no held bytes to drop; here there are some.
+ *
+ * compact: as qh_dec_blocked_compact.  Every continued section leaves its
+ * previous copy dead in held, so this log wants compacting more often than
+ * the blocked one: after k continuations of a section of n bytes about k n / 2
+ * bytes are dead.
+ *
+ * Not built: the reference reports a framing error at the piece where it
+ * occurs and BLOCKED as soon as the two prefix integers are read; here both
+ * come at fin, from the whole-section calls (the final verdict, fields,
+ * Required Insert Count and decoder-stream bytes are the same).  A limit on
+ * open streams per table (the caller's QUIC stream limit bounds it),
+ * QH_WHERE_HOST staging, a hashed stream index. */
+#define QH_PART_DONE 0 /* verdict: the section is complete and in done */
+#define QH_PART_KEPT 2 /* verdict: the piece is held (or was empty)    */
+typedef struct qh_dec_part  { uint64_t stream_id, off; uint32_t len, reserved0; uint64_t reserved1; } qh_dec_part;   /* 32 B */
+typedef struct qh_dec_parts { uint64_t base, n, max_bytes, flags; } qh_dec_parts;                                    /* 32 B */
+QH_EXPORT void qh_dec_parts_init(uint64_t max_bytes, qh_dec_parts *pq);
+
+QH_EXPORT int qh_qpack_dec_partial_push(
+    const uint8_t *src, const qh_span_in *pieces, const uint64_t *piece_sid,
+    const uint32_t *piece_view, const uint8_t *piece_fin, size_t npieces, size_t ntables,
+    qh_dec_parts *pq, qh_dec_part *parts, uint64_t *nparts, uint64_t parts_cap, uint8_t *held,
+    uint64_t *nheld, uint64_t held_cap, int32_t *verdict, uint8_t *done, uint64_t done_cap,
+    uint64_t *done_need, qh_span_in *done_blocks, uint64_t *done_sid, uint32_t *done_view,
+    uint64_t *ndone);
+QH_EXPORT int qh_dec_partial_push_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *pieces, const uint64_t *piece_sid,
+    const uint32_t *piece_view, const uint8_t *piece_fin, size_t npieces, size_t ntables,
+    qh_dec_parts *pq, qh_dec_part *parts, uint64_t *nparts, uint64_t parts_cap, uint8_t *held,
+    uint64_t *nheld, uint64_t held_cap, int32_t *verdict, uint8_t *done, uint64_t done_cap,
+    uint64_t *done_need, qh_span_in *done_blocks, uint64_t *done_sid, uint32_t *done_view,
+    uint64_t *ndone, int where);
+
+QH_EXPORT int qh_qpack_dec_partial_cancel(
+    const uint64_t *cancel_sid, const uint32_t *cancel_view, size_t ncancel, size_t ntables,
+    qh_dec_parts *pq, qh_dec_part *parts, uint64_t nparts, uint8_t *removed);
+QH_EXPORT int qh_dec_partial_cancel_batch(
+    qh_ctx *ctx, const uint64_t *cancel_sid, const uint32_t *cancel_view, size_t ncancel,
+    size_t ntables, qh_dec_parts *pq, qh_dec_part *parts, uint64_t nparts, uint8_t *removed,
+    int where);
+
+QH_EXPORT int qh_qpack_dec_partial_compact(
+    const uint32_t *tsel, size_t nsel, size_t ntables, qh_dec_parts *pq, const qh_dec_part *parts,
+    uint64_t nparts, const uint8_t *held, uint64_t nheld, qh_dec_part *parts_out,
+    uint64_t *nparts_out, uint64_t parts_out_cap, uint8_t *held_out, uint64_t *nheld_out,
+    uint64_t held_out_cap);
+QH_EXPORT int qh_dec_partial_compact_batch(
+    qh_ctx *ctx, const uint32_t *tsel, size_t nsel, size_t ntables, qh_dec_parts *pq,
+    const qh_dec_part *parts, uint64_t nparts, const uint8_t *held, uint64_t nheld,
+    qh_dec_part *parts_out, uint64_t *nparts_out, uint64_t parts_out_cap, uint8_t *held_out,
+    uint64_t *nheld_out, uint64_t held_out_cap, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

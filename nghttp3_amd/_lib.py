@@ -211,6 +211,15 @@ EXPORTED_FUNCTIONS = (
     "qh_dec_blocked_cancel_batch",
     "qh_qpack_dec_blocked_compact",
     "qh_dec_blocked_compact_batch",
+    # field sections in pieces: held until fin, cancelled and compacted per batch
+    # (csrc/qh_partial.c, csrc/qh_partial.inc)
+    "qh_dec_parts_init",
+    "qh_qpack_dec_partial_push",
+    "qh_dec_partial_push_batch",
+    "qh_qpack_dec_partial_cancel",
+    "qh_dec_partial_cancel_batch",
+    "qh_qpack_dec_partial_compact",
+    "qh_dec_partial_compact_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -43,6 +43,8 @@ enum BufId {
   kBufAck,          // the acknowledgement calls (qh_ack.inc): owner words, counts, scan headers
   kBufBlocked,      // the blocked-section calls (qh_blocked.inc): runs, counts, per-block records, scan headers
   kBufBlockedWork,  // ... compaction's flat list of output records
+  kBufPartial,      // the calls for sections in pieces (qh_partial.inc): runs, counts, per-piece records, copy items, scan headers
+  kBufPartialWork,  // ... compaction's copy items
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap

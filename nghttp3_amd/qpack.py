@@ -75,6 +75,12 @@ DEC_BLK_DTYPE = np.dtype([("stream_id", "<u8"), ("ricnt", "<u8"), ("off", "<u8")
                           ("reserved", "<u4")])
 DEC_BLKS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("max_blocked", "<u8"), ("flags", "<u8")])
 assert DEC_BLK_DTYPE.itemsize == 32 and DEC_BLKS_DTYPE.itemsize == 32
+# include/qhuff.h qh_dec_part, qh_dec_parts
+DEC_PART_DTYPE = np.dtype([("stream_id", "<u8"), ("off", "<u8"), ("len", "<u4"), ("reserved0", "<u4"),
+                           ("reserved1", "<u8")])
+DEC_PARTS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("max_bytes", "<u8"), ("flags", "<u8")])
+assert DEC_PART_DTYPE.itemsize == 32 and DEC_PARTS_DTYPE.itemsize == 32
+PART_DONE, PART_KEPT = 0, 2
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -218,6 +224,12 @@ def _load():
         _pair(lib, "dec_blocked_release", [vp, sz, sz, vp, vp, vp, u64, vp, vp, vp, vp, vp, pu64, u64])
         _pair(lib, "dec_blocked_cancel", [vp, vp, sz, sz, vp, vp, u64, vp])
         _pair(lib, "dec_blocked_compact", [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64])
+        lib.qh_dec_parts_init.argtypes = [u64, vp]
+        lib.qh_dec_parts_init.restype = None
+        _pair(lib, "dec_partial_push", [vp, vp, vp, vp, vp, sz, sz, vp, vp, pu64, u64, vp, pu64, u64, vp, vp,
+                                        u64, pu64, vp, vp, vp, pu64])
+        _pair(lib, "dec_partial_cancel", [vp, vp, sz, sz, vp, vp, u64, vp])
+        _pair(lib, "dec_partial_compact", [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64])
         _L = lib
     return _L
 
@@ -923,10 +935,21 @@ class DynamicTableSet:
     DEC_BLKS_DTYPE), the record log ``blks`` / ``nblks`` (DEC_BLK_DTYPE) and
     the byte log ``pend`` / ``npend``, fed by ``push_blocked`` after an emit,
     drained by ``release_blocked`` after ``read_encoder`` and by
-    ``cancel_blocked``; ``compact_blocked`` replaces the two logs."""
+    ``cancel_blocked``; ``compact_blocked`` replaces the two logs.
+
+    With `max_section_bytes` (a scalar, or one value per table; the
+    project's own limit on a section's length) the set also keeps the
+    sections that arrive in pieces until their last piece: ``pq`` (uint8
+    [ntables * 32], DEC_PARTS_DTYPE), the record log ``parts`` / ``nparts``
+    (DEC_PART_DTYPE) and the byte log ``held`` / ``nheld``, fed by
+    ``push_pieces``, which hands the finished sections on whole;
+    ``cancel_pieces`` drops the streams that were reset, ``compact_pieces``
+    replaces the two logs.  Every continued section leaves its previous copy
+    dead in ``held``: this log wants compacting more often than the blocked
+    one."""
 
     def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None,
-                 max_blocked=None):
+                 max_blocked=None, max_section_bytes=None):
         self._lib = _load()
         self.codec = codec
         self.ntables = int(ntables)
@@ -959,6 +982,18 @@ class DynamicTableSet:
             self.npend = 0
             self.bq = be.put(bq.view(np.uint8).copy())
             self.blks, self.pend = be.empty(0), be.empty(0)
+        self.max_section_bytes = max_section_bytes
+        if max_section_bytes is not None:
+            mx = np.broadcast_to(np.asarray(max_section_bytes, dtype=np.uint64), (self.ntables,))
+            pq = np.zeros(max(self.ntables, 1), dtype=DEC_PARTS_DTYPE)[:self.ntables]
+            p1 = np.zeros(1, dtype=DEC_PARTS_DTYPE)
+            for t in range(self.ntables):
+                self._lib.qh_dec_parts_init(int(mx[t]), _vp(p1))
+                pq[t] = p1[0]
+            self.nparts = 0
+            self.nheld = 0
+            self.pq = be.put(pq.view(np.uint8).copy())
+            self.parts, self.held = be.empty(0), be.empty(0)
 
     # -- capacity: the arrays grow by cap_for, the log's prefix kept
 
@@ -1243,6 +1278,142 @@ class DynamicTableSet:
         h = self._blocked().host
         return (h(self.bq).view(DEC_BLKS_DTYPE), h(self.blks[:self.nblks * 32]).view(DEC_BLK_DTYPE),
                 h(self.pend[:self.npend]))
+
+    # -- sections in pieces (max_section_bytes given): qh_dec_partial_* / qh_qpack_dec_partial_*
+
+    def _partial(self):
+        if self.max_section_bytes is None:
+            raise ValueError("the set was made without max_section_bytes")
+        return self._be
+
+    _DONE = (("done_blocks", 16), ("done_sid", 8), ("done_view", 4))  # (bytes per section)
+
+    def _push_pieces(self, src, pieces, piece_sid, piece_view, fin, caps, dtypes):
+        be = self._partial()
+        ptr = be.ptr
+        n = be.size(piece_sid)
+        fixed = caps is not None
+        verdict = be.zeros(max(n, 1), np.int32)
+        o = {k: be.zeros(max(n, 1) * w) for k, w in self._DONE}
+        dcap = caps[2] if fixed else getattr(self, "_done_cap", 4096)
+
+        def attempt():
+            # (tests: sentinel bytes behind a fixed capacity)
+            o["done"] = be.room(dcap, 64) if fixed else be.empty(dcap)
+            nr, nb = ctypes.c_uint64(self.nparts), ctypes.c_uint64(self.nheld)
+            dn, nd = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rcap, bcap = caps[:2] if fixed else (be.size(self.parts) // 32, be.size(self.held))
+            rv = be.call(self._lib, "dec_partial_push", ptr(src), ptr(pieces), ptr(piece_sid),
+                         ptr(piece_view), ptr(fin), n, self.ntables, ptr(self.pq), ptr(self.parts),
+                         ctypes.byref(nr), rcap, ptr(self.held), ctypes.byref(nb), bcap, ptr(verdict),
+                         ptr(o["done"]), dcap, ctypes.byref(dn), ptr(o["done_blocks"]),
+                         ptr(o["done_sid"]), ptr(o["done_view"]), ctypes.byref(nd))
+            return rv, (int(nr.value), int(nb.value), int(dn.value), int(nd.value))
+
+        def enlarge(needs):
+            nonlocal dcap
+            self._grow("parts", self.nparts * 32, needs[0] * 32, 4096)
+            self._grow("held", self.nheld, needs[1], 4096)
+            dcap = self._done_cap = cap_for(needs[2], dcap)
+        rv, (nr, nb, dn, nd) = be.retry("dec_partial_push", attempt, enlarge, fixed)
+        if rv == 0:
+            self.nparts, self.nheld = nr, nb
+        k = nd if rv == 0 else 0
+        for (name, w), d in zip(self._DONE, dtypes):
+            o[name + "_raw"] = o[name]
+            o[name] = o[name][:k * w].view(d)
+        o.update({"rv": rv, "verdict": verdict[:n], "nparts": nr, "nheld": nb, "done_need": dn, "ndone": nd})
+        return o
+
+    def push_pieces(self, src, pieces, piece_sid, piece_view, fin, caps=None):
+        """Pieces of field sections as they arrive (host form,
+        qh_qpack_dec_partial_push): pieces SPAN_IN_DTYPE spans of src,
+        piece_sid uint64, piece_view uint32 (a table's pieces consecutive, a
+        stream at most once per call), fin uint8 (the section ends with the
+        piece).  -> dict: verdict (int32: PART_DONE the section is complete,
+        PART_KEPT held, -101 the stream came earlier in the call, -109 longer
+        than max_section_bytes: dropped), and the finished sections done
+        (uint8), done_blocks (SPAN_IN_DTYPE spans of done), done_sid
+        (uint64), done_view (uint32), ndone, done_need; rv, nparts, nheld.
+        done / done_blocks / done_view go into decode_blocks and emit_fields,
+        done_sid / done_view into push_blocked and write_decoder.  The logs
+        grow as needed; caps = (records, held bytes, done bytes) fixes the
+        capacities instead and hands the call's return value back in rv."""
+        assert self.codec is None
+        return self._push_pieces(_u8(src), _as(pieces, SPAN_IN_DTYPE), _as(piece_sid, np.uint64),
+                                 _as(piece_view, np.uint32), _as(fin, np.uint8), caps,
+                                 (SPAN_IN_DTYPE, np.uint64, np.uint32))
+
+    def push_pieces_dev(self, src, pieces, piece_sid, piece_view, fin, caps=None):
+        """qh_dec_partial_push_batch: the same over torch tensors in HBM (src
+        uint8, pieces int64 [n, 2], piece_sid int64, piece_view int32, fin
+        uint8).  -> dict of tensors (done_blocks int64 [ndone, 2], done_sid
+        int64, done_view int32).  One host wait, for the totals."""
+        import torch
+        assert self.codec is not None
+        o = self._push_pieces(src, pieces, piece_sid, piece_view, fin, caps,
+                              (torch.int64, torch.int64, torch.int32))
+        o["done_blocks"] = o["done_blocks"].reshape(-1, 2)
+        return o
+
+    def _cancel_pieces(self, sid, view):
+        be = self._partial()
+        ptr = be.ptr
+        n = be.size(sid)
+        removed = be.zeros(max(n, 1))
+        rv = be.call(self._lib, "dec_partial_cancel", ptr(sid), ptr(view), n, self.ntables, ptr(self.pq),
+                     ptr(self.parts), self.nparts, ptr(removed))
+        return rv, removed[:n]
+
+    def cancel_pieces(self, cancel_sid, cancel_view, check=True):
+        """Host form (qh_qpack_dec_partial_cancel), on a stream reset: the held
+        bytes of the cancelled streams (uint64 ids, uint32 tables; a table's
+        consecutive) are dropped.  -> removed (uint8: 1 where some were held)."""
+        assert self.codec is None
+        rv, removed = self._cancel_pieces(np.ascontiguousarray(cancel_sid, dtype=np.uint64),
+                                          np.ascontiguousarray(cancel_view, dtype=np.uint32))
+        if check:
+            self._be.check(rv, "dec_partial_cancel")
+            return removed
+        return rv, removed
+
+    def cancel_pieces_dev(self, cancel_sid, cancel_view):
+        """qh_dec_partial_cancel_batch (int64 ids, int32 tables): no host wait;
+        removed is 0xFF for the items of a table's second run or of a table
+        out of range, which remove nothing."""
+        assert self.codec is not None
+        rv, removed = self._cancel_pieces(cancel_sid, cancel_view)
+        self._be.check(rv, "dec_partial_cancel")
+        return removed
+
+    def compact_pieces(self):
+        """Replaces ``parts`` and ``held`` by logs that hold the unfinished
+        sections of every table alone, back to back in table order, ``pq``
+        rebased.  When to call is the caller's decision: compare ``nheld``
+        with what is held; every continued section leaves its previous copy
+        dead, so this log fills faster than the blocked one.  A failed call
+        leaves the object as it was."""
+        be = self._partial()
+        ptr = be.ptr
+        pq = be.own(self.pq)
+
+        def call(outs):
+            recs, byts = outs
+            nr, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rv = be.call(self._lib, "dec_partial_compact", None, self.ntables, self.ntables, ptr(pq),
+                         ptr(self.parts), self.nparts, ptr(self.held), self.nheld, ptr(recs),
+                         ctypes.byref(nr), be.size(recs) // 32, ptr(byts), ctypes.byref(nb),
+                         be.size(byts))
+            return rv, (int(nr.value), int(nb.value))
+        (recs, byts), (nr, nb) = be.sized("dec_partial_compact", call, self._LOG_ROOMS, be.zeros)
+        self.pq, self.parts, self.held, self.nparts, self.nheld = pq, recs, byts, nr, nb
+
+    def piece_records(self):
+        """-> (pq DEC_PARTS_DTYPE [ntables], parts DEC_PART_DTYPE [nparts],
+        held uint8 [nheld]): host copies of the unfinished sections' state."""
+        h = self._partial().host
+        return (h(self.pq).view(DEC_PARTS_DTYPE), h(self.parts[:self.nparts * 32]).view(DEC_PART_DTYPE),
+                h(self.held[:self.nheld]))
 
     def compact(self, extra_views=None):
         """Compacts the log (qh_dtables_compact_batch on the device form,
