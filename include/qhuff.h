@@ -1616,6 +1616,151 @@ QH_EXPORT int qh_dec_partial_compact_batch(
     qh_dec_part *parts_out, uint64_t *nparts_out, uint64_t parts_out_cap, uint8_t *held_out,
     uint64_t *nheld_out, uint64_t held_out_cap, int where);
 
+/* ---- Encoder and decoder streams as they arrive: cut instructions held ----
+ *
+ * qh_dtables_apply_batch and qh_enc_read_decoder_batch stop before an
+ * instruction that the end of the input cuts and leave the rest to the caller.
+ * The reference takes whatever has arrived and buffers a cut instruction
+ * itself (nghttp3_qpack_decoder_read_encoder lib/nghttp3_qpack.c:2815-3157,
+ * nghttp3_qpack_encoder_read_decoder :2545-2641).  This layer keeps that tail
+ * beside the other per-connection records: one qh_ustream per table (beside
+ * views / acct / bq / pq) or per connection (beside qh_enc_refs), the unread
+ * bytes log[off, + len) in one caller-owned, append-only byte log
+ * log[0, *nlog).  Each call has a host form over host pointers and a device
+ * form over pointers in HBM (where must be QH_WHERE_DEVICE; counts are host
+ * scalars).  The host functions and the kernels compile the same rules
+ * (csrc/qh_ustream_core.h) and follow the same layout, so records, log (dead
+ * regions included), joined and verdicts are equal byte for byte.
+ *
+ * A record also holds the two pieces of read_encoder's per-connection state
+ * that no other call keeps: flags & QH_USTREAM_BAD is decoder->ctx.bad (set at
+ * :3155 after an encoder-stream error and at :3803 after a failed section,
+ * tested at :2826), ulen is uninterrupted_encoderlen (:2834-2837, limited by
+ * NGHTTP3_QPACK_MAX_ENCODERLEN = 131,072, lib/nghttp3_qpack.h:54; reset when a
+ * section finishes, :3797).  The encoder side's 4 KiB twin is
+ * qh_enc_refs.dlen, kept by qh_enc_read_decoder_batch itself.
+ *
+ * join: piece p is src[pieces[p].off, + len), the new bytes of the stream of
+ * table tsel[p] (NULL: table p, nsel = ntables).  limit is
+ * QH_USTREAM_MAX_ENCODERLEN for tables and 0 (no rule) for decoder streams.
+ * Per listed stream, in list order:
+ *   1. QH_USTREAM_BAD set: verdict QH_ERR_QPACK_FATAL (-108), the piece is
+ *      dropped, joined[p] is empty, the record is unchanged;
+ *   2. else an empty piece: verdict 0, joined[p] is the tail as it lies
+ *      (off, len), held = len, no byte is copied;
+ *   3. else limit != 0 and ulen + len > limit: verdict
+ *      QH_ERR_QPACK_ENCODER_STREAM_ERROR (-402), ulen += len all the same (as
+ *      :2834), BAD is not set, the piece is dropped, the tail is kept,
+ *      joined[p] is empty;
+ *   4. else verdict 0: the tail followed by the piece is written at the log's
+ *      cursor, held = the old len, off = the cursor, len += the piece's, (limit
+ *      != 0) ulen += the piece's, joined[p] = (off, len).
+ * An empty joined[p] is (0, 0).  joined goes as it is into
+ * qh_dtables_apply_batch / qh_enc_read_decoder_batch as `streams`, with src =
+ * log and the same list; the call's status for p is verdict[p] where that is
+ * negative, else the apply's or read's.  New bytes go back to back in list
+ * order at *nlog; nothing written earlier is modified, and the tail of a table
+ * that is not listed stays where it is.  Nothing is read outside a piece or a
+ * tail.  Returns 0; QH_ERR_INVALID_ARGUMENT with nothing written when a table
+ * index is >= ntables, a table is named twice, a listed record's tail leaves
+ * log[0, *nlog) or tail + piece is 2^32 bytes or more; QH_ERR_NOMEM when
+ * log_cap is short, *nlog then the exact need and nothing else written.
+ * Device: a lane per stream (rules and lengths), one qh_k_scan_seg, one host
+ * wait for the total and the error flag, a lane per stream (records, joined,
+ * verdicts, two copy items per stream: the tail, then the piece), the byte
+ * copy of the pieces layer (qh_k_part_bytes: a lane per 16 bytes of the
+ * destination, so one long tail and many short ones balance).
+ *
+ * keep: after the apply or read, with its status and consumed and the same
+ * list.  status 0: off += consumed, len -= consumed (consumed above len counts
+ * as len).  status < 0 with QH_USTREAM_LATCH (tables): len = 0 and BAD is set.
+ * status < 0 without it (decoder streams): len = min(len, held): a refused
+ * call read nothing (:2553-2564), so the head the reference buffered before it
+ * survives; after an error that sets QH_ENC_REFS_BAD nothing is read again.
+ * No bytes move; the device call is asynchronous and has no host wait, so a
+ * list error (which the join before it has already refused) leaves the
+ * offending streams untouched there and is QH_ERR_INVALID_ARGUMENT with
+ * nothing written on the host.  An apply that answers QH_ERR_NOMEM is repeated
+ * on the same joined before keep.
+ *
+ * sections: after a finished emit call, with its status per block and
+ * block_view (NULL: table 0).  A table with a block of status 0 gets ulen = 0
+ * (:3797); one with a block of status < 0 gets BAD (:3803); QH_EMIT_BLOCKED
+ * changes nothing.  Host: a block_view entry >= ntables is
+ * QH_ERR_INVALID_ARGUMENT, nothing written; device (a lane per block, no host
+ * wait): such a block is passed over.
+ *
+ * compact: the tails of all ntables records copied back to back, in table
+ * order, to a fresh log (log_out, not overlapping log), off rebased (an empty
+ * tail's too); len, held, ulen and flags stay.  log_out_cap 0 with a null
+ * log_out is the sizing call: QH_ERR_NOMEM, *nlog_out the exact need, records
+ * untouched.  A tail that leaves log[0, nlog) is QH_ERR_INVALID_ARGUMENT,
+ * nothing written.  Call it between a keep and the next join (held describes
+ * the last joined stream, which is gone).  Every join writes tail + piece
+ * anew, so the log grows by what arrives plus the tails; a caller may compact
+ * after every keep at the cost of the tails alone, and no tail is longer than
+ * the longest instruction the scanners accept (an encoder-stream insert of
+ * 10 + 256 + 10 + 65,536 bytes, a decoder-stream instruction of 11).
+ *
+ * Not built: the reference parses byte by byte and may report an error inside
+ * an instruction that is still cut (in the recorded cases: a dynamic name
+ * index that is not live while the value is still to come); here the apply
+ * sees whole instructions, so the same code comes at the call that delivers
+ * the instruction's last byte, status 0 until then (the reference's is the
+ * error and then -108), the table states equal at every step, and no
+ * instruction the reference did not apply is applied.
+ * On the decoder stream the read is handed tail and piece, so dlen takes the
+ * tail with the piece that completes it; the reference counted the head when
+ * it came.  Where a tail is held while an encode resets dlen, or while a call
+ * is refused by the length rule (-403), the next call that is read counts the
+ * head once more: until the next encode with no tail held dlen is ahead of the
+ * reference's count by at most a cut instruction's bytes, and a piece that
+ * takes the reference's count into (4096 - tail, 4096] is refused here where
+ * the reference still accepts it.  QH_WHERE_HOST staging, a
+ * per-table selection for compact. */
+#define QH_USTREAM_BAD 0x1u           /* qh_ustream.flags: ctx.bad, nothing is read again */
+#define QH_USTREAM_LATCH 0x1u         /* keep opts: a failed stream sets QH_USTREAM_BAD   */
+#define QH_USTREAM_MAX_ENCODERLEN 131072u /* NGHTTP3_QPACK_MAX_ENCODERLEN */
+typedef struct qh_ustream { /* 32 B */
+  uint64_t off;  /* the unread bytes are log[off, + len)                          */
+  uint32_t len;
+  uint32_t held; /* of the last joined stream, the leading bytes that were tail   */
+  uint64_t ulen; /* uninterrupted_encoderlen                                      */
+  uint32_t flags;
+  uint32_t reserved;
+} qh_ustream;
+QH_EXPORT void qh_ustream_init(qh_ustream *us);
+
+QH_EXPORT int qh_qpack_ustream_join(
+    const uint8_t *src, const qh_span_in *pieces, const uint32_t *tsel, size_t nsel, size_t ntables,
+    uint64_t limit, qh_ustream *us, uint8_t *log, uint64_t *nlog, uint64_t log_cap,
+    qh_span_in *joined, int32_t *verdict);
+QH_EXPORT int qh_ustream_join_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *pieces, const uint32_t *tsel, size_t nsel,
+    size_t ntables, uint64_t limit, qh_ustream *us, uint8_t *log, uint64_t *nlog, uint64_t log_cap,
+    qh_span_in *joined, int32_t *verdict, int where);
+
+QH_EXPORT int qh_qpack_ustream_keep(
+    const int32_t *status, const uint32_t *consumed, const uint32_t *tsel, size_t nsel,
+    size_t ntables, uint32_t opts, qh_ustream *us);
+QH_EXPORT int qh_ustream_keep_batch(
+    qh_ctx *ctx, const int32_t *status, const uint32_t *consumed, const uint32_t *tsel, size_t nsel,
+    size_t ntables, uint32_t opts, qh_ustream *us, int where);
+
+QH_EXPORT int qh_qpack_ustream_sections(
+    const int32_t *status, const uint32_t *block_view, size_t nblocks, size_t ntables,
+    qh_ustream *us);
+QH_EXPORT int qh_ustream_sections_batch(
+    qh_ctx *ctx, const int32_t *status, const uint32_t *block_view, size_t nblocks, size_t ntables,
+    qh_ustream *us, int where);
+
+QH_EXPORT int qh_qpack_ustream_compact(
+    size_t ntables, qh_ustream *us, const uint8_t *log, uint64_t nlog, uint8_t *log_out,
+    uint64_t *nlog_out, uint64_t log_out_cap);
+QH_EXPORT int qh_ustream_compact_batch(
+    qh_ctx *ctx, size_t ntables, qh_ustream *us, const uint8_t *log, uint64_t nlog,
+    uint8_t *log_out, uint64_t *nlog_out, uint64_t log_out_cap, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

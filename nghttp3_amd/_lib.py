@@ -220,6 +220,17 @@ EXPORTED_FUNCTIONS = (
     "qh_dec_partial_cancel_batch",
     "qh_qpack_dec_partial_compact",
     "qh_dec_partial_compact_batch",
+    # encoder and decoder streams as they arrive: cut instructions held per batch
+    # (csrc/qh_ustream.c, csrc/qh_ustream.inc)
+    "qh_ustream_init",
+    "qh_qpack_ustream_join",
+    "qh_ustream_join_batch",
+    "qh_qpack_ustream_keep",
+    "qh_ustream_keep_batch",
+    "qh_qpack_ustream_sections",
+    "qh_ustream_sections_batch",
+    "qh_qpack_ustream_compact",
+    "qh_ustream_compact_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -45,6 +45,7 @@ enum BufId {
   kBufBlockedWork,  // ... compaction's flat list of output records
   kBufPartial,      // the calls for sections in pieces (qh_partial.inc): runs, counts, per-piece records, copy items, scan headers
   kBufPartialWork,  // ... compaction's copy items
+  kBufUstream,      // the calls for streams as they arrive (qh_ustream.inc): owner words, lengths, copy items, scan headers
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap

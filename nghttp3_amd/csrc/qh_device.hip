@@ -22,8 +22,9 @@
 //   qh_k_ack_*, qh_k_ackw_*  acknowledgements: the reference log, decoder streams read and written
 //   qh_k_blk_*         blocked sections: queued, released, cancelled, compacted
 //   qh_k_part_*        sections in pieces: held, reassembled at fin, compacted
+//   qh_k_us_*          encoder and decoder streams as they arrive: cut instructions held
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
-// The kernels from qh_k_encsec_* to qh_k_part_* work a 16-lane group per table,
+// The kernels from qh_k_encsec_* to qh_k_us_* work a 16-lane group per table,
 // connection or block and leave their totals in one scan header: both are
 // qh_group.inc's.
 // Development variants (the pair decoder, the segment encoder) build only
@@ -88,4 +89,5 @@
 #include "qh_ack.inc"           // acknowledgements: reference log, decoder streams read and written
 #include "qh_blocked.inc"       // blocked sections: the queue log, push, release, cancel, compact
 #include "qh_partial.inc"       // sections in pieces: held until fin, handed on whole; cancel, compact
+#include "qh_ustream.inc"       // encoder and decoder streams as they arrive: cut instructions held; join, keep, sections, compact
 

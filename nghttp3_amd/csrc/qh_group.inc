@@ -1,6 +1,6 @@
 // What the state kernels share (qh_enc_sections.inc, qh_emit.inc,
 // qh_plan_dyn.inc, qh_dtset.inc, qh_encconn.inc, qh_ack.inc, qh_blocked.inc,
-// qh_partial.inc):
+// qh_partial.inc, qh_ustream.inc):
 // the 16-lane group that serves one table, connection, block or record, and
 // the header of a segmented scan (qh_k_scan_seg) whose totals the host reads
 // back (scan_hdr_reset / scan_hdr_wait, qh_api.inc).

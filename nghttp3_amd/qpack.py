@@ -81,6 +81,11 @@ DEC_PART_DTYPE = np.dtype([("stream_id", "<u8"), ("off", "<u8"), ("len", "<u4"),
 DEC_PARTS_DTYPE = np.dtype([("base", "<u8"), ("n", "<u8"), ("max_bytes", "<u8"), ("flags", "<u8")])
 assert DEC_PART_DTYPE.itemsize == 32 and DEC_PARTS_DTYPE.itemsize == 32
 PART_DONE, PART_KEPT = 0, 2
+# include/qhuff.h qh_ustream
+USTREAM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("held", "<u4"), ("ulen", "<u8"), ("flags", "<u4"),
+                          ("reserved", "<u4")])
+assert USTREAM_DTYPE.itemsize == 32
+USTREAM_BAD, USTREAM_LATCH, USTREAM_MAX_ENCODERLEN = 0x1, 0x1, 131072
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
@@ -230,6 +235,12 @@ def _load():
                                         u64, pu64, vp, vp, vp, pu64])
         _pair(lib, "dec_partial_cancel", [vp, vp, sz, sz, vp, vp, u64, vp])
         _pair(lib, "dec_partial_compact", [vp, sz, sz, vp, vp, u64, vp, u64, vp, pu64, u64, vp, pu64, u64])
+        lib.qh_ustream_init.argtypes = [vp]
+        lib.qh_ustream_init.restype = None
+        _pair(lib, "ustream_join", [vp, vp, vp, sz, sz, u64, vp, vp, pu64, u64, vp, vp])
+        _pair(lib, "ustream_keep", [vp, vp, vp, sz, sz, c.c_uint32, vp])
+        _pair(lib, "ustream_sections", [vp, vp, sz, sz, vp])
+        _pair(lib, "ustream_compact", [sz, vp, vp, u64, vp, pu64, u64])
         _L = lib
     return _L
 
@@ -915,6 +926,102 @@ class DynamicTable:
                 "nentries": int(ents.size), "nbytes": int(byts.size)}
 
 
+class HeldStreams:
+    """The encoder or decoder streams of `n` tables or connections as they
+    arrive (qh_ustream_* / qh_qpack_ustream_*): one USTREAM_DTYPE record each
+    in ``us`` (uint8 [n * 32]) and the append-only byte log ``log`` /
+    ``nlog`` that holds every joined stream, the cut instructions among them.
+    `be` is the owning state object's Backend; a device form without a codec
+    of its own takes one per call."""
+
+    def __init__(self, lib, be, n: int):
+        self._lib, self._be, self.n = lib, be, int(n)
+        # (a fresh record is all zeros: qh_ustream_init)
+        self.us = be.put(np.zeros(self.n * 32, dtype=np.uint8))
+        self.log = be.empty(4096)
+        self.nlog = 0
+
+    _grow = grow
+
+    def join(self, src, pieces, tsel, limit, codec=None, cap=None):
+        """-> (rv, need, joined, verdict): joined the listed streams' spans of
+        ``log`` (bytes, 16 per stream), ready to be `streams` with src =
+        ``log``; verdict int32; need the log's length after the call (on
+        QH_ERR_NOMEM: what it would be).  cap: a fixed capacity of the log
+        instead of growing, as the other state calls take ``caps=``; rv is
+        then the call's return value, unchecked."""
+        be = self._be
+        ptr = be.ptr
+        nsel = self.n if tsel is None else be.size(tsel)
+        # (a call that returns 0 writes every listed entry of both)
+        joined = be.empty(max(nsel, 1) * 16)
+        verdict = be.empty(max(nsel, 1), np.int32)
+        fixed = cap is not None
+
+        def attempt():
+            n = ctypes.c_uint64(self.nlog)
+            rv = be.call(self._lib, "ustream_join", ptr(src), ptr(pieces), be.list_ptr(tsel), nsel, self.n,
+                         limit, ptr(self.us), ptr(self.log), ctypes.byref(n),
+                         cap if fixed else be.size(self.log), ptr(joined), ptr(verdict), codec=codec)
+            return rv, int(n.value)
+        rv, need = be.retry("ustream_join", attempt, lambda need: self._grow("log", self.nlog, need, 4096),
+                            fixed)
+        if rv == 0:
+            self.nlog = need
+        return rv, need, joined[:nsel * 16], verdict[:nsel]
+
+    def keep(self, status, consumed, tsel, opts, codec=None, check=True):
+        be = self._be
+        nsel = self.n if tsel is None else be.size(tsel)
+        rv = be.call(self._lib, "ustream_keep", be.ptr(status), be.ptr(consumed), be.list_ptr(tsel), nsel,
+                     self.n, opts, be.ptr(self.us), codec=codec)
+        if check:
+            be.check(rv, "ustream_keep")
+        return rv
+
+    def sections(self, status, block_view, codec=None, check=True):
+        be = self._be
+        # (an emit result's status may have room behind its blocks: the list says how many there are)
+        nblocks = be.size(status) if block_view is None else be.size(block_view)
+        assert nblocks <= be.size(status)
+        rv = be.call(self._lib, "ustream_sections", be.ptr(status), be.list_ptr(block_view), nblocks,
+                     self.n, be.ptr(self.us), codec=codec)
+        if check:
+            be.check(rv, "ustream_sections")
+        return rv
+
+    def compact(self, codec=None):
+        """Replaces ``log`` by one that holds the tails alone, back to back in
+        table order, ``us`` rebased.  A failed call leaves the object as it
+        was."""
+        be = self._be
+        us = be.own(self.us)
+
+        def call(outs):
+            n = ctypes.c_uint64(0)
+            rv = be.call(self._lib, "ustream_compact", self.n, be.ptr(us), be.ptr(self.log), self.nlog,
+                         be.ptr(outs[0]), ctypes.byref(n), be.size(outs[0]), codec=codec)
+            return rv, (int(n.value),)
+        (log,), (n,) = be.sized("ustream_compact", call, ((1, 4096),), be.zeros)
+        self.us, self.log, self.nlog = us, log, n
+
+    def records(self):
+        """-> (us USTREAM_DTYPE [n], log uint8 [nlog]), numpy copies."""
+        h = self._be.host
+        return h(self.us).view(USTREAM_DTYPE), h(self.log[:self.nlog])
+
+    def feed(self, read, src, pieces, tsel, limit, opts, codec=None):
+        """join -> read(log, joined, tsel) -> (status, consumed) -> keep.
+        -> status: the join's verdict where that is negative, else the
+        read's."""
+        _, _, joined, verdict = self.join(src, pieces, tsel, limit, codec)
+        status, consumed = read(self.log, joined, tsel)
+        self.keep(status, consumed, tsel, opts, codec)
+        if self._be.dev:
+            return self._be.torch.where(verdict < 0, verdict, status)
+        return np.where(verdict < 0, verdict, status)
+
+
 class DynamicTableSet:
     """The dynamic tables of many connections over one log
     (qh_dtables_apply_batch / qh_qpack_dtables_apply): `ntables` fresh tables
@@ -946,10 +1053,18 @@ class DynamicTableSet:
     ``cancel_pieces`` drops the streams that were reset, ``compact_pieces``
     replaces the two logs.  Every continued section leaves its previous copy
     dead in ``held``: this log wants compacting more often than the blocked
-    one."""
+    one.
+
+    With ``streams=True`` the set also keeps each table's encoder stream as it
+    arrives (``ustreams``, a HeldStreams): ``feed_encoder`` takes whatever
+    bytes have come, holds a cut instruction until the rest follows, and
+    keeps the reference's sticky failure and its 128 KiB rule;
+    ``note_sections`` tells it what an emit call found, ``compact_streams``
+    replaces its log, ``stream_records`` reads it back.  ``read_encoder`` is
+    unchanged."""
 
     def __init__(self, hard_max, ntables: int, codec: HuffmanBatchCodec | None = None,
-                 max_blocked=None, max_section_bytes=None):
+                 max_blocked=None, max_section_bytes=None, streams: bool = False):
         self._lib = _load()
         self.codec = codec
         self.ntables = int(ntables)
@@ -994,6 +1109,7 @@ class DynamicTableSet:
             self.nheld = 0
             self.pq = be.put(pq.view(np.uint8).copy())
             self.parts, self.held = be.empty(0), be.empty(0)
+        self.ustreams = HeldStreams(self._lib, be, self.ntables) if streams else None
 
     # -- capacity: the arrays grow by cap_for, the log's prefix kept
 
@@ -1041,6 +1157,56 @@ class DynamicTableSet:
         status, consumed = self._read_encoder(_u8(src), _as(streams, SPAN_IN_DTYPE),
                                               _as(tsel, np.uint32))
         return status, consumed.view(np.uint32)
+
+    # -- the encoder streams as they arrive (streams=True): qh_ustream_* / qh_qpack_ustream_*
+
+    def _ustreams(self):
+        if self.ustreams is None:
+            raise ValueError("the set was made without streams=True")
+        return self.ustreams
+
+    def feed_encoder(self, src, pieces, tsel=None):
+        """Encoder-stream bytes as they arrive (host form): piece p is
+        src[pieces[p].off, + len) (SPAN_IN_DTYPE), the new bytes of table
+        tsel[p]'s stream (None: table p), cut anywhere.  Runs join -> apply
+        (growing the table log as ``read_encoder`` does) -> keep.  -> status
+        int32 per piece: 0, the first failing instruction's error (reported
+        with the piece that completes the instruction), -402 once more than
+        128 KiB have come without a finished section, -108 for every piece
+        after a failure."""
+        assert self.codec is None
+        return self._ustreams().feed(self._read_encoder, _u8(src), _as(pieces, SPAN_IN_DTYPE),
+                                     _as(tsel, np.uint32), USTREAM_MAX_ENCODERLEN, USTREAM_LATCH)
+
+    def feed_encoder_dev(self, src, pieces, tsel=None):
+        """The same over torch tensors in HBM (src uint8, pieces int64 [nsel, 2]
+        as SPAN_IN_DTYPE records, tsel int32 or None): qh_ustream_join_batch,
+        qh_dtables_apply_batch, qh_ustream_keep_batch.  -> status int32
+        tensor.  One host wait more than ``read_encoder_dev``, for the join's
+        total."""
+        assert self.codec is not None
+        return self._ustreams().feed(self._read_encoder, src, pieces, tsel, USTREAM_MAX_ENCODERLEN,
+                                     USTREAM_LATCH)
+
+    def note_sections(self, emit_result, block_view):
+        """After an emit call: a table with a section that finished may take
+        another 128 KiB of encoder stream, a table with one that failed reads
+        no more (arrays of the object's kind: the result's status, block_view
+        uint32 / int32 or None for table 0)."""
+        st = self._ustreams()
+        if self.codec is None:
+            return st.sections(_as(emit_result["status"], np.int32), _as(block_view, np.uint32))
+        return st.sections(emit_result["status"], block_view)
+
+    def compact_streams(self):
+        """Replaces the streams' log by one that holds the cut instructions
+        alone.  When to call is the caller's decision; after every
+        ``feed_encoder`` it costs the tails alone."""
+        self._ustreams().compact()
+
+    def stream_records(self):
+        """-> (us USTREAM_DTYPE [ntables], log uint8 [nlog]), numpy copies."""
+        return self._ustreams().records()
 
     def _write_decoder(self, emit_result, block_sid, block_view, cancel, dst_cap):
         be = self._be
@@ -1491,10 +1657,17 @@ class EncoderSet:
     and ``compact_refs()`` gives the log's abandoned regions back.  Without
     it acknowledgements are the caller's: between calls it edits
     ``enc_records()`` (krcnt, pin_min, nblocked, nstreams) and stores them
-    back with ``set_enc_records``."""
+    back with ``set_enc_records``.
+
+    With ``streams=True`` (and ``refs=True``) the object also keeps each
+    connection's decoder stream as it arrives (``ustreams``, a HeldStreams):
+    ``feed_decoder`` / ``feed_decoder_dev`` take whatever bytes have come and
+    hold a cut instruction until the rest follows."""
 
     def __init__(self, hard_max, n: int, max_blocked=0, immediate_ack: bool = False, device=None,
-                 strat_none: bool = False, refs: bool = False):
+                 strat_none: bool = False, refs: bool = False, streams: bool = False):
+        if streams and not refs:
+            raise ValueError("streams=True needs refs=True: the decoder stream is read into the reference log")
         self._lib = _load()
         self.n = int(n)
         self.has_refs = bool(refs)
@@ -1521,6 +1694,7 @@ class EncoderSet:
             setattr(self, k, be.put(a.view(np.uint8).copy()))
         for k in ("entries", "dyn_bytes", "keys"):
             setattr(self, k, be.empty(0))
+        self.ustreams = HeldStreams(self._lib, be, self.n) if streams else None
 
     # -- state access (numpy copies; the device form copies through the host)
 
@@ -1689,6 +1863,36 @@ class EncoderSet:
         -> (status int32, consumed int32) tensors.  Asynchronous on the codec
         stream, no host wait."""
         return self._read_decoder(codec, src, streams, tsel)
+
+    def _ustreams(self):
+        if self.ustreams is None:
+            raise ValueError("the set was made without streams=True")
+        return self.ustreams
+
+    def feed_decoder(self, src, pieces, tsel=None):
+        """Decoder-stream bytes as they arrive (host form): piece p is the new
+        bytes of connection tsel[p]'s stream (None: connection p), cut
+        anywhere.  Runs join -> ``read_decoder`` -> keep.  -> status int32
+        per piece (0, -403, -108 once the connection is bad)."""
+        assert self.device is None
+        return self._ustreams().feed(lambda log, joined, sel: self._read_decoder(None, log, joined, sel),
+                                  _u8(src), _as(pieces, SPAN_IN_DTYPE), _as(tsel, np.uint32), 0, 0)
+
+    def feed_decoder_dev(self, codec: HuffmanBatchCodec, src, pieces, tsel=None):
+        """The same over torch tensors in HBM: qh_ustream_join_batch,
+        qh_enc_read_decoder_batch, qh_ustream_keep_batch.  One host wait, for
+        the join's total."""
+        return self._ustreams().feed(lambda log, joined, sel: self._read_decoder(codec, log, joined, sel),
+                                  src, pieces, tsel, 0, 0, codec=codec)
+
+    def compact_streams(self, codec: HuffmanBatchCodec | None = None):
+        """Replaces the decoder streams' log by one that holds the cut
+        instructions alone."""
+        self._ustreams().compact(codec)
+
+    def stream_records(self):
+        """-> (us USTREAM_DTYPE [n], log uint8 [nlog]), numpy copies."""
+        return self._ustreams().records()
 
     def refs_records(self):
         """-> (rv ENC_REFS_DTYPE [n], refs ENC_REF_DTYPE [nrefs]), numpy copies:
