@@ -804,7 +804,11 @@ QH_EXPORT int qh_dtables_apply_batch(
  * and the result does not depend on which entries happened to share bytes.
  * The source arrays are only read: a view copied before the call stays valid
  * against the old arrays, which the caller frees when it no longer needs
- * them.
+ * them.  A hashed index (qh_dyn_index_batch below) names records by their
+ * place in the log, so it does not survive this call: build it again over
+ * the rewritten views.  The same holds for a table that an apply relocated
+ * (its ent_base changed); until then the planners fall back to the scan for
+ * that view by themselves, the record's ent_base no longer being the view's.
  *
  * Returns 0 with the views rewritten and *nentries_out / *nbytes_out the
  * compacted log's lengths (nviews == 0 or every view empty: 0 and 0; null
@@ -1078,6 +1082,98 @@ QH_EXPORT int qh_encode_fields_dyn_batch(
     const uint32_t *field_start, size_t nsections, const qh_plan_dyn *dyn,
     uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
     uint64_t *max_cnt, uint64_t *min_cnt, int where);
+
+/* ---- A hashed index over the keys: lookups that do not scan ---------------
+ * What encoder_qpack_map_find walks (qpack.c:799-835): a hash chain instead
+ * of every live key.  An index covers one view: the entries [lo, hi) of its
+ * live range, cut to the records inside the log as a scan range is; n = hi -
+ * lo.  It is a record (caller-owned, one per view, parallel to views) and a
+ * region of a caller-owned uint32_t slots[] array that starts at slot_off and
+ * holds four blocks: nbuckets name heads, nbuckets exact heads, n name links,
+ * n exact links.  A slot value is (a - lo) + 1; 0 means none.  nbuckets is the
+ * smallest power of two >= max(16, 2 n), cut to the largest power of two <=
+ * max_buckets when max_buckets != 0; a view of more than 2^28 entries gets
+ * nbuckets 0 and no region (it is scanned).  Both bucket functions read only
+ * an entry's qh_dyn_key: the name chain hashes (name_id, name_len), the exact
+ * chain (name_id, name_len, value_len, value_hash); no string byte is read to
+ * build an index.  A chain lists its bucket's entries newest first; the
+ * content is that of: for a from lo up to hi - 1, link[a] = head[b], head[b]
+ * = a, once per chain kind -- byte for byte, whoever builds it.
+ *
+ * A lookup over a section's range [s.lo, s.hi) uses the view's index iff
+ * nbuckets != 0, the record's ent_base is the view's, rec.lo <= s.lo and the
+ * region lies inside [0, nslots); else it is the scan.  Entries of
+ * [max(s.lo, rec.hi), s.hi), inserted after the build, are scanned first (an
+ * older index of a log that has only grown stays usable); then the exact
+ * chain, then, where the line still needs it, the name chain.  A key or a
+ * chain only ever rules entries out: every match is verified as the scan
+ * verifies it.  A chain walk takes at most n steps and a slot value above n
+ * ends it, so whatever slots holds, a lookup may miss a match but reads
+ * nothing outside the arrays and ends.
+ *
+ * An index names records of the log by position: it must be rebuilt after
+ * qh_dtables_compact_batch, and for a table that an apply relocated (its
+ * ent_base changed; the lookup then falls back to the scan by itself). */
+typedef struct qh_dyn_index_rec { /* 48 B, one per view */
+  int64_t ent_base;  /* the view's, when the index was built */
+  uint64_t lo, hi;   /* the entries covered */
+  uint64_t slot_off; /* the region's first slot */
+  uint32_t nbuckets; /* a power of two; 0: no index */
+  uint32_t reserved[3];
+} qh_dyn_index_rec;
+
+typedef struct qh_plan_dyn_index {
+  const qh_dyn_index_rec *recs; /* nviews, parallel to dyn->views */
+  const uint32_t *slots;
+  uint64_t nslots;
+} qh_plan_dyn_index;
+
+/* Builds the indexes of views vsel[0, nsel) (vsel NULL: every view, nsel
+ * ignored) over keys[0, nentries): recs[v] is written per listed view, its
+ * region allocated from *nslots on, in list order; *nslots becomes the slots
+ * in use.  Returns 0; QH_ERR_INVALID_ARGUMENT for an index >= nviews or a
+ * view listed twice (nothing is written); QH_ERR_NOMEM when slots_cap is
+ * short, with *nslots the exact need (nothing else is written).  Host C;
+ * qh_dyn_index_batch is the same on the GPU, recs and slots byte for byte:
+ * QH_WHERE_DEVICE takes HBM pointers and a host nslots, and waits once, for
+ * the total; QH_WHERE_HOST is staged and blocking. */
+QH_EXPORT int qh_qpack_dyn_index(const qh_dtable_view *views, size_t nviews,
+                                 const uint32_t *vsel, size_t nsel,
+                                 const qh_dyn_key *keys, size_t nentries,
+                                 uint32_t max_buckets, qh_dyn_index_rec *recs,
+                                 uint32_t *slots, uint64_t *nslots,
+                                 uint64_t slots_cap);
+QH_EXPORT int qh_dyn_index_batch(qh_ctx *ctx, const qh_dtable_view *views,
+                                 size_t nviews, const uint32_t *vsel,
+                                 size_t nsel, const qh_dyn_key *keys,
+                                 size_t nentries, uint32_t max_buckets,
+                                 qh_dyn_index_rec *recs, uint32_t *slots,
+                                 uint64_t *nslots, uint64_t slots_cap,
+                                 int where);
+
+/* qh_qpack_plan_fields_dyn, qh_plan_fields_dyn_batch and
+ * qh_encode_fields_dyn_batch with the lookups through `index` (a host
+ * struct; its pointers live where dyn's do): the same lines, prefixes,
+ * counts and sections, byte for byte.  index == NULL: the calls above.  The
+ * device forms add no host wait. */
+QH_EXPORT int qh_qpack_plan_fields_dyn_indexed(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, const qh_plan_dyn_index *index,
+    qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt);
+QH_EXPORT int qh_plan_fields_dyn_indexed_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, const qh_plan_dyn_index *index,
+    qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, int where);
+QH_EXPORT int qh_encode_fields_dyn_indexed_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_field *fields, size_t nfields,
+    const uint32_t *field_start, size_t nsections, const qh_plan_dyn *dyn,
+    const qh_plan_dyn_index *index, uint8_t *dst, uint64_t dst_cap,
+    qh_span_in *sections, uint64_t *dst_need, uint64_t *max_cnt,
+    uint64_t *min_cnt, int where);
 
 /* ---- The encoder with dynamic-table inserts, for many connections --------
  * nghttp3_qpack_encoder_encode (qpack.c:1139-1204) for a batch of

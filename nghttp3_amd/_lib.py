@@ -181,6 +181,13 @@ EXPORTED_FUNCTIONS = (
     "qh_qpack_plan_fields_dyn",
     "qh_plan_fields_dyn_batch",
     "qh_encode_fields_dyn_batch",
+    # ... through a hashed index over the views' keys (csrc/qh_index_core.h,
+    # csrc/qh_dyn_index.inc)
+    "qh_qpack_dyn_index",
+    "qh_dyn_index_batch",
+    "qh_qpack_plan_fields_dyn_indexed",
+    "qh_plan_fields_dyn_indexed_batch",
+    "qh_encode_fields_dyn_indexed_batch",
     # the encoder with dynamic-table inserts for many connections
     # (csrc/qh_encconn.c, csrc/qh_encconn.inc)
     "qh_enc_state_init",

@@ -23,6 +23,7 @@
 //   qh_k_blk_*         blocked sections: queued, released, cancelled, compacted
 //   qh_k_part_*        sections in pieces: held, reassembled at fin, compacted
 //   qh_k_us_*          encoder and decoder streams as they arrive: cut instructions held
+//   qh_k_idx_*         the hashed index over the views' keys: count, build
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
 // The kernels from qh_k_encsec_* to qh_k_us_* work a 16-lane group per table,
 // connection or block and leave their totals in one scan header: both are
@@ -83,7 +84,8 @@
 #include "qh_enc_sections.inc"  // whole field sections out: count -> pick -> encode -> write
 #include "qh_emit.inc"          // decoded fields: resolve indices -> scan -> gather names and values
 #include "qh_plan.inc"          // fields -> field lines (the encoder's static-table choice) -> sections
-#include "qh_plan_dyn.inc"      // ... against a frozen dynamic table: keys, references, prefixes
+#include "qh_dyn_index.inc"     // a hashed index over the views' keys: count -> scan -> build
+#include "qh_plan_dyn.inc"      // ... against a frozen dynamic table: keys, references, prefixes, scanned or through the index
 #include "qh_dtset.inc"         // encoder streams of many connections -> dynamic tables in one log
 #include "qh_encconn.inc"       // fields of many connections -> sections, encoder streams and tables, with inserts
 #include "qh_ack.inc"           // acknowledgements: reference log, decoder streams read and written

@@ -88,9 +88,10 @@ struct Layout {
   }
 };
 
-// The most pieces with a host side that a call stages (qh_plan_fields_dyn_batch;
-// the two calls of qh_plan_dyn.inc that stage a table state assert theirs).
-constexpr int kStagePieces = 14;
+// The most pieces with a host side that a call stages
+// (qh_plan_fields_dyn_indexed_batch; the two calls of qh_plan_dyn.inc that
+// stage a table state and its index assert theirs).
+constexpr int kStagePieces = 16;
 
 // A host-memory call's pieces in one device buffer.  Each take is a Layout's
 // over no base, kept as a typed offset: once the buffer of `sized.total` bytes

@@ -20,6 +20,7 @@
  * tests/golden/static_table.json).
  */
 #include <pthread.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/qhuff.h"
@@ -30,7 +31,7 @@
 #define QH_PLAN_TOKEN(t, plain, off, len) qh_qpack_lookup_token((plain) + (off), (len))
 #define QH_PLAN_VALUE(v, plain, off, len) const uint8_t *const v = (plain) + (off)
 #define QH_PLAN_EQ(tb, v, len) (memcmp((tb), (v), (len)) == 0)
-#include "qh_plan_core.h"
+#include "qh_index_core.h"
 
 #define QH_NSTATIC 99
 
@@ -200,11 +201,11 @@ QH_EXPORT int qh_qpack_dyn_keys(const qh_dyn_entry *entries, size_t nentries,
   return 0;
 }
 
-QH_EXPORT int qh_qpack_plan_fields_dyn(
+static int plan_fields_dyn(
     const uint8_t *plain, const qh_span_in *strs, size_t nfields,
     const uint8_t *never, const uint32_t *field_start, size_t nsections,
-    const qh_plan_dyn *dyn, qh_field_line *lines, qh_section_prefix *prefixes,
-    uint64_t *max_cnt, uint64_t *min_cnt) {
+    const qh_plan_dyn *dyn, const qh_plan_dyn_index *index, qh_field_line *lines,
+    qh_section_prefix *prefixes, uint64_t *max_cnt, uint64_t *min_cnt) {
   static const qh_plan_dyn none;
   qh_plan_tab t;
   size_t b, nbytes;
@@ -238,17 +239,18 @@ QH_EXPORT int qh_qpack_plan_fields_dyn(
   t.tok = NULL;
   for (b = 0; b < nsections; ++b) {
     qh_plan_dyn_sec s;
-    uint64_t mx = 0, mn = UINT64_MAX;
+    uint64_t mx = 0, mn = UINT64_MAX, sv;
     size_t i;
     if (field_start[b] > field_start[b + 1] || field_start[b + 1] > nfields) {
       return QH_ERR_INVALID_ARGUMENT;
     }
     qh_plan_dyn_section(dyn, b, &s);
+    sv = dyn->section_view ? dyn->section_view[b] : 0;
     for (i = field_start[b]; i < field_start[b + 1]; ++i) {
       const qh_span_in *nm = &strs[2 * i], *v = &strs[2 * i + 1];
       uint64_t ref1;
-      qh_plan_field_dyn(&t, dyn, &s, plain, nm->off, nm->len, v->off, v->len,
-                        never && never[i], i, &lines[i], &ref1);
+      qh_plan_field_dyn_indexed(&t, dyn, &s, index, sv, plain, nm->off, nm->len, v->off, v->len,
+                                never && never[i], i, &lines[i], &ref1);
       if (ref1) {
         mx = ref1 > mx ? ref1 : mx;
         mn = ref1 < mn ? ref1 : mn;
@@ -262,5 +264,86 @@ QH_EXPORT int qh_qpack_plan_fields_dyn(
       min_cnt[b] = mn;
     }
   }
+  return 0;
+}
+
+QH_EXPORT int qh_qpack_plan_fields_dyn(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, qh_field_line *lines, qh_section_prefix *prefixes,
+    uint64_t *max_cnt, uint64_t *min_cnt) {
+  return plan_fields_dyn(plain, strs, nfields, never, field_start, nsections, dyn, NULL, lines,
+                         prefixes, max_cnt, min_cnt);
+}
+
+/* ---- the hashed index over a view's keys (qh_index_core.h) ---- */
+
+QH_EXPORT int qh_qpack_plan_fields_dyn_indexed(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *never, const uint32_t *field_start, size_t nsections,
+    const qh_plan_dyn *dyn, const qh_plan_dyn_index *index, qh_field_line *lines,
+    qh_section_prefix *prefixes, uint64_t *max_cnt, uint64_t *min_cnt) {
+  if (index && index->nslots && index->slots == NULL) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  return plan_fields_dyn(plain, strs, nfields, never, field_start, nsections, dyn, index, lines,
+                         prefixes, max_cnt, min_cnt);
+}
+
+/* The list checked, then two passes over it: the need, then the records and
+ * their regions (qh_index_build_view: the loop that fixes the content). */
+QH_EXPORT int qh_qpack_dyn_index(const qh_dtable_view *views, size_t nviews,
+                                 const uint32_t *vsel, size_t nsel,
+                                 const qh_dyn_key *keys, size_t nentries,
+                                 uint32_t max_buckets, qh_dyn_index_rec *recs,
+                                 uint32_t *slots, uint64_t *nslots, uint64_t slots_cap) {
+  uint64_t need, at;
+  size_t c;
+  if (nslots == NULL) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (vsel == NULL) {
+    nsel = nviews;
+  }
+  if (nsel && (views == NULL || recs == NULL || (nentries && keys == NULL))) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (slots_cap && slots == NULL) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (vsel && nsel) {
+    uint8_t *const seen = calloc(nviews ? nviews : 1, 1);
+    if (seen == NULL) {
+      return QH_ERR_FATAL;
+    }
+    for (c = 0; c < nsel && vsel[c] < nviews && !seen[vsel[c]]; ++c) {
+      seen[vsel[c]] = 1;
+    }
+    free(seen);
+    if (c < nsel) {
+      return QH_ERR_INVALID_ARGUMENT;
+    }
+  }
+  need = *nslots;
+  for (c = 0; c < nsel; ++c) {
+    qh_dyn_index_rec r;
+    qh_index_rec_of(&views[vsel ? vsel[c] : c], nentries, max_buckets, &r);
+    need += qh_index_need(r.hi - r.lo, r.nbuckets);
+  }
+  if (need > slots_cap) {
+    *nslots = need;
+    return QH_ERR_NOMEM;
+  }
+  at = *nslots;
+  for (c = 0; c < nsel; ++c) {
+    const size_t v = vsel ? vsel[c] : c;
+    qh_dyn_index_rec r;
+    qh_index_rec_of(&views[v], nentries, max_buckets, &r);
+    r.slot_off = at;
+    at += qh_index_need(r.hi - r.lo, r.nbuckets);
+    qh_index_build_view(keys, &r, slots);
+    recs[v] = r;
+  }
+  *nslots = at;
   return 0;
 }

@@ -55,6 +55,8 @@ ACCT_DTYPE = np.dtype([("hard_max", "<u8"), ("cap", "<u8"), ("size", "<u8"), ("r
 VIEW_DTYPE = np.dtype([("ent_base", "<i8"), ("live_lo", "<u8"), ("insert_count", "<u8"),
                        ("max_entries", "<u8"), ("reserved", "<u8")])
 assert FIELD_DTYPE.itemsize == 32 and DYN_ENTRY_DTYPE.itemsize == 32 and VIEW_DTYPE.itemsize == 40
+DYN_INDEX_REC_DTYPE = np.dtype([("ent_base", "<i8"), ("lo", "<u8"), ("hi", "<u8"), ("slot_off", "<u8"),
+                                ("nbuckets", "<u4"), ("reserved", "<u4", (3,))])
 DYN_KEY_DTYPE = np.dtype([("name_id", "<u4"), ("name_len", "<u4"), ("value_len", "<u4"),
                           ("value_hash", "<u4")])
 assert DYN_KEY_DTYPE.itemsize == 16
@@ -103,6 +105,11 @@ class qh_plan_dyn(ctypes.Structure):
                 ("dyn_entries", ctypes.c_void_p), ("nentries", ctypes.c_size_t),
                 ("dyn_keys", ctypes.c_void_p), ("dyn_bytes", ctypes.c_void_p),
                 ("nbytes", ctypes.c_uint64)]
+
+
+class qh_plan_dyn_index(ctypes.Structure):
+    """include/qhuff.h qh_plan_dyn_index (the index of a planning call)."""
+    _fields_ = [("recs", ctypes.c_void_p), ("slots", ctypes.c_void_p), ("nslots", ctypes.c_uint64)]
 
 
 SECTIONS_DTABLE0 = 0x1
@@ -190,6 +197,12 @@ def _load():
         lib.qh_encode_fields_dyn_batch.argtypes = [vp, vp, vp, sz, vp, sz, dynp, vp, u64, vp,
                                                    c.POINTER(u64), vp, vp, i32]
         lib.qh_encode_fields_dyn_batch.restype = i32
+        idxp = c.POINTER(qh_plan_dyn_index)
+        _pair(lib, "dyn_index", [vp, sz, vp, sz, vp, sz, c.c_uint32, vp, vp, c.POINTER(u64), u64])
+        _pair(lib, "plan_fields_dyn_indexed", [vp, vp, sz, vp, vp, sz, dynp, idxp, vp, vp, vp, vp])
+        lib.qh_encode_fields_dyn_indexed_batch.argtypes = [vp, vp, vp, sz, vp, sz, dynp, idxp, vp, u64, vp,
+                                                           c.POINTER(u64), vp, vp, i32]
+        lib.qh_encode_fields_dyn_indexed_batch.restype = i32
         lib.qh_dtable_new.argtypes = [c.POINTER(vp), u64]
         lib.qh_dtable_new.restype = i32
         lib.qh_dtable_del.argtypes = [vp]
@@ -898,12 +911,24 @@ class DynamicTable:
         self._keys = have
         return have
 
+    def index(self, rebuild=False, max_buckets=0):
+        """The hashed index over the current view's keys (dyn_index): built at
+        the first call and kept; only ``rebuild=True`` builds it again.  The
+        log never relocates, so an older index stays usable after later
+        applies: the planners scan the entries inserted since and walk the
+        chains for the rest."""
+        if rebuild or getattr(self, "_index", None) is None:
+            self._index = dyn_index(self.view(), self.keys(), max_buckets=max_buckets)
+        return self._index
+
     def to_device(self, device):
         """-> {"views" uint8 [40], "entries" uint8 [n * 32], "bytes" uint8,
-        "keys" uint8 [n * 16], "nentries", "nbytes"} torch tensors on
-        `device` holding the current state, the log and its keys.  Only the
+        "keys" uint8 [n * 16], "nentries", "nbytes", "index"} torch tensors
+        on `device` holding the current state, the log and its keys.  Only the
         records, keys and bytes appended since the last upload are copied
-        (the tensors are kept, with room to grow)."""
+        (the tensors are kept, with room to grow).  "index": the tensors of
+        the index ``index()`` keeps ({"recs" uint8 [48], "slots" uint8,
+        "nslots"}), uploaded once per build; None when none was built."""
         import torch
         ents, byts, keys = self.entries(), self.bytes(), self.keys()
         d = self._dev
@@ -922,8 +947,15 @@ class DynamicTable:
                 d[key][d[have]:host.size] = torch.from_numpy(host[d[have]:].copy()).to(device)
                 d[have] = host.size
         views = torch.from_numpy(self.view().view(np.uint8).copy()).to(device)
+        ix = getattr(self, "_index", None)
+        if ix is None:
+            d["index"] = d["index_of"] = None
+        elif d.get("index_of") is not ix:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(device)
+            d["index"] = {"recs": up(ix["recs"]), "slots": up(ix["slots"]), "nslots": ix["nslots"]}
+            d["index_of"] = ix
         return {"views": views, "entries": d["entries"], "bytes": d["bytes"], "keys": d["keys"],
-                "nentries": int(ents.size), "nbytes": int(byts.size)}
+                "nentries": int(ents.size), "nbytes": int(byts.size), "index": d["index"]}
 
 
 class HeldStreams:
@@ -1618,6 +1650,7 @@ class DynamicTableSet:
         self.views = views if extra_views is None else be.own(views[:own])
         self.entries, self.dyn_bytes, self.nentries, self.nbytes = ents, byts, ne, nb
         self._nkeys = 0  # (keys depend on content alone: keys() computes them over the new log)
+        self._index_recs = None  # (an index names records by position: index() builds it again)
         if not be.dev:
             self._keys = be.empty(0)  # (an array handed out by keys() before stays as it was)
         return None if extra_views is None else be.own(views[own:])
@@ -1635,6 +1668,41 @@ class DynamicTableSet:
             self._nkeys = n
         keys = self._keys[:n * 16]
         return keys if be.dev else keys.view(DYN_KEY_DTYPE)
+
+    def index(self, tsel=None, max_buckets=0):
+        """The hashed index over the tables' keys (qh_dyn_index_batch /
+        qh_qpack_dyn_index): built for the tables `tsel` (uint32 indices;
+        None: every table, from an empty slots array), the other tables'
+        records and regions kept.  -> {"recs", "slots", "nslots"} for the
+        planners' ``index=`` (uint8 tensors on the device form;
+        DYN_INDEX_REC_DTYPE records and uint32 slots on the host).  A table's
+        index is built only here: after ``compact()`` every index has to be
+        built again (the set drops what it kept), and after more inserts an
+        older one stays usable until the caller asks for a new one."""
+        be = self._be
+        ptr = be.ptr
+        keys = self.keys()
+        if not be.dev:
+            tsel = _as(tsel, np.uint32)
+        if getattr(self, "_index_recs", None) is None or tsel is None:
+            self._index_recs, self._index_slots, self._nslots = be.zeros(max(self.ntables, 1) * 48), None, 0
+        keep, old, recs = self._nslots, self._index_slots, self._index_recs
+        nsel = 0 if tsel is None else be.size(tsel)
+
+        def call(outs):
+            (slots,) = outs
+            if slots is not None and keep:
+                slots[:keep * 4] = old[:keep * 4]
+            ns = ctypes.c_uint64(keep)
+            rv = be.call(self._lib, "dyn_index", ptr(self.views), self.ntables, be.list_ptr(tsel), nsel,
+                         ptr(keys), self.nentries, max_buckets, ptr(recs), ptr(slots), ctypes.byref(ns),
+                         be.size(slots) // 4)
+            return rv, (int(ns.value),)
+        (self._index_slots,), (self._nslots,) = be.sized("dyn_index", call, ((4, 1024),), be.empty)
+        if be.dev:
+            return {"recs": recs, "slots": self._index_slots, "nslots": self._nslots}
+        return {"recs": recs.view(DYN_INDEX_REC_DTYPE)[:self.ntables],
+                "slots": self._index_slots.view(np.uint32), "nslots": self._nslots}
 
 
 class EncoderSet:
@@ -2017,6 +2085,66 @@ def dyn_keys_dev(codec: HuffmanBatchCodec, entries, nentries, dyn_bytes, nbytes,
                                      p(keys), _lib.QH_WHERE_DEVICE), "qh_dyn_keys_batch")
 
 
+def _dyn_index(be, views, nviews, vsel, keys, nentries, max_buckets):
+    lib = _load()
+    ptr = be.ptr
+    recs = be.zeros(max(nviews, 1) * DYN_INDEX_REC_DTYPE.itemsize)
+    nsel = 0 if vsel is None else be.size(vsel)
+
+    def call(outs):
+        (slots,) = outs
+        ns = ctypes.c_uint64(0)
+        rv = be.call(lib, "dyn_index", ptr(views), nviews, be.list_ptr(vsel), nsel, ptr(keys), nentries,
+                     max_buckets, ptr(recs), ptr(slots), ctypes.byref(ns), be.size(slots) // 4)
+        return rv, (int(ns.value),)
+    (slots,), (ns,) = be.sized("dyn_index", call, ((4, 1024),), be.empty)
+    return recs, slots, ns
+
+
+def dyn_index(views, keys, vsel=None, max_buckets=0):
+    """qh_qpack_dyn_index: the hashed index over the keys (DYN_KEY_DTYPE, the
+    whole log's) of views (VIEW_DTYPE) `vsel` (uint32 indices; None: every
+    view) -> {"recs": DYN_INDEX_REC_DTYPE [nviews], "slots": uint32,
+    "nslots": int}, what the planners take as ``index=``.  `max_buckets`
+    (0: no limit) cuts every view's bucket count to a power of two."""
+    vw = np.ascontiguousarray(views, dtype=VIEW_DTYPE).reshape(-1)
+    ks = np.ascontiguousarray(keys, dtype=DYN_KEY_DTYPE).reshape(-1)
+    recs, slots, ns = _dyn_index(Backend(), vw.view(np.uint8), vw.size, _as(vsel, np.uint32),
+                                 ks.view(np.uint8), ks.size, max_buckets)
+    return {"recs": recs.view(DYN_INDEX_REC_DTYPE)[:vw.size], "slots": slots.view(np.uint32), "nslots": ns}
+
+
+def dyn_index_dev(codec: HuffmanBatchCodec, views, keys, nentries, vsel=None, max_buckets=0):
+    """qh_dyn_index_batch over torch tensors in HBM (views uint8 [nviews *
+    40], keys uint8 [>= nentries * 16], vsel int32 or None) -> {"recs" uint8
+    [nviews * 48], "slots" uint8 [>= nslots * 4], "nslots"}.  A sizing call
+    and the build: each waits once, for the total."""
+    be = Backend(views.device, codec)
+    recs, slots, ns = _dyn_index(be, views, views.numel() // VIEW_DTYPE.itemsize, vsel, keys, nentries,
+                                 max_buckets)
+    return {"recs": recs, "slots": slots, "nslots": ns}
+
+
+def _plan_index(index, d):
+    """-> (qh_plan_dyn_index or None, the arrays it points into) from a
+    dyn_index / dyn_index_dev result (or any dict of "recs", "slots",
+    "nslots": numpy arrays or torch tensors), for the table states d."""
+    if index is None or d is None:
+        return None, ()
+    recs, slots = index["recs"], index["slots"]
+    if isinstance(recs, np.ndarray):
+        recs = np.ascontiguousarray(recs, dtype=DYN_INDEX_REC_DTYPE).reshape(-1)
+        slots = np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1)
+        if recs.size < d.nviews or slots.size < index["nslots"]:
+            raise ValueError("index smaller than the views or than nslots")
+        p = lambda a: a.ctypes.data if a.size else None
+    else:
+        if recs.numel() < d.nviews * DYN_INDEX_REC_DTYPE.itemsize or slots.numel() < index["nslots"] * 4:
+            raise ValueError("index smaller than the views or than nslots")
+        p = lambda t: t.data_ptr() if t.numel() else None
+    return qh_plan_dyn_index(p(recs), p(slots), int(index["nslots"])), (recs, slots)
+
+
 def _plan_dyn_host(table, views, section_view, ref_limit, entries, keys, dyn_bytes):
     """-> (qh_plan_dyn or None, the arrays it points into) from host arrays:
     `table` (a DynamicTable: its log, keys and, without `views`, its current
@@ -2066,14 +2194,17 @@ def _plan_dyn_dev(table, device, views, section_view, ref_limit, entries, keys, 
 
 
 def plan_fields_dyn(plain, strs, never, field_start, table=None, views=None, section_view=None,
-                    ref_limit=None, entries=None, keys=None, dyn_bytes=None, codec=None):
+                    ref_limit=None, entries=None, keys=None, dyn_bytes=None, codec=None, index=None):
     """qh_qpack_plan_fields_dyn: the fields (strs[2i], strs[2i+1]) of
     sections [field_start[b], field_start[b+1]) planned against a frozen
     dynamic table (`table`, or views / entries / keys / dyn_bytes; section b
     against views[section_view[b]], referencing entries a + 1 <=
     ref_limit[b]).  -> dict: lines, prefixes (PREFIX_DTYPE), max_cnt, min_cnt.
     With `codec` the same on the GPU over the host arrays
-    (qh_plan_fields_dyn_batch, staged)."""
+    (qh_plan_fields_dyn_batch, staged).  With `index` (dyn_index's result,
+    or a table's ``index()``) the lookups walk its chains instead of
+    scanning (qh_qpack_plan_fields_dyn_indexed /
+    qh_plan_fields_dyn_indexed_batch): the same result."""
     lib = _load()
     plain = _plain(plain)
     strs = np.ascontiguousarray(strs, dtype=SPAN_IN_DTYPE)
@@ -2087,35 +2218,40 @@ def plan_fields_dyn(plain, strs, never, field_start, table=None, views=None, sec
     mx = np.zeros(max(nsec, 1), dtype=np.uint64)
     mn = np.zeros(max(nsec, 1), dtype=np.uint64)
     dp = None if d is None else ctypes.byref(d)
-    args = (_vp(plain), _vp(strs), nf, None if nv is None else _vp(nv), _vp(fs), nsec, dp, _vp(lines),
-            _vp(pfx), _vp(mx), _vp(mn))
+    x, xkeep = _plan_index(index, d)
+    stem = "plan_fields_dyn" if x is None else "plan_fields_dyn_indexed"
+    args = (_vp(plain), _vp(strs), nf, None if nv is None else _vp(nv), _vp(fs), nsec, dp) + \
+        (() if x is None else (ctypes.byref(x),)) + (_vp(lines), _vp(pfx), _vp(mx), _vp(mn))
     if codec is None:
-        _lib.check(lib.qh_qpack_plan_fields_dyn(*args), "qh_qpack_plan_fields_dyn")
+        _lib.check(getattr(lib, "qh_qpack_" + stem)(*args), "qh_qpack_" + stem)
     else:
-        _lib.check(lib.qh_plan_fields_dyn_batch(codec._ctx, *args, _lib.QH_WHERE_HOST),
-                   "qh_plan_fields_dyn_batch")
-    del keep
+        _lib.check(getattr(lib, "qh_%s_batch" % stem)(codec._ctx, *args, _lib.QH_WHERE_HOST),
+                   "qh_%s_batch" % stem)
+    del keep, xkeep
     return {"lines": lines[:nf], "prefixes": pfx[:nsec], "max_cnt": mx[:nsec], "min_cnt": mn[:nsec]}
 
 
 def plan_fields_dyn_dev(codec: HuffmanBatchCodec, plain, strs, never, field_start, lines, prefixes,
                         max_cnt=None, min_cnt=None, table=None, views=None, section_view=None,
                         ref_limit=None, entries=None, keys=None, dyn_bytes=None, nentries=None,
-                        nbytes=None):
+                        nbytes=None, index=None):
     """Device-resident form over torch tensors (plan_fields_dev's, plus
     field_start int32 [nsec + 1], prefixes uint8 [nsec * 24], max_cnt /
     min_cnt int64 [nsec] or None); asynchronous on the codec stream, no host
-    wait."""
+    wait.  `index`: dyn_index_dev's result, or ``to_device(...)["index"]``
+    (qh_plan_fields_dyn_indexed_batch)."""
     lib = _load()
     p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     d, keep = _plan_dyn_dev(table, plain.device, views, section_view, ref_limit, entries, keys,
                             dyn_bytes, nentries, nbytes)
-    _lib.check(lib.qh_plan_fields_dyn_batch(codec._ctx, p(plain), p(strs), strs.shape[0] // 2,
-                                            p(never), p(field_start), field_start.shape[0] - 1,
-                                            None if d is None else ctypes.byref(d), p(lines),
-                                            p(prefixes), p(max_cnt), p(min_cnt),
-                                            _lib.QH_WHERE_DEVICE), "qh_plan_fields_dyn_batch")
-    return keep
+    x, xkeep = _plan_index(index, d)
+    stem = "qh_plan_fields_dyn_batch" if x is None else "qh_plan_fields_dyn_indexed_batch"
+    args = (codec._ctx, p(plain), p(strs), strs.shape[0] // 2, p(never), p(field_start),
+            field_start.shape[0] - 1, None if d is None else ctypes.byref(d)) + \
+        (() if x is None else (ctypes.byref(x),)) + \
+        (p(lines), p(prefixes), p(max_cnt), p(min_cnt), _lib.QH_WHERE_DEVICE)
+    _lib.check(getattr(lib, stem)(*args), stem)
+    return keep + xkeep
 
 
 def static_entry(idx: int):
@@ -2226,18 +2362,20 @@ class FieldSectionEncoder:
         return need.value
 
     def encode_fields(self, plain, fields, field_start, table=None, views=None, section_view=None,
-                      ref_limit=None, entries=None, keys=None, dyn_bytes=None):
+                      ref_limit=None, entries=None, keys=None, dyn_bytes=None, index=None):
         """Host arrays: fields (FIELD_DTYPE; offsets into plain) of sections
         [field_start[b], field_start[b + 1]) -> (dst uint8, sections
         SPAN_IN_DTYPE), the bytes of write_sections(plan_fields(...)).  With
         `table` (a DynamicTable) or `views` (with entries / keys / dyn_bytes;
         `section_view` / `ref_limit` as plan_fields_dyn takes them) the
         fields are planned against it (qh_encode_fields_dyn_batch) and the
-        result is (dst, sections, max_cnt, min_cnt)."""
+        result is (dst, sections, max_cnt, min_cnt); `index` (dyn_index's
+        result) takes the lookups through the hashed index
+        (qh_encode_fields_dyn_indexed_batch)."""
         lib = _load()
         if table is not None or views is not None:
             return self._encode_fields_dyn(plain, fields, field_start, table, views, section_view,
-                                           ref_limit, entries, keys, dyn_bytes)
+                                           ref_limit, entries, keys, dyn_bytes, index)
         plain = _plain(plain)
         fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
         if fields.size == 0:
@@ -2251,7 +2389,7 @@ class FieldSectionEncoder:
         return dst, sections[:nsec]
 
     def _encode_fields_dyn(self, plain, fields, field_start, table, views, section_view, ref_limit,
-                           entries, keys, dyn_bytes):
+                           entries, keys, dyn_bytes, index=None):
         lib = _load()
         plain = _plain(plain)
         fields = np.ascontiguousarray(fields, dtype=FIELD_DTYPE)
@@ -2263,17 +2401,20 @@ class FieldSectionEncoder:
         sections = np.zeros(max(nsec, 1), dtype=SPAN_IN_DTYPE)
         mx = np.zeros(max(nsec, 1), dtype=np.uint64)
         mn = np.zeros(max(nsec, 1), dtype=np.uint64)
-        fn = lib.qh_encode_fields_dyn_batch
-        dst = self._with_dst("qh_encode_fields_dyn_batch", lambda dst, cap, need: fn(
+        x, xkeep = _plan_index(index, d)
+        stem = "qh_encode_fields_dyn_batch" if x is None else "qh_encode_fields_dyn_indexed_batch"
+        fn = getattr(lib, stem)
+        dst = self._with_dst(stem, lambda dst, cap, need: fn(
             self.codec._ctx, _vp(plain), _vp(fields), fields.size, _vp(field_start), nsec,
-            None if d is None else ctypes.byref(d), dst, cap, _vp(sections), need, _vp(mx), _vp(mn),
-            _lib.QH_WHERE_HOST))
-        del keep
+            None if d is None else ctypes.byref(d), *(() if x is None else (ctypes.byref(x),)), dst, cap,
+            _vp(sections), need, _vp(mx), _vp(mn), _lib.QH_WHERE_HOST))
+        del keep, xkeep
         return dst, sections[:nsec], mx[:nsec], mn[:nsec]
 
     def encode_fields_dev(self, plain, fields, nfields, field_start, dst, sections, table=None,
                           views=None, section_view=None, ref_limit=None, max_cnt=None, min_cnt=None,
-                          entries=None, keys=None, dyn_bytes=None, nentries=None, nbytes=None):
+                          entries=None, keys=None, dyn_bytes=None, nentries=None, nbytes=None,
+                          index=None):
         """Device-resident form over torch tensors, emit_fields_dev's as they
         are: plain uint8 (its `out`), fields uint8 [>= nfields * 32],
         field_start int32 [nsec + 1], dst uint8, sections int64 [nsec, 2].
@@ -2281,7 +2422,9 @@ class FieldSectionEncoder:
         with to_device) or views / entries / keys / dyn_bytes tensors the
         fields are planned against the table (qh_encode_fields_dyn_batch);
         max_cnt / min_cnt (int64 [nsec]) then receive every section's
-        reference counts, and the result is (dst_need, max_cnt, min_cnt)."""
+        reference counts, and the result is (dst_need, max_cnt, min_cnt);
+        `index` (dyn_index_dev's result) takes the lookups through the
+        hashed index (qh_encode_fields_dyn_indexed_batch)."""
         lib = _load()
         p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         need = ctypes.c_uint64(0)
@@ -2294,12 +2437,14 @@ class FieldSectionEncoder:
                 max_cnt = torch.empty(max(nsec, 1), dtype=torch.int64, device=plain.device)
             if min_cnt is None:
                 min_cnt = torch.empty(max(nsec, 1), dtype=torch.int64, device=plain.device)
-            rv = lib.qh_encode_fields_dyn_batch(self.codec._ctx, p(plain), p(fields), int(nfields),
-                                                p(field_start), nsec, ctypes.byref(d), p(dst),
-                                                dst.numel(), p(sections), ctypes.byref(need),
-                                                p(max_cnt), p(min_cnt), _lib.QH_WHERE_DEVICE)
-            _lib.check(rv, "qh_encode_fields_dyn_batch")
-            del keep  # (the call has waited for the totals)
+            x, xkeep = _plan_index(index, d)
+            stem = "qh_encode_fields_dyn_batch" if x is None else "qh_encode_fields_dyn_indexed_batch"
+            rv = getattr(lib, stem)(self.codec._ctx, p(plain), p(fields), int(nfields), p(field_start), nsec,
+                                    ctypes.byref(d), *(() if x is None else (ctypes.byref(x),)), p(dst),
+                                    dst.numel(), p(sections), ctypes.byref(need), p(max_cnt), p(min_cnt),
+                                    _lib.QH_WHERE_DEVICE)
+            _lib.check(rv, stem)
+            del keep, xkeep  # (the call has waited for the totals)
             return need.value, max_cnt, min_cnt
         rv = lib.qh_encode_fields_batch(self.codec._ctx, p(plain), p(fields), int(nfields),
                                         p(field_start), field_start.shape[0] - 1, p(dst), dst.numel(),
