@@ -27,7 +27,7 @@ $(LIBDIR)/qh_scalar.o: $(CSRC)/qh_scalar.c $(CSRC)/qh_tables.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_scratch.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_index_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_enc_core.h $(CSRC)/qh_ack_core.h $(CSRC)/qh_blocked_core.h $(CSRC)/qh_partial_core.h $(CSRC)/qh_ustream_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
+$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_scratch.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_index_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_enc_core.h $(CSRC)/qh_enc_index_core.h $(CSRC)/qh_ack_core.h $(CSRC)/qh_blocked_core.h $(CSRC)/qh_partial_core.h $(CSRC)/qh_ustream_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -47,7 +47,7 @@ $(LIBDIR)/qh_dtset.o: $(CSRC)/qh_dtset.c $(CSRC)/qh_dtable_core.h $(CSRC)/qh_emi
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/qh_encconn.o: $(CSRC)/qh_encconn.c $(CSRC)/qh_enc_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_qpack_core.h include/qhuff.h
+$(LIBDIR)/qh_encconn.o: $(CSRC)/qh_encconn.c $(CSRC)/qh_enc_core.h $(CSRC)/qh_enc_index_core.h $(CSRC)/qh_index_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_qpack_core.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 

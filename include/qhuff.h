@@ -1309,6 +1309,124 @@ QH_EXPORT int qh_encode_conns_batch(
     uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
     int where);
 
+/* ---- The connection encoder's hashed index, kept up per insert -----------
+ * What encoder_qpack_map_find walks (qpack.c:799-835) and ent->sum (:2106),
+ * for the tables qh_qpack_encode_conns inserts into: a hash chain per bucket
+ * in place of a scan of every live key, and can_reference, check_draining and
+ * can_index from a running sum in O(1).  Opt-in per connection; a
+ * qh_dyn_index_rec cannot serve here (it names records by log position, and
+ * every inserting call moves the table).
+ *
+ * Entries are named by insert number a (the view's absolute index), never by
+ * log position, so the index survives the relocation of an inserting call and
+ * the rebasing of a compaction; it is never rebuilt.  One qh_enc_index_rec per
+ * connection (caller-owned, beside views, acct and enc) owns a fixed region of
+ * a caller-owned uint32_t slots[] array, sized once from acct.hard_max:
+ *   ring      the smallest power of two >= max(16, hard_max / 32): an entry
+ *             costs at least 32 bytes, so at most hard_max / 32 are live (under
+ *             a pending capacity reduction too) and no two live entries share
+ *             a mod ring.  ring == 0: the connection is scanned (hard_max / 32
+ *             < min_entries, or more than 2^28).
+ *   nbuckets  qh_qpack_dyn_index's rule over ring: the smallest power of two
+ *             >= max(16, 2 ring), cut to the largest power of two <=
+ *             max_buckets when that is not 0.
+ * The region, from slot_off on, 2 nbuckets + 4 ring slots:
+ *   [0, nbuckets)                 name heads, by qh_index_name_bucket
+ *   [nbuckets, 2 nbuckets)        exact heads, by qh_index_exact_bucket
+ *   then ring name links, ring exact links, and ring cumulative-space words
+ *   of 64 bits (two slots, low half first), each at a mod ring.
+ * A head or link value names an entry: 0 is none, else 0x80000000 | (a mod
+ * 2^31), read back as the one number below the point it is read from (hi for
+ * a head, the entry before for a link) with those 31 bits.  Entry a's
+ * cumulative word is the space (name_len + value_len + 32) of the entries
+ * inserted before it, from the oldest entry that was live when the index last
+ * had no linked live entry (for a connection indexed since it was fresh: from
+ * entry 0); only differences are used.  Linking entry a is, per chain kind,
+ * link[a mod ring] = head[b]; head[b] = value(a), in insert order -- byte for
+ * byte, host or device.  hi: every live entry below it is linked.
+ *
+ * Eviction writes nothing.  A value read on a chain is stale, and ends the
+ * walk, when it names an entry below live_lo or one not older than the step
+ * before (chains descend; a head's step before is hi).  A walk takes at most
+ * ring steps; every slot read lies in the region, which is checked once
+ * against nslots, and every log read in the live range.  So whatever slots
+ * holds, a lookup may miss a match, but it reads nothing outside the arrays
+ * and it ends.  A key or a chain only rules entries out: a match is verified
+ * as the scan verifies it (key, lengths, the name's bytes when the token is
+ * -1, the value's hash, the value's bytes).  A record that is unusable --
+ * ring 0 or not a power of two, ring < hard_max / 32, nbuckets 0 or not a
+ * power of two, a region outside [0, nslots), hi above the insert count --
+ * makes its connection fall back to the scan, by itself.
+ *
+ * The lookup: entries of [hi, insert_count) (an un-indexed call ran in
+ * between) and those inserted by this call are scanned newest first as ever;
+ * below hi the exact chain is walked (not in never-index mode), then the name
+ * chain when the line can still use a name (no exact match, no static name
+ * reference).  The space from a candidate to the newest entry is size -
+ * (cum[a] - cum[live_lo]).  The head sum of can_index is a difference of two
+ * cumulative words.  (A record whose strings leave the byte log fails its
+ * connection when a lookup reads it; the chains read fewer records than the
+ * scan.) */
+typedef struct qh_enc_index_rec { /* 32 B, one per connection */
+  uint64_t slot_off; /* the region's first slot */
+  uint64_t hi;       /* every live entry below it is linked */
+  uint32_t ring;     /* a power of two; 0: the connection is scanned */
+  uint32_t nbuckets; /* a power of two */
+  uint64_t reserved;
+} qh_enc_index_rec;
+
+/* Sizes and allocates the regions of connections tsel[0, nsel) (NULL: every
+ * connection, nsel ignored) from *nslots on, in list order, zeroes them, links
+ * the entries live now (keys[0, nentries) are the log's) and writes recs[t]:
+ * a set can adopt an index mid-life.  A connection with hard_max / 32 <
+ * min_entries, or whose view leaves the log, gets ring 0 and no region.
+ * *nslots becomes the slots in use.  QH_ERR_INVALID_ARGUMENT for an index >=
+ * ntables or a connection listed twice, and QH_ERR_NOMEM when slots_cap is
+ * short, *nslots then the exact need: nothing else is written.  Host C;
+ * qh_enc_index_init_batch is the same over HBM pointers (where must be
+ * QH_WHERE_DEVICE; nslots a host scalar), recs and slots byte for byte, and
+ * waits once, for the total. */
+QH_EXPORT int qh_qpack_enc_index_init(const qh_dtable_view *views, const qh_dtable_acct *acct,
+                                      size_t ntables, const uint32_t *tsel, size_t nsel,
+                                      const qh_dyn_key *keys, size_t nentries, uint64_t min_entries,
+                                      uint32_t max_buckets, qh_enc_index_rec *recs, uint32_t *slots,
+                                      uint64_t *nslots, uint64_t slots_cap);
+QH_EXPORT int qh_enc_index_init_batch(qh_ctx *ctx, const qh_dtable_view *views,
+                                      const qh_dtable_acct *acct, size_t ntables,
+                                      const uint32_t *tsel, size_t nsel, const qh_dyn_key *keys,
+                                      size_t nentries, uint64_t min_entries, uint32_t max_buckets,
+                                      qh_enc_index_rec *recs, uint32_t *slots, uint64_t *nslots,
+                                      uint64_t slots_cap, int where);
+
+/* qh_qpack_encode_conns / qh_encode_conns_batch with the lookups through
+ * recs[ntables] and slots[0, nslots): every output is the un-indexed call's
+ * byte for byte (lines, prefixes, counts, sections, streams, status, views,
+ * acct, enc, log, keys).  recs == NULL: the calls above.  The walk writes no
+ * index; the commit, which runs only when the four caps hold, links every
+ * entry of [max(hi, live_lo), insert_count) in insert order after relocating
+ * and sets hi.  On QH_ERR_NOMEM, and for a failed connection, recs and slots
+ * are untouched.  The device form adds no host wait. */
+QH_EXPORT int qh_qpack_encode_conns_indexed(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields, const uint8_t *nvflags,
+    const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
+    const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
+    qh_dtable_view *views, qh_dtable_acct *acct, qh_enc_state *enc, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
+    qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
+    qh_enc_index_rec *recs, uint32_t *slots, uint64_t nslots);
+QH_EXPORT int qh_encode_conns_indexed_batch(
+    qh_ctx *ctx, const uint8_t *plain, const qh_span_in *strs, size_t nfields,
+    const uint8_t *nvflags, const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
+    const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
+    qh_dtable_view *views, qh_dtable_acct *acct, qh_enc_state *enc, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
+    qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
+    qh_enc_index_rec *recs, uint32_t *slots, uint64_t nslots, int where);
+
 /* ---- Acknowledgements: the decoder stream read and written per batch -----
  * The encoder's side of nghttp3_qpack_encoder_read_decoder (qpack.c:2545-2641)
  * with ack_header (:2329-2372), add_icnt (:2374-2383), cancel_stream

@@ -194,6 +194,11 @@ EXPORTED_FUNCTIONS = (
     "qh_enc_state_set_capacity",
     "qh_qpack_encode_conns",
     "qh_encode_conns_batch",
+    # ... with a hashed index per connection, kept up per insert
+    "qh_qpack_enc_index_init",
+    "qh_enc_index_init_batch",
+    "qh_qpack_encode_conns_indexed",
+    "qh_encode_conns_indexed_batch",
     # acknowledgements: the reference log and the decoder stream's two ends
     # (csrc/qh_ack.c, csrc/qh_ack.inc)
     "qh_enc_refs_init",

@@ -523,13 +523,18 @@ QH_HD static inline void qh_enc_field_finish(qh_enc_walk *w, const qh_enc_tab *T
  * can_reference :791-795 (the space from an entry to the newest grows with
  * age, so the walk ends at the first entry beyond the capacity).  An entry
  * is taken only if its key agrees and its bytes are equal (the name's only
- * when the token is -1, :814-816). */
-QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
-                                     const qh_enc_field *f, uint64_t name_off, uint32_t name_len,
-                                     uint64_t value_off, uint32_t value_len, qh_enc_found *r) {
+ * when the token is -1, :814-816).
+ * qh_enc_find_from is that walk over the entries [lo, count) alone: 1 when
+ * the lookup is over (a match that ends it, the capacity, a bad record), 0
+ * when the entries below lo could still matter (qh_enc_index_core.h goes on
+ * through the chains). */
+QH_HD static inline int qh_enc_find_from(const qh_enc_tab *T, const qh_enc_walk *w,
+                                         const qh_enc_field *f, uint64_t name_off,
+                                         uint32_t name_len, uint64_t value_off, uint32_t value_len,
+                                         uint64_t lo, qh_enc_found *r) {
   const int name_only = f->mode == QH_ENC_MODE_NEVER;
   uint64_t a, suffix = 0;
-  for (a = w->count; a-- > w->live_lo;) {
+  for (a = w->count; a-- > lo;) {
     const qh_dyn_key k = qh_enc_key(T, w, a);
     const int refable = w->allow_blocking || a + 1 <= w->e.krcnt; /* :819 */
     const int vlen_ok = qh_dyn_key_value(&k, value_len);
@@ -537,7 +542,7 @@ QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
     uint32_t nl, vl;
     suffix += qh_enc_key_space(&k);
     if (suffix > w->cap) {
-      return;
+      return 1;
     }
     if (!qh_dyn_key_name(&k, f->name_id, name_len)) {
       continue;
@@ -550,7 +555,7 @@ QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
     }
     if (qh_enc_entry_strs(T, w, a, &np, &nl, &vp, &vl) != 0) {
       r->bad = 1;
-      return;
+      return 1;
     }
     if (nl != name_len ||
         (f->token == -1 && !qh_dyn_bytes_eq(np, T->plain + name_off, name_len))) {
@@ -559,7 +564,7 @@ QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
     if (refable && !r->name1) {
       r->name1 = a + 1;
       if (name_only) {
-        return; /* :822-824 */
+        return 1; /* :822-824 */
       }
     }
     if (!vlen_ok || vl != value_len) {
@@ -575,10 +580,17 @@ QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
     if (refable) {
       r->exact1 = a + 1;
       r->exact_suffix = suffix;
-      return;
+      return 1;
     }
     r->pb = 1;
   }
+  return 0;
+}
+
+QH_HD static inline void qh_enc_find(const qh_enc_tab *T, const qh_enc_walk *w,
+                                     const qh_enc_field *f, uint64_t name_off, uint32_t name_len,
+                                     uint64_t value_off, uint32_t value_len, qh_enc_found *r) {
+  (void)qh_enc_find_from(T, w, f, name_off, name_len, value_off, value_len, w->live_lo, r);
 }
 
 QH_HD static inline uint64_t qh_enc_head(const qh_enc_tab *T, const qh_enc_walk *w, uint64_t to) {

@@ -13,6 +13,11 @@
  * writers (qh_qpack.c); and, once the four caps hold, the commit copies the
  * bytes out and writes the log, the keys and the three records of every
  * connection.
+ *
+ * With an index (qh_qpack_enc_index_init, qh_qpack_encode_conns_indexed;
+ * qh_enc_index_core.h) a connection whose record is usable is looked up
+ * through its chains and cumulative words instead of scanned, and the commit
+ * links the entries that are live and not linked yet; nothing else changes.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -23,7 +28,7 @@
 #define QH_PLAN_TOKEN(t, plain, off, len) qh_qpack_lookup_token((plain) + (off), (len))
 #define QH_PLAN_VALUE(v, plain, off, len) const uint8_t *const v = (plain) + (off)
 #define QH_PLAN_EQ(tb, v, len) (memcmp((tb), (v), (len)) == 0)
-#include "qh_enc_core.h"
+#include "qh_enc_index_core.h"
 
 /* (qh_emit.c, qh_static.c) the static table as records over one blob, and
  * the entries of a name as chains */
@@ -64,6 +69,7 @@ typedef struct ec_conn {
   qh_enc_walk w;
   uint64_t nes; /* encoder-stream instructions written */
   int bad;
+  int idx; /* its index record was usable on entry: looked up through it, linked by the commit */
 } ec_conn;
 
 typedef struct ec_buf {
@@ -135,7 +141,7 @@ static int ec_put_line(ec_buf *b, const qh_field_line *l, const uint8_t *plain,
   return 0;
 }
 
-QH_EXPORT int qh_qpack_encode_conns(
+QH_EXPORT int qh_qpack_encode_conns_indexed(
     const uint8_t *plain, const qh_span_in *strs, size_t nfields, const uint8_t *nvflags,
     const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
     const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
@@ -143,7 +149,8 @@ QH_EXPORT int qh_qpack_encode_conns(
     uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
     qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
     uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
-    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status) {
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status,
+    qh_enc_index_rec *recs, uint32_t *slots, uint64_t nslots) {
   qh_plan_tab t;
   qh_enc_tab T;
   size_t stat_n, c, b;
@@ -167,7 +174,7 @@ QH_EXPORT int qh_qpack_encode_conns(
                      min_cnt == NULL || sections == NULL)) ||
       (nfields && (plain == NULL || strs == NULL || lines == NULL)) ||
       (entries_cap && (entries == NULL || keys == NULL)) || (bytes == NULL && bytes_cap) ||
-      (dst == NULL && dst_cap) || (edst == NULL && edst_cap) ||
+      (dst == NULL && dst_cap) || (edst == NULL && edst_cap) || (recs && nslots && slots == NULL) ||
       nfields > ((size_t)1 << 30) || nsections > ((size_t)1 << 30) || nconns > 0x7ffffffull) {
     return QH_ERR_INVALID_ARGUMENT;
   }
@@ -244,6 +251,7 @@ QH_EXPORT int qh_qpack_encode_conns(
     T.nrec = nrec + f0;
     T.nkeys = nkeys + f0;
     x->bad = qh_dt_view_check(&views[tt], ne0) != 0;
+    x->idx = recs != NULL && qh_eidx_usable(&recs[tt], w->hard_max, w->count_in, nslots);
     for (s = s0; s < s1 && !x->bad; ++s) {
       const uint32_t sf = sec_flags ? sec_flags[s] : 0;
       uint32_t nes;
@@ -259,7 +267,11 @@ QH_EXPORT int qh_qpack_encode_conns(
                            &f);
         if (f.lookup) {
           f.name_id = qh_dyn_name_id(f.token, f.token == -1 ? qh_dyn_hash(plain + nm.off, nm.len) : 0);
-          qh_enc_find(&T, w, &f, nm.off, nm.len, v.off, v.len, &r);
+          if (x->idx) {
+            qh_enc_find_indexed(&T, w, &f, &recs[tt], slots, nm.off, nm.len, v.off, v.len, &r);
+          } else {
+            qh_enc_find(&T, w, &f, nm.off, nm.len, v.off, v.len, &r);
+          }
           if (r.bad) {
             x->bad = 1;
             break;
@@ -267,7 +279,8 @@ QH_EXPORT int qh_qpack_encode_conns(
         }
         qh_enc_choose(w, &r, &f);
         if (!f.decided) {
-          qh_enc_head_verdict(&f, qh_enc_head(&T, w, f.head_to));
+          qh_enc_head_verdict(&f, x->idx ? qh_enc_head_indexed(&T, w, &recs[tt], slots, f.head_to)
+                                         : qh_enc_head(&T, w, f.head_to));
         }
         if (f.verdict && f.kind != QH_EA_DUPLICATE && !r.have_vhash) {
           r.vhash = qh_dyn_hash(plain + v.off, v.len);
@@ -394,6 +407,11 @@ QH_EXPORT int qh_qpack_encode_conns(
     acct[tt].cap = w->cap;
     acct[tt].size = w->size;
     enc[tt] = w->e;
+    if (x->idx) { /* the entries not linked yet, in insert order */
+      qh_eidx_link_range(&recs[tt], slots, keys, (uint64_t)views[tt].ent_base, w->live_lo,
+                         w->count);
+      recs[tt].hi = w->count;
+    }
   }
 out:
   free(cs);
@@ -403,4 +421,93 @@ out:
   free(sb.p);
   free(eb.p);
   return rv;
+}
+
+QH_EXPORT int qh_qpack_encode_conns(
+    const uint8_t *plain, const qh_span_in *strs, size_t nfields, const uint8_t *nvflags,
+    const uint32_t *field_start, size_t nsections, const uint8_t *sec_flags,
+    const uint32_t *conn_start, size_t nconns, const uint32_t *tsel, size_t ntables,
+    qh_dtable_view *views, qh_dtable_acct *acct, qh_enc_state *enc, qh_dyn_entry *entries,
+    uint64_t *nentries, uint64_t entries_cap, uint8_t *bytes, uint64_t *nbytes, uint64_t bytes_cap,
+    qh_dyn_key *keys, qh_field_line *lines, qh_section_prefix *prefixes, uint64_t *max_cnt,
+    uint64_t *min_cnt, uint8_t *dst, uint64_t dst_cap, qh_span_in *sections, uint64_t *dst_need,
+    uint8_t *edst, uint64_t edst_cap, qh_span_in *estreams, uint64_t *edst_need, int32_t *status) {
+  return qh_qpack_encode_conns_indexed(plain, strs, nfields, nvflags, field_start, nsections,
+                                       sec_flags, conn_start, nconns, tsel, ntables, views, acct, enc,
+                                       entries, nentries, entries_cap, bytes, nbytes, bytes_cap, keys,
+                                       lines, prefixes, max_cnt, min_cnt, dst, dst_cap, sections,
+                                       dst_need, edst, edst_cap, estreams, edst_need, status, NULL,
+                                       NULL, 0);
+}
+
+/* The record of connection t as an init call leaves it, its region not placed
+ * yet (hi: the first entry it links). */
+static void ec_index_rec(const qh_dtable_view *v, const qh_dtable_acct *a, size_t nentries,
+                         uint64_t min_entries, uint32_t max_buckets, qh_enc_index_rec *r) {
+  memset(r, 0, sizeof(*r));
+  if (qh_dt_view_check(v, nentries) == 0) {
+    qh_eidx_size(a->hard_max, min_entries, max_buckets, &r->ring, &r->nbuckets);
+  }
+  r->hi = v->live_lo;
+}
+
+QH_EXPORT int qh_qpack_enc_index_init(const qh_dtable_view *views, const qh_dtable_acct *acct,
+                                      size_t ntables, const uint32_t *tsel, size_t nsel,
+                                      const qh_dyn_key *keys, size_t nentries, uint64_t min_entries,
+                                      uint32_t max_buckets, qh_enc_index_rec *recs, uint32_t *slots,
+                                      uint64_t *nslots, uint64_t slots_cap) {
+  uint64_t need, at;
+  size_t c;
+  if (nslots == NULL) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (tsel == NULL) {
+    nsel = ntables;
+  }
+  if ((nsel && (views == NULL || acct == NULL || recs == NULL || (nentries && keys == NULL))) ||
+      (slots_cap && slots == NULL)) {
+    return QH_ERR_INVALID_ARGUMENT;
+  }
+  if (tsel && nsel) {
+    uint8_t *const seen = calloc(ntables ? ntables : 1, 1);
+    if (seen == NULL) {
+      return QH_ERR_FATAL;
+    }
+    for (c = 0; c < nsel && tsel[c] < ntables && !seen[tsel[c]]; ++c) {
+      seen[tsel[c]] = 1;
+    }
+    free(seen);
+    if (c < nsel) {
+      return QH_ERR_INVALID_ARGUMENT;
+    }
+  }
+  need = *nslots;
+  for (c = 0; c < nsel; ++c) {
+    const size_t t = tsel ? tsel[c] : c;
+    qh_enc_index_rec r;
+    ec_index_rec(&views[t], &acct[t], nentries, min_entries, max_buckets, &r);
+    need += qh_eidx_need(r.ring, r.nbuckets);
+  }
+  if (need > slots_cap) {
+    *nslots = need;
+    return QH_ERR_NOMEM;
+  }
+  at = *nslots;
+  for (c = 0; c < nsel; ++c) {
+    const size_t t = tsel ? tsel[c] : c;
+    qh_enc_index_rec r;
+    ec_index_rec(&views[t], &acct[t], nentries, min_entries, max_buckets, &r);
+    if (r.ring) {
+      const uint64_t n = qh_eidx_need(r.ring, r.nbuckets);
+      r.slot_off = at;
+      memset(slots + at, 0, n * sizeof(*slots));
+      at += n;
+      qh_eidx_link_range(&r, slots, keys, (uint64_t)views[t].ent_base, views[t].live_lo,
+                         views[t].insert_count);
+    }
+    r.hi = views[t].insert_count;
+    recs[t] = r;
+  }
+  *nslots = at;
+  return 0;
 }

@@ -60,6 +60,9 @@ DYN_INDEX_REC_DTYPE = np.dtype([("ent_base", "<i8"), ("lo", "<u8"), ("hi", "<u8"
 DYN_KEY_DTYPE = np.dtype([("name_id", "<u4"), ("name_len", "<u4"), ("value_len", "<u4"),
                           ("value_hash", "<u4")])
 assert DYN_KEY_DTYPE.itemsize == 16
+ENC_INDEX_REC_DTYPE = np.dtype([("slot_off", "<u8"), ("hi", "<u8"), ("ring", "<u4"), ("nbuckets", "<u4"),
+                                ("reserved", "<u8")])
+assert ENC_INDEX_REC_DTYPE.itemsize == 32
 ENC_STATE_DTYPE = np.dtype([("krcnt", "<u8"), ("pin_min", "<u8"), ("max_blocked", "<u8"),
                             ("nblocked", "<u8"), ("nstreams", "<u8"), ("flags", "<u8"),
                             ("min_update", "<u8"), ("last_update", "<u8")])
@@ -229,6 +232,10 @@ def _load():
         _pair(lib, "encode_conns", [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, pu64, u64,
                                     vp, pu64, u64, vp, vp, vp, vp, vp, vp, u64, vp, pu64, vp, u64, vp, pu64,
                                     vp])
+        _pair(lib, "enc_index_init", [vp, vp, sz, vp, sz, vp, sz, u64, c.c_uint32, vp, vp, pu64, u64])
+        _pair(lib, "encode_conns_indexed", [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, pu64,
+                                            u64, vp, pu64, u64, vp, vp, vp, vp, vp, vp, u64, vp, pu64, vp, u64,
+                                            vp, pu64, vp, vp, vp, u64])
         lib.qh_enc_refs_init.argtypes = [vp]
         lib.qh_enc_refs_init.restype = None
         _pair(lib, "enc_sec_flags", [vp, sz, vp, sz, vp, sz, vp, vp, vp, u64, vp, vp])
@@ -1730,10 +1737,22 @@ class EncoderSet:
     With ``streams=True`` (and ``refs=True``) the object also keeps each
     connection's decoder stream as it arrives (``ustreams``, a HeldStreams):
     ``feed_decoder`` / ``feed_decoder_dev`` take whatever bytes have come and
-    hold a cut instruction until the rest follows."""
+    hold a cut instruction until the rest follows.
+
+    With ``index=True`` the object also owns a hashed index per connection
+    (``recs``, one ENC_INDEX_REC_DTYPE record each, and ``slots``):
+    ``encode`` / ``encode_dev`` then make the indexed calls
+    (qh_qpack_encode_conns_indexed / qh_encode_conns_indexed_batch), whose
+    outputs are the un-indexed ones byte for byte while a lookup walks a hash
+    chain instead of every live key.  The regions are made by the first call
+    (``init_index``); a connection with fewer than `index_min_entries`
+    possible entries (hard_max / 32) is scanned as before, and
+    `index_max_buckets` (0: no limit) cuts the bucket counts.
+    ``index_records()`` and ``index_slots()`` read the index back."""
 
     def __init__(self, hard_max, n: int, max_blocked=0, immediate_ack: bool = False, device=None,
-                 strat_none: bool = False, refs: bool = False, streams: bool = False):
+                 strat_none: bool = False, refs: bool = False, streams: bool = False,
+                 index: bool = False, index_min_entries: int = 0, index_max_buckets: int = 0):
         if streams and not refs:
             raise ValueError("streams=True needs refs=True: the decoder stream is read into the reference log")
         self._lib = _load()
@@ -1763,6 +1782,49 @@ class EncoderSet:
         for k in ("entries", "dyn_bytes", "keys"):
             setattr(self, k, be.empty(0))
         self.ustreams = HeldStreams(self._lib, be, self.n) if streams else None
+        # the index: its regions are made by the first call, which has the device form's codec
+        self.has_index, self._index_ready = bool(index), False
+        self._index_opts = (int(index_min_entries), int(index_max_buckets))
+        self.nslots = 0
+        self.recs, self.slots = be.zeros(max(self.n, 1) * ENC_INDEX_REC_DTYPE.itemsize), be.empty(0)
+
+    # -- the index (index=True): qh_qpack_enc_index_init / qh_enc_index_init_batch
+
+    def init_index(self, codec: HuffmanBatchCodec | None = None, tsel=None, slots_cap=None):
+        """Sizes and allocates the index regions of connections `tsel` (uint32
+        / int32 indices; None: all) behind the slots in use, and links the
+        entries live now: a set made without ``index=True`` adopts an index
+        this way mid-life.  ``encode`` / ``encode_dev`` call it once by
+        themselves.  slots grows on QH_ERR_NOMEM (slots_cap: a fixed capacity
+        instead, for tests; the call is then made once).  -> (the call's
+        return value, the slots in use or needed)."""
+        be = self._be
+        ptr = be.ptr
+        nsel = 0 if tsel is None else be.size(tsel)
+        self.has_index = self._index_ready = True
+
+        def attempt():
+            ns = ctypes.c_uint64(self.nslots)
+            cap = be.size(self.slots) // 4 if slots_cap is None else slots_cap
+            rv = be.call(self._lib, "enc_index_init", ptr(self.views), ptr(self.acct), self.n,
+                         be.list_ptr(tsel), nsel, ptr(self.keys), self.nentries, self._index_opts[0],
+                         self._index_opts[1], ptr(self.recs), ptr(self.slots), ctypes.byref(ns), cap,
+                         codec=codec)
+            return rv, int(ns.value)
+        rv, ns = be.retry("enc_index_init", attempt,
+                          lambda need: self._grow("slots", self.nslots * 4, need * 4, 4096),
+                          slots_cap is not None)
+        if rv == 0:
+            self.nslots = ns
+        return rv, ns
+
+    def index_records(self):
+        """-> ENC_INDEX_REC_DTYPE [n], a numpy copy."""
+        return self._host("recs", np.uint8)[:self.n * ENC_INDEX_REC_DTYPE.itemsize].view(ENC_INDEX_REC_DTYPE)
+
+    def index_slots(self):
+        """-> uint32 [nslots], a numpy copy of the slots in use."""
+        return self._host("slots", np.uint8)[:self.nslots * 4].view(np.uint32)
 
     # -- state access (numpy copies; the device form copies through the host)
 
@@ -1813,6 +1875,10 @@ class EncoderSet:
         then made once and its return value and needs handed back)."""
         be = self._be
         ptr, new = be.ptr, be.zeros
+        if self.has_index and not self._index_ready:
+            self.init_index(codec)
+        # (the indexed stem's three arguments more; the regions never move, so they are fixed here)
+        index = (ptr(self.recs), ptr(self.slots), self.nslots) if self.has_index else ()
         lines = new(max(nfields, 1) * 24)
         prefixes = new(max(nsections, 1) * 24)
         mx, mn = new(max(nsections, 1) * 8), new(max(nsections, 1) * 8)
@@ -1842,13 +1908,14 @@ class EncoderSet:
             dn, en = ctypes.c_uint64(0), ctypes.c_uint64(0)
             ecap = caps[0] if fixed else min(be.size(self.entries) // 32, be.size(self.keys) // 16)
             bcap = caps[1] if fixed else be.size(self.dyn_bytes)
-            rv = be.call(self._lib, "encode_conns", ptr(plain), ptr(strs), nfields, ptr(nvflags),
+            rv = be.call(self._lib, "encode_conns" + ("_indexed" if index else ""), ptr(plain), ptr(strs),
+                         nfields, ptr(nvflags),
                          ptr(field_start), nsections, ptr(sec_flags), ptr(conn_start), nconns,
                          be.list_ptr(tsel), self.n, ptr(self.views), ptr(self.acct), ptr(self.enc),
                          ptr(self.entries), ctypes.byref(ne), ecap, ptr(self.dyn_bytes),
                          ctypes.byref(nb), bcap, ptr(self.keys), ptr(lines), ptr(prefixes), ptr(mx),
                          ptr(mn), ptr(dst), dst_cap, ptr(sections), ctypes.byref(dn), ptr(edst),
-                         edst_cap, ptr(estreams), ctypes.byref(en), ptr(status), codec=codec)
+                         edst_cap, ptr(estreams), ctypes.byref(en), ptr(status), *index, codec=codec)
             return rv, (int(ne.value), int(nb.value), int(dn.value), int(en.value))
 
         def enlarge(needs):
