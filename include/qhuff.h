@@ -1975,6 +1975,115 @@ QH_EXPORT int qh_ustream_compact_batch(
     qh_ctx *ctx, size_t ntables, qh_ustream *us, const uint8_t *log, uint64_t nlog,
     uint8_t *log_out, uint64_t *nlog_out, uint64_t log_out_cap, int where);
 
+/* ---- Decoded header sections as HTTP messages --------
+ * What conn_decode_headers does with every emitted field
+ * (lib/nghttp3_conn.c:1880-1944): nghttp3_http_on_header
+ * (lib/nghttp3_http.c:538-571, the two switches :319-534) passes it on, drops
+ * it (NGHTTP3_ERR_REMOVE_HTTP_HEADER) or fails the stream
+ * (NGHTTP3_ERR_MALFORMED_HTTP_HEADER), and the end of a header section is
+ * nghttp3_http_on_request_headers / _on_response_headers (http.c:573-627,
+ * conn.c:1713-1730), for every section of a batch.
+ *
+ * Inputs: the outputs of an emit call made with `out` -- fields (nfields
+ * records), field_start (nsec + 1), out (nout bytes) and optionally emit's
+ * status (emit_status, nsec) -- plus kind[p], one byte per section
+ * (QH_HTTP_REQUEST or 0 for a response, | QH_HTTP_TRAILERS, |
+ * QH_HTTP_CONNECT_PROTOCOL: conn->server && enable_connect_protocol,
+ * conn.c:1917), and states[p], in / out: section p owns record p (the caller
+ * gathers and scatters per-stream records, so the sections of a call are
+ * independent).  The state carries what a later section of the stream needs:
+ * the request's method for its response (METH_HEAD, METH_CONNECT;
+ * nghttp3_http_record_request_method :651-673), EXPECT_FINAL_RESPONSE after
+ * a 1xx, the headers' flags for the trailers.
+ *
+ * Outputs:
+ *   fverdict[f]  QH_HTTP_KEEP, _REMOVE, _MALFORMED, or _UNSEEN for a field
+ *                behind the section's first malformed one (the reference
+ *                never reads it) and for every field of a skipped section;
+ *   status[p]    0 or QH_ERR_MALFORMED_HTTP_HEADER;
+ *   bad_field[p] (optional) the section-relative index of the malformed
+ *                field, the section's field count when the end-of-headers
+ *                check failed, QH_HTTP_NO_FIELD otherwise;
+ *   kept, kept_start[nsec + 1] (optional, together) the records recv_header
+ *                / recv_trailer would receive (conn.c:1924-1931), compacted
+ *                in order: the KEEP fields before any malformed one, section
+ *                p's at [kept_start[p], kept_start[p + 1]).  kept_cap >=
+ *                nfields is required, so that nothing has to come back to the
+ *                host;
+ *   states[p]    updated when status[p] is 0.
+ * A section is skipped (verdicts UNSEEN, nothing kept, state untouched) when
+ * emit_status[p] != 0 (copied to status[p]), or when its range does not lie
+ * inside [0, nfields) or one of its records does not have both strings in
+ * out[0, nout) as QH_IN_OUT (status[p] = QH_ERR_INVALID_ARGUMENT).
+ *
+ * Two departures from the reference: (1) the `priority` dictionary
+ * (http.c:437-449) is not parsed: a request's priority field with a bad
+ * value byte is removed and sets QH_HTTP_FLAG_BAD_PRIORITY (:426-431),
+ * otherwise it is kept and QH_HTTP_FLAG_PRIORITY is never set -- the caller
+ * finds the field by its token; (2) the state of a section that ends -105 is
+ * left as on entry (the reference leaves a partial state on a stream it then
+ * resets).
+ *
+ * Returns 0, or QH_ERR_INVALID_ARGUMENT with nothing written (a NULL
+ * argument that is needed, kept without kept_start or the reverse, kept_cap <
+ * nfields, nfields or nsec of 2^31 or more).  qh_qpack_http_check is host C
+ * over host pointers; qh_http_check_batch is the same over pointers in HBM
+ * (where must be QH_WHERE_DEVICE), asynchronous on the context stream with
+ * no host wait. */
+#define QH_ERR_MALFORMED_HTTP_HEADER (-105) /* nghttp3.h:211 */
+
+#define QH_HTTP_REQUEST 1u
+#define QH_HTTP_TRAILERS 2u
+#define QH_HTTP_CONNECT_PROTOCOL 4u
+
+#define QH_HTTP_KEEP 0
+#define QH_HTTP_REMOVE 1
+#define QH_HTTP_MALFORMED 2
+#define QH_HTTP_UNSEEN 3
+#define QH_HTTP_NO_FIELD 0xFFFFFFFFu
+
+/* NGHTTP3_HTTP_FLAG_*, lib/nghttp3_http.h:42-83 */
+#define QH_HTTP_FLAG__AUTHORITY 0x01u
+#define QH_HTTP_FLAG__PATH 0x02u
+#define QH_HTTP_FLAG__METHOD 0x04u
+#define QH_HTTP_FLAG__SCHEME 0x08u
+#define QH_HTTP_FLAG_HOST 0x10u
+#define QH_HTTP_FLAG__STATUS 0x20u
+#define QH_HTTP_FLAG_REQ_HEADERS \
+  (QH_HTTP_FLAG__METHOD | QH_HTTP_FLAG__PATH | QH_HTTP_FLAG__SCHEME)
+#define QH_HTTP_FLAG_PSEUDO_HEADER_DISALLOWED 0x40u
+#define QH_HTTP_FLAG_METH_CONNECT 0x80u
+#define QH_HTTP_FLAG_METH_HEAD 0x0100u
+#define QH_HTTP_FLAG_METH_OPTIONS 0x0200u
+#define QH_HTTP_FLAG_METH_ALL \
+  (QH_HTTP_FLAG_METH_CONNECT | QH_HTTP_FLAG_METH_HEAD | QH_HTTP_FLAG_METH_OPTIONS)
+#define QH_HTTP_FLAG_PATH_REGULAR 0x0400u
+#define QH_HTTP_FLAG_PATH_ASTERISK 0x0800u
+#define QH_HTTP_FLAG_SCHEME_HTTP 0x1000u
+#define QH_HTTP_FLAG_EXPECT_FINAL_RESPONSE 0x2000u
+#define QH_HTTP_FLAG__PROTOCOL 0x4000u
+#define QH_HTTP_FLAG_PRIORITY 0x8000u
+#define QH_HTTP_FLAG_BAD_PRIORITY 0x010000u
+
+typedef struct qh_http_state { /* 16 B: nghttp3_http_state without pri and recv_content_length */
+  int64_t content_length;
+  int32_t status_code;
+  uint32_t flags; /* QH_HTTP_FLAG_* */
+} qh_http_state;
+/* -1 / -1 / 0, as lib/nghttp3_stream.c:67-68 sets them. */
+QH_EXPORT void qh_http_state_init(qh_http_state *states, size_t n);
+
+QH_EXPORT int qh_qpack_http_check(
+    const qh_field *fields, size_t nfields, const uint32_t *field_start, size_t nsec,
+    const uint8_t *out, uint64_t nout, const int32_t *emit_status, const uint8_t *kind,
+    qh_http_state *states, int8_t *fverdict, int32_t *status, uint32_t *bad_field,
+    qh_field *kept, size_t kept_cap, uint32_t *kept_start);
+QH_EXPORT int qh_http_check_batch(
+    qh_ctx *ctx, const qh_field *fields, size_t nfields, const uint32_t *field_start,
+    size_t nsec, const uint8_t *out, uint64_t nout, const int32_t *emit_status,
+    const uint8_t *kind, qh_http_state *states, int8_t *fverdict, int32_t *status,
+    uint32_t *bad_field, qh_field *kept, size_t kept_cap, uint32_t *kept_start, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

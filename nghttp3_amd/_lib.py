@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("QHUFF_LIB", LIB_PATH)
 
 QH_OK = 0
 QH_ERR_INVALID_ARGUMENT = -101
+QH_ERR_MALFORMED_HTTP_HEADER = -105
 QH_ERR_QPACK_FATAL = -108
 QH_ERR_FATAL = -900
 QH_ERR_NOMEM = -901
@@ -243,6 +244,10 @@ EXPORTED_FUNCTIONS = (
     "qh_ustream_sections_batch",
     "qh_qpack_ustream_compact",
     "qh_ustream_compact_batch",
+    # decoded sections as HTTP messages (csrc/qh_httpmsg.c, csrc/qh_httpmsg.inc)
+    "qh_http_state_init",
+    "qh_qpack_http_check",
+    "qh_http_check_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

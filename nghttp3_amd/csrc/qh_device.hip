@@ -23,9 +23,10 @@
 //   qh_k_blk_*         blocked sections: queued, released, cancelled, compacted
 //   qh_k_part_*        sections in pieces: held, reassembled at fin, compacted
 //   qh_k_us_*          encoder and decoder streams as they arrive: cut instructions held
+//   qh_k_http_*        decoded sections as HTTP messages: field verdicts, the kept records
 //   qh_k_idx_*         the hashed index over the views' keys: count, build
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
-// The kernels from qh_k_encsec_* to qh_k_us_* work a 16-lane group per table,
+// The kernels from qh_k_encsec_* to qh_k_http_* work a 16-lane group per table,
 // connection or block and leave their totals in one scan header: both are
 // qh_group.inc's.
 // Development variants (the pair decoder, the segment encoder) build only
@@ -92,4 +93,5 @@
 #include "qh_blocked.inc"       // blocked sections: the queue log, push, release, cancel, compact
 #include "qh_partial.inc"       // sections in pieces: held until fin, handed on whole; cancel, compact
 #include "qh_ustream.inc"       // encoder and decoder streams as they arrive: cut instructions held; join, keep, sections, compact
+#include "qh_httpmsg.inc"       // decoded sections as HTTP messages: fields kept, removed or malformed, the state per stream
 

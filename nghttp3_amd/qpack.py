@@ -92,6 +92,13 @@ USTREAM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("held", "<u4"), ("ule
 assert USTREAM_DTYPE.itemsize == 32
 USTREAM_BAD, USTREAM_LATCH, USTREAM_MAX_ENCODERLEN = 0x1, 0x1, 131072
 IN_SRC, IN_DST, IN_STATIC, IN_DYN, IN_OUT = range(5)
+# include/qhuff.h qh_http_state, QH_HTTP_*
+HTTP_STATE_DTYPE = np.dtype([("content_length", "<i8"), ("status_code", "<i4"), ("flags", "<u4")])
+assert HTTP_STATE_DTYPE.itemsize == 16
+HTTP_REQUEST, HTTP_TRAILERS, HTTP_CONNECT_PROTOCOL = 1, 2, 4
+HTTP_KEEP, HTTP_REMOVE, HTTP_MALFORMED, HTTP_UNSEEN = range(4)
+HTTP_NO_FIELD = 0xFFFFFFFF
+QH_ERR_MALFORMED_HTTP_HEADER = -105
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
 
@@ -261,6 +268,9 @@ def _load():
         _pair(lib, "ustream_keep", [vp, vp, vp, sz, sz, c.c_uint32, vp])
         _pair(lib, "ustream_sections", [vp, vp, sz, sz, vp])
         _pair(lib, "ustream_compact", [sz, vp, vp, u64, vp, pu64, u64])
+        lib.qh_http_state_init.argtypes = [vp, sz]
+        lib.qh_http_state_init.restype = None
+        _pair(lib, "http_check", [vp, sz, vp, sz, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, vp])
         _L = lib
     return _L
 
@@ -832,6 +842,98 @@ class FieldSectionDecoder:
         b.update({"nfields": int(e.nfields), "out_need": int(e.out_need),
                   "nblocked": int(e.nblocked)})
         return b
+
+
+    # ---- sections as HTTP messages (qh_qpack_http_check / qh_http_check_batch) ----
+
+    @staticmethod
+    def _http_check(be, fields, nfields, field_start, nsec, out, nout, emit_status, kind, states, o,
+                    kept_cap=None, codec=None):
+        """The call over the arrays of backend `be` -> rv.  `o`: the outputs
+        fverdict, status, bad_field, kept, kept_start (bad_field and the kept
+        pair may be None); kept_cap defaults to kept's room in records."""
+        kept = o.get("kept")
+        if kept_cap is None:
+            kept_cap = be.size(kept) // FIELD_DTYPE.itemsize
+        return be.call(_load(), "http_check", be.ptr(fields), nfields, be.ptr(field_start), nsec,
+                       be.ptr(out), nout, be.ptr(emit_status), be.ptr(kind), be.ptr(states),
+                       be.ptr(o["fverdict"]), be.ptr(o["status"]), be.ptr(o.get("bad_field")),
+                       be.ptr(kept), kept_cap, be.ptr(o.get("kept_start")), codec=codec)
+
+    @staticmethod
+    def check_http(emit_result, kind, states, keep=True):
+        """Host arrays: every section of an emit_fields(..., materialise=True)
+        result judged as conn_decode_headers judges it (nghttp3_http_on_header
+        per field, the end-of-headers check per section).  kind: one byte per
+        section (HTTP_REQUEST or 0 for a response, | HTTP_TRAILERS, |
+        HTTP_CONNECT_PROTOCOL); states: HTTP_STATE_DTYPE records
+        (``http_states``), section p's at p, updated in place where the
+        section passes.  -> dict: fverdict (int8 per field: HTTP_KEEP, _REMOVE,
+        _MALFORMED, _UNSEEN), status (0, -105, or the skipped section's),
+        bad_field, and with ``keep`` kept (FIELD_DTYPE: what recv_header would
+        receive) and kept_start.  Runs on the host (qh_qpack_http_check)."""
+        e = emit_result
+        if e.get("out") is None:
+            raise ValueError("check_http needs an emit result made with materialise=True")
+        nf, fs = int(e["nfields"]), np.ascontiguousarray(e["field_start"], np.uint32)
+        nsec = fs.size - 1
+        kind = np.ascontiguousarray(kind, np.uint8)
+        if kind.size != nsec or states.dtype != HTTP_STATE_DTYPE or states.size != nsec or \
+                not states.flags.c_contiguous:
+            raise ValueError("check_http: one kind byte and one state record per section")
+        fields = np.ascontiguousarray(e["fields"], FIELD_DTYPE)
+        out = _u8(e["out"])
+        o = {"fverdict": np.zeros(nf, np.int8), "status": np.zeros(nsec, np.int32),
+             "bad_field": np.zeros(nsec, np.uint32),
+             "kept": np.zeros(max(nf, 1), FIELD_DTYPE).view(np.uint8) if keep else None,
+             "kept_start": np.zeros(nsec + 1, np.uint32) if keep else None}
+        be = Backend()
+        st = None if e.get("status") is None else np.ascontiguousarray(e["status"], np.int32)
+        rv = FieldSectionDecoder._http_check(be, fields.view(np.uint8), nf, fs, nsec, out, out.size, st,
+                                             kind, states.view(np.uint8), o, kept_cap=nf)
+        be.check(rv, "http_check")
+        if keep:
+            o["kept"] = o["kept"].view(FIELD_DTYPE)[:int(o["kept_start"][nsec])]
+        o["states"] = states
+        return o
+
+    def check_http_dev(self, emit_result, kind, states, keep=True, bufs=None):
+        """Device-resident form (qh_http_check_batch): `emit_result` an
+        emit_fields_dev(..., materialise=True) result, kind a uint8 tensor
+        [nsec], states a uint8 tensor [nsec * 16] (``http_states`` uploaded),
+        updated in place.  -> dict of torch tensors (fverdict int8, status and
+        bad_field and kept_start int32, kept uint8 [nfields * 32]); `bufs` (a
+        previous result) reuses its allocations.  Asynchronous on the
+        context's stream: no host wait."""
+        import torch
+        e = emit_result
+        nf, nsec = int(e["nfields"]), int(kind.shape[0])
+        dev = kind.device
+        b = bufs or {}
+        if b.get("nf", -1) < nf or b.get("nsec", -1) < nsec or (keep and b.get("kept") is None):
+            b = {"nf": nf, "nsec": nsec,
+                 "fverdict": torch.empty(max(nf, 1), dtype=torch.int8, device=dev),
+                 "status": torch.empty(max(nsec, 1), dtype=torch.int32, device=dev),
+                 "bad_field": torch.empty(max(nsec, 1), dtype=torch.int32, device=dev),
+                 "kept": torch.empty(max(nf, 1) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+                 if keep else None,
+                 "kept_start": torch.empty(nsec + 1, dtype=torch.int32, device=dev) if keep else None}
+        o = b if keep else dict(b, kept=None, kept_start=None)
+        be = Backend(dev)
+        rv = self._http_check(be, e["fields"], nf, e["field_start"], nsec, e["out"], int(e["out_need"]),
+                              e.get("status"), kind, states, o, kept_cap=b["nf"] if keep else 0,
+                              codec=self.codec)
+        be.check(rv, "http_check")
+        b["states"] = states
+        return b
+
+
+def http_states(n: int):
+    """n fresh HTTP_STATE_DTYPE records (-1 / -1 / 0, qh_http_state_init)."""
+    st = np.zeros(n, dtype=HTTP_STATE_DTYPE)
+    if n:
+        _load().qh_http_state_init(_vp(st), n)
+    return st
 
 
 class DynamicTable:
