@@ -1,5 +1,5 @@
 /* Replays a case file through the reference library's QPACK encoder and
- * decoder and writes what it did as a transcript (oracle/README.md has both
+ * decoder and its HTTP message checks and writes what it did as a transcript (oracle/README.md has both
  * formats).  The program decides nothing: every stream id, flag,
  * acknowledgement and capacity is in the case file, and every line of the
  * transcript is read back from the library.  Built by oracle/ref.mk against
@@ -10,7 +10,8 @@
  *
  * nghttp3/nghttp3.h is the public API; lib/nghttp3_qpack.h is included for
  * the values the public API does not return (the encoder's scalars, the
- * table's entries, a section's counts, Base). */
+ * table's entries, a section's counts, Base); lib/nghttp3_http.h and
+ * lib/nghttp3_stream.h for the HTTP checks and their state record. */
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +20,9 @@
 #include <nghttp3/nghttp3.h>
 
 #include "nghttp3_qpack.h"
+#include "nghttp3_http.h"
+#include "nghttp3_stream.h"
+#include "sfparse/sfparse.h"
 
 static FILE *in;
 static const nghttp3_mem *mem;
@@ -60,6 +64,19 @@ static uint64_t number(void) {
     die("number expected");
   }
   v = strtoull(t, &end, 10);
+  if (*end) {
+    die("bad number");
+  }
+  return v;
+}
+
+static int64_t snumber(void) {
+  char *t = token(), *end;
+  int64_t v;
+  if (!t) {
+    die("number expected");
+  }
+  v = strtoll(t, &end, 10);
   if (*end) {
     die("bad number");
   }
@@ -127,6 +144,136 @@ static void put_table(nghttp3_qpack_context *ctx) {
     putchar(']');
   }
   putchar(']');
+}
+
+/* ---- HTTP message checks ---- */
+
+/* The two functions of oracle/shim/sfparse/sfparse.h: a dictionary that is
+ * always empty, so nghttp3_http_parse_priority returns 0 whenever it is
+ * reached (oracle/README.md: the one part the transcripts do not judge). */
+void sfparse_parser_init(sfparse_parser *sfp, const uint8_t *data, size_t datalen) {
+  sfp->pos = data;
+  sfp->end = data + datalen;
+}
+
+int sfparse_parser_dict(sfparse_parser *sfp, sfparse_vec *dest_key, sfparse_value *dest_value) {
+  (void)sfp;
+  (void)dest_key;
+  (void)dest_value;
+  return SFPARSE_ERR_EOF;
+}
+
+static int http_on;
+
+/* One section's walk: what conn_decode_headers does with the fields it is
+ * given (lib/nghttp3_conn.c:1914-1935) and what the end of the headers adds
+ * (:1713-1730).  v: one letter per field seen. */
+typedef struct hwalk {
+  nghttp3_http_state *http;
+  int kind; /* 1 request, 2 trailers, 4 connect protocol */
+  char *v;
+  size_t n, cap;
+  int rv;
+  int64_t bad; /* -1: none */
+} hwalk;
+
+static void hwalk_init(hwalk *w, nghttp3_http_state *http, int kind) {
+  memset(w, 0, sizeof(*w));
+  w->http = http;
+  w->kind = kind;
+  w->bad = -1;
+}
+
+static void hwalk_field(hwalk *w, const nghttp3_qpack_nv *nv) {
+  int rv;
+  if (w->rv != 0) { /* conn_decode_headers returned at the malformed field */
+    return;
+  }
+  if (w->n + 2 > w->cap) {
+    w->cap = w->cap ? w->cap * 2 : 64;
+    w->v = realloc(w->v, w->cap);
+    if (!w->v) {
+      die("out of memory");
+    }
+  }
+  rv = nghttp3_http_on_header(w->http, nv, w->kind & 1, (w->kind & 2) != 0, (w->kind & 4) != 0);
+  if (rv == NGHTTP3_ERR_MALFORMED_HTTP_HEADER) {
+    w->rv = rv;
+    w->bad = (int64_t)w->n;
+    w->v[w->n++] = 'm';
+  } else if (rv == NGHTTP3_ERR_REMOVE_HTTP_HEADER) {
+    w->v[w->n++] = 'r';
+  } else if (rv == 0) {
+    w->v[w->n++] = 'k';
+  } else {
+    die("nghttp3_http_on_header returned what conn_decode_headers does not expect");
+  }
+}
+
+/* nfields: the section's fields, seen or not. */
+static void hwalk_end(hwalk *w, size_t nfields) {
+  if (w->rv != 0 || (w->kind & 2)) {
+    return;
+  }
+  w->rv = (w->kind & 1) ? nghttp3_http_on_request_headers(w->http)
+                        : nghttp3_http_on_response_headers(w->http);
+  if (w->rv != 0) {
+    w->bad = (int64_t)nfields;
+  }
+}
+
+static void hwalk_put(hwalk *w) {
+  printf("\"v\":\"%.*s\",", (int)w->n, w->v ? w->v : "");
+  if (w->bad < 0) {
+    printf("\"bad\":null,");
+  } else {
+    printf("\"bad\":%" PRId64 ",", w->bad);
+  }
+  printf("\"cl\":%" PRId64 ",\"sc\":%d,\"fl\":%u", w->http->content_length, (int)w->http->status_code,
+         (unsigned)w->http->flags);
+  free(w->v);
+  w->v = NULL;
+}
+
+static void http_state_set(nghttp3_http_state *http, int64_t cl, int64_t sc, uint64_t fl) {
+  memset(http, 0, sizeof(*http)); /* recv_content_length and pri zeroed */
+  http->content_length = cl;
+  http->status_code = (int32_t)sc;
+  http->flags = (uint32_t)fl;
+}
+
+/* hsec KIND CL STATUS FLAGS NFIELDS, then per field TOKEN NAME VALUE */
+static void http_hsec(void) {
+  int kind = (int)number();
+  nghttp3_http_state http;
+  hwalk w;
+  size_t nf, i;
+  int64_t cl = snumber(), sc = snumber();
+  http_state_set(&http, cl, sc, number());
+  nf = (size_t)number();
+  hwalk_init(&w, &http, kind);
+  for (i = 0; i < nf; ++i) {
+    nghttp3_qpack_nv nv;
+    size_t nlen, vlen;
+    uint8_t *name, *value;
+    nv.token = (int32_t)snumber();
+    nv.flags = NGHTTP3_NV_FLAG_NONE;
+    name = hexbytes(&nlen);
+    value = hexbytes(&vlen);
+    if (nghttp3_rcbuf_new2(&nv.name, name, nlen, mem) != 0 ||
+        nghttp3_rcbuf_new2(&nv.value, value, vlen, mem) != 0) {
+      die("out of memory");
+    }
+    hwalk_field(&w, &nv);
+    nghttp3_rcbuf_decref(nv.name);
+    nghttp3_rcbuf_decref(nv.value);
+    free(name);
+    free(value);
+  }
+  hwalk_end(&w, nf);
+  printf("{\"op\":\"hsec\",\"rv\":%d,", w.rv);
+  hwalk_put(&w);
+  printf("}\n");
 }
 
 /* ---- encoder ---- */
@@ -240,13 +387,16 @@ static void drop_held(held **pp) {
 }
 
 /* read_request with fin set until the section ends, fails or blocks; prints
- * the step's line (with `left`, the unread bytes, when with_left).  -> the
- * bytes read when the library reports BLOCKED, -1 otherwise. */
+ * the step's line (with `left`, the unread bytes, when with_left; with the
+ * HTTP verdicts when w: every emitted field goes through hwalk_field with the
+ * token read_request gave it, a section read to its end through hwalk_end).
+ * -> the bytes read when the library reports BLOCKED, -1 otherwise. */
 static ptrdiff_t read_section(const char *op, int64_t sid, nghttp3_qpack_stream_context *sctx,
-                              const uint8_t *src, size_t len, int with_left) {
+                              const uint8_t *src, size_t len, int with_left, hwalk *w) {
   size_t at = 0;
   nghttp3_ssize total = 0;
-  int blocked = 0, first = 1;
+  int blocked = 0, first = 1, final = 0;
+  size_t nfields = 0;
   printf("{\"op\":\"%s\",\"sid\":%" PRId64 ",\"fields\":[", op, sid);
   for (;;) {
     nghttp3_qpack_nv nv;
@@ -270,10 +420,15 @@ static ptrdiff_t read_section(const char *op, int64_t sid, nghttp3_qpack_stream_
       putchar(',');
       put_hex(value.base, value.len);
       printf(",%d,%d]", (int)nv.token, (nv.flags & NGHTTP3_NV_FLAG_NEVER_INDEX) ? 1 : 0);
+      ++nfields;
+      if (w) {
+        hwalk_field(w, &nv);
+      }
       nghttp3_rcbuf_decref(nv.name);
       nghttp3_rcbuf_decref(nv.value);
     }
     if (flags & NGHTTP3_QPACK_DECODE_FLAG_FINAL) {
+      final = 1;
       break;
     }
     if (n == 0 && !(flags & NGHTTP3_QPACK_DECODE_FLAG_EMIT)) {
@@ -284,6 +439,14 @@ static ptrdiff_t read_section(const char *op, int64_t sid, nghttp3_qpack_stream_
          nghttp3_qpack_stream_context_get_ricnt2(sctx), sctx->base);
   if (with_left) {
     printf("\"left\":%zu,", len - at);
+  }
+  if (w) {
+    if (final) {
+      hwalk_end(w, nfields);
+    }
+    printf("\"hrv\":%d,", w->rv);
+    hwalk_put(w);
+    putchar(',');
   }
   put_dec_state();
   printf("}\n");
@@ -302,7 +465,7 @@ static void dec_section(int hold) {
   if (nghttp3_qpack_stream_context_new(&sctx, sid, mem) != 0) {
     die("out of memory");
   }
-  at = read_section(hold ? "hold" : "section", sid, sctx, src, len, hold);
+  at = read_section(hold ? "hold" : "section", sid, sctx, src, len, hold, NULL);
   if (hold && at >= 0) { /* blocked: the context and the unread tail are kept */
     held *h = calloc(1, sizeof(*h));
     if (!h) {
@@ -324,6 +487,61 @@ static void dec_section(int hold) {
   free(src);
 }
 
+/* The nghttp3_http_state of every stream an hsection or hstate step named,
+ * kept until the connection ends. */
+typedef struct hstream {
+  int64_t sid;
+  nghttp3_http_state http;
+  struct hstream *next;
+} hstream;
+static hstream *hstreams;
+
+static nghttp3_http_state *hstream_of(int64_t sid) {
+  hstream *h;
+  for (h = hstreams; h; h = h->next) {
+    if (h->sid == sid) {
+      return &h->http;
+    }
+  }
+  h = calloc(1, sizeof(*h));
+  if (!h) {
+    die("out of memory");
+  }
+  h->sid = sid;
+  http_state_set(&h->http, -1, -1, 0); /* as nghttp3_stream_new leaves it */
+  h->next = hstreams;
+  hstreams = h;
+  return &h->http;
+}
+
+/* hsection SID KIND BYTES: as `section`, every field through the HTTP checks */
+static void dec_hsection(void) {
+  int64_t sid = (int64_t)number();
+  int kind = (int)number();
+  size_t len;
+  uint8_t *src = hexbytes(&len);
+  nghttp3_qpack_stream_context *sctx;
+  hwalk w;
+  if (nghttp3_qpack_stream_context_new(&sctx, sid, mem) != 0) {
+    die("out of memory");
+  }
+  hwalk_init(&w, hstream_of(sid), kind);
+  read_section("hsection", sid, sctx, src, len, 0, &w);
+  nghttp3_qpack_stream_context_del(sctx);
+  free(src);
+}
+
+/* hstate SID CL STATUS FLAGS: the stream's record as the case gives it (what
+ * a client records of its request's method, for instance) */
+static void dec_hstate(void) {
+  int64_t sid = (int64_t)number();
+  nghttp3_http_state *http = hstream_of(sid);
+  int64_t cl = snumber(), sc = snumber();
+  http_state_set(http, cl, sc, number());
+  printf("{\"op\":\"hstate\",\"sid\":%" PRId64 ",\"cl\":%" PRId64 ",\"sc\":%d,\"fl\":%u}\n", sid,
+         http->content_length, (int)http->status_code, (unsigned)http->flags);
+}
+
 static void dec_resume(void) {
   int64_t sid = (int64_t)number();
   held **pp = find_held(sid), *h = *pp;
@@ -331,7 +549,7 @@ static void dec_resume(void) {
   if (!h) {
     die("resume of a stream that is not held");
   }
-  at = read_section("resume", sid, h->sctx, h->tail, h->len, 1);
+  at = read_section("resume", sid, h->sctx, h->tail, h->len, 1, NULL);
   if (at >= 0) { /* still blocked */
     memmove(h->tail, h->tail + at, h->len - (size_t)at);
     h->len -= (size_t)at;
@@ -361,6 +579,12 @@ static void del_both(void) {
   while (kept) {
     drop_held(&kept);
   }
+  while (hstreams) {
+    hstream *h = hstreams;
+    hstreams = h->next;
+    free(h);
+  }
+  http_on = 0;
   nghttp3_qpack_encoder_del(enc);
   nghttp3_qpack_decoder_del(dec);
   enc = NULL;
@@ -402,6 +626,17 @@ int main(int argc, char **argv) {
       printf("{\"op\":\"new\",");
       put_dec_state();
       printf("}\n");
+    } else if (strcmp(t, "http") == 0) { /* http new */
+      token();
+      del_both();
+      http_on = 1;
+      printf("{\"op\":\"new\"}\n");
+    } else if (strcmp(t, "hsec") == 0 && http_on) {
+      http_hsec();
+    } else if (strcmp(t, "hsection") == 0 && dec) {
+      dec_hsection();
+    } else if (strcmp(t, "hstate") == 0 && dec) {
+      dec_hstate();
     } else if (strcmp(t, "cap") == 0 && enc) {
       nghttp3_qpack_encoder_set_max_dtable_capacity(enc, (size_t)number());
       printf("{\"op\":\"cap\",");

@@ -9,7 +9,9 @@ function by function, and driven by the reference's own class tables
 (tests/golden/http_chars.json, tests/golden/http_msg_chars.json); the C core
 uses range compares instead.  The `priority` dictionary is not parsed (the
 library's stated departure: :437-449 are left out), and a section that ends
-malformed gives back the state it was given (the second departure)."""
+malformed gives back the state it was given (the second departure).  The
+model is itself held against the reference library's transcripts on every
+case in tests/test_http_ref.py."""
 import json
 import os
 

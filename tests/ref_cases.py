@@ -18,7 +18,8 @@ table (enc_state_digest); a decoder's step its numbers and a digest of the
 table or of the decoded fields.  A digest is the first 16 hex digits of a
 SHA-256.  The walk case of the closure test also keeps its bytes.  The
 planners' transcripts (kind "planner": a fill step and probe steps) are
-written and compared by tests/plan_ref_cases.py.  What a
+written and compared by tests/plan_ref_cases.py, the HTTP message check's
+(kind "http": entry and hwin steps) by tests/http_ref_cases.py.  What a
 digest stands for is printed by the driver: a mismatch is looked into by
 running it on the case file (enc_script, dec_script)."""
 import hashlib
@@ -272,7 +273,8 @@ def record(name, kind, scripts, full=False, note="", copies=False):
 # On disk a step is a list: the operation's letter, then the values of its
 # keys in this order, trailing absent ones left off.
 LETTER = {"new": "n", "cap": "c", "ack": "a", "ackall": "A", "encode": "e", "estream": "s", "section": "q",
-          "dstream": "d", "cancel": "x", "hold": "h", "resume": "r", "dwrite": "w", "fill": "f", "probe": "p"}
+          "dstream": "d", "cancel": "x", "hold": "h", "resume": "r", "dwrite": "w", "fill": "f", "probe": "p",
+          "entry": "E", "hwin": "H"}
 KEYS = {"encoder": {"new": (), "cap": ("st",), "ack": ("sid", "rv", "st"), "ackall": ("st",),
                     "encode": ("sid", "rv", "eslen", "out", "st", "sec", "es"),
                     "dstream": ("rv", "dlen", "bad", "st"), "cancel": ("sid", "st")},
@@ -281,7 +283,8 @@ KEYS = {"encoder": {"new": (), "cap": ("st",), "ack": ("sid", "rv", "st"), "acka
                     "hold": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
                     "resume": ("sid", "rv", "blocked", "ricnt", "base", "n", "d", "left"),
                     "cancel": ("sid", "rv"), "dwrite": ("len", "d", "written_icnt", "ds")},
-        "planner": {"new": (), "fill": ("insert_count", "krcnt", "cap", "n", "d"), "probe": ("k", "rv", "out")}}
+        "planner": {"new": (), "fill": ("insert_count", "krcnt", "cap", "n", "d"), "probe": ("k", "rv", "out")},
+        "http": {"new": (), "entry": ("at", "cl", "sc", "fl"), "hwin": ("k", "nk", "nr", "nm", "d", "t", "rows")}}
 
 
 def _pack(kind, d):
@@ -492,4 +495,7 @@ def registry():
     import plan_ref_cases as pr
     for name in pr.names():
         reg[name] = (lambda n=name: pr.record(n))
+    import http_ref_cases as hr
+    for name in hr.names():
+        reg[name] = (lambda n=name: hr.record(n))
     return reg

@@ -1,10 +1,14 @@
 """Decoded header sections as HTTP messages on the host (qh_qpack_http_check,
-csrc/qh_httpmsg.c over csrc/qh_http_core.h).  The reference library cannot
-judge this step (the replay driver does not link nghttp3_http.c), so the
-anchor is a restatement in three parts: the reference's class tables as
-fixtures (tests/golden/http_chars.json, http_msg_chars.json), a Python model
-written from the reference and driven by those tables
-(tests/http_msg_model.py), and hand-written cases (tests/http_msg_cases.py).
+csrc/qh_httpmsg.c over csrc/qh_http_core.h).  The reference library itself
+judges this step in tests/test_http_ref.py and tests/test_gpu_http_ref.py:
+the replay driver links nghttp3_http.c, and its transcripts cover every case
+here that it can express, everything but the `priority` dictionary
+(oracle/README.md).  This file keeps the restatement in three parts, which
+also covers what the transcripts leave out (skipped sections, corrupted
+records, refusals): the reference's class tables as fixtures
+(tests/golden/http_chars.json, http_msg_chars.json), a Python model written
+from the reference and driven by those tables (tests/http_msg_model.py), and
+hand-written cases (tests/http_msg_cases.py).
 Here: the model against the tables and against landmarks stated outright,
 the host twin against the model on every case, and the twin under the
 sanitizers as a stand-alone program (tests/c/http_msg_check.c)."""

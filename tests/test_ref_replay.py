@@ -24,7 +24,7 @@ def test_every_case_has_a_transcript_and_every_transcript_a_case():
         path = os.path.join(rc.DIR, f)
         tr = rc.load(name)
         assert tr["case"] == name and tr["kind"] in ("encoder", "decoder tables", "decoder sections",
-                                                      "decoder stream", "planner")
+                                                      "decoder stream", "planner", "http")
         assert tr["conns"] and all(0 <= c < len(tr["conns"]) for c in tr["conn_of"])
         for steps in tr["conns"]:
             assert steps[0]["op"] == "new" and len(steps) > 1
