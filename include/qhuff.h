@@ -2084,6 +2084,179 @@ QH_EXPORT int qh_http_check_batch(
     const uint8_t *kind, qh_http_state *states, int8_t *fverdict, int32_t *status,
     uint32_t *bad_field, qh_field *kept, size_t kept_cap, uint32_t *kept_start, int where);
 
+/* ---- Request streams as they arrive: HTTP/3 frames cut per batch ----------
+ *
+ * What nghttp3_conn_read_bidi does with the bytes of a request stream
+ * (lib/nghttp3_conn.c:1514-1813): the frame type and length varints, which a
+ * packet may cut anywhere (nghttp3_read_varint, lib/nghttp3_stream.c:181-223),
+ * the HEADERS / DATA / unknown-frame state machine, which frames are legal
+ * when (nghttp3_stream_transit_rx_http_state, stream.c:1057-1226) and the body
+ * accounting against content-length (nghttp3_http_on_data_chunk and
+ * nghttp3_http_on_remote_end_stream, lib/nghttp3_http.c:629-649), for the
+ * chunks of many streams in one call.  Its output is the input of the pieces
+ * layer (qh_dec_partial_push_batch) and of the HTTP check.  Each call has a
+ * host form over host pointers and a device form over pointers in HBM (where
+ * must be QH_WHERE_DEVICE; counts are host scalars); both compile the same
+ * rules (csrc/qh_h3_core.h) and agree byte for byte on every output and
+ * every record.
+ *
+ * qh_h3_stream is the per-stream record, beside the stream's qh_http_state
+ * and caller-owned; chunk c owns rs[c] and hs[c] (the caller gathers and
+ * scatters, as for the HTTP check).  Layout (32 B):
+ *   left    rstate->left: payload bytes of the frame in progress still to
+ *           come (up to 2^62 - 1);
+ *   acc     rvint->acc: the value of the bytes of a cut varint read so far
+ *           (the first byte's length bits removed);
+ *   recv    recv_content_length;
+ *   state   QH_H3_ST_* (NGHTTP3_REQ_STREAM_STATE_*, lib/nghttp3_stream.h:77-84);
+ *   vleft   rvint->left: the bytes of the cut varint still missing (0 to 7);
+ *   fclass  QH_H3_F_*: the class of the frame in progress (set once its type
+ *           is read);
+ *   hstate  the rx HTTP state (NGHTTP3_HTTP_STATE_*, stream.h:133-151: 1
+ *           REQ_INITIAL .. 8 REQ_END, 9 RESP_INITIAL .. 16 RESP_END);
+ *   flags   QH_H3_RESPONSE (a client reading responses: selects RESP_INITIAL),
+ *           QH_H3_PENDING, QH_H3_SAW_DATA, QH_H3_SAW_END;
+ *   err     the first error, latched (0: none).
+ *
+ * read.  Chunk c is src[chunks[c].off, + len), the new bytes of stream
+ * chunk_sid[c] of table chunk_view[c], chunk_fin[c] != 0 when they end the
+ * stream.  Per chunk:
+ *   status[c]    QH_H3_OPEN, QH_H3_END, QH_H3_WAIT or the error;
+ *   consumed[c]  the bytes of the chunk that were walked;
+ *   nunknown[c]  (optional) the unknown frames begun (the reference's glitch
+ *                rate limiter, conn.c:1657, is per connection and timed: the
+ *                caller's).
+ * HEADERS pieces, compacted in chunk order: pieces[j] (a span into src),
+ * piece_sid, piece_view, piece_fin, piece_kind (QH_HTTP_REQUEST or 0, |
+ * QH_HTTP_TRAILERS), *npieces.  The first four go as they are into
+ * qh_dec_partial_push_batch, piece_kind (per finished section) to the HTTP
+ * check.  A chunk yields at most one piece, so room for nchunks entries always
+ * suffices and is required.  A piece exists only when at least one payload
+ * byte of a HEADERS frame lies in the chunk and carries fin only when it holds
+ * the frame's last byte.  Body spans: dspans[dspan_start[c], dspan_start[c +
+ * 1]) are the spans into src that recv_data would receive for chunk c, in
+ * order (dspan_start has nchunks + 1 entries).  When dspan_cap is short the
+ * call returns QH_ERR_NOMEM with the exact need in *ndspans and nothing else
+ * written.  Rules per chunk, in the reference's order:
+ *   1. an error is latched: status is that error, consumed 0, nothing changes;
+ *   2. QH_H3_PENDING is set: status QH_H3_WAIT, consumed 0, nothing changes and
+ *      fin is not acted on (conn.c:1533-1545 buffers a stream whose headers are
+ *      blocked); the caller feeds the same bytes again after the settle call;
+ *   3. else the chunk is walked as read_bidi walks it.  Varints are continued
+ *      from the record; one cut by fin is -606 in the type state and -602 in
+ *      the length state.  DATA: the transition, recv += the bytes,
+ *      on_data_chunk against hs[c], a span (an empty DATA frame makes its
+ *      transitions and no span).  HEADERS: the transition with its three tests
+ *      against hs[c] (METH_CONNECT; status_code == -1 after a 1xx; CONNECT
+ *      with a 2xx); length 0 outside trailers is -107, empty trailers begin
+ *      and end with no piece.  The eleven types of conn.c:1643-1653 are -601
+ *      once their length is read; every other type is skipped and counted.
+ *      fin at a frame boundary is MSG_END (on_remote_end_stream, status
+ *      QH_H3_END), anywhere else -602; in QH_H3_ST_IGN_REST (set by the caller,
+ *      conn.c:506) everything is consumed and fin ends nothing.
+ *      The one departure: when a HEADERS frame that is not trailers ends, the
+ *      record gains QH_H3_PENDING, because hs[c] does not know that section
+ *      yet.  For the rest of the call DATA frames are taken provisionally
+ *      (QH_H3_SAW_DATA, counted into recv, spans emitted), unknown frames are
+ *      skipped, refused types are still -601, fin at a boundary sets
+ *      QH_H3_SAW_END with status 0, and a HEADERS frame stops the walk as soon
+ *      as its type is known: consumed[c] is the offset of that frame's first
+ *      byte, the record is clean in the type state, status QH_H3_WAIT;
+ *   4. on an error the record is left as on entry with the error latched,
+ *      consumed[c] is the offset of the first byte of the frame at which it
+ *      arose (0 when that lies in an earlier chunk), and the piece and spans
+ *      of the chunk that precede it stay.
+ * Returns 0; QH_ERR_INVALID_ARGUMENT with nothing written for a NULL argument
+ * that is needed, nchunks of 2^27 or more, or a record that no call here
+ * leaves (state, vleft, fclass, hstate or flags out of range); QH_ERR_NOMEM as
+ * above.  No byte outside a chunk is read: src needs no padding.  Device: a
+ * lane per chunk hops from frame header to frame header (payloads are not
+ * read) and counts, one scan over two segments, one host wait (the totals and
+ * the list's errors), then a lane per chunk replays the walk and writes.
+ *
+ * settle, after the HTTP check, for the streams whose section was checked:
+ * rs[j], hs[j] (now including the section), sec_status[j] (the check's status;
+ * NULL: all 0).  A record without QH_H3_PENDING is untouched, status 0.
+ * sec_status[j] < 0 is latched and returned.  Otherwise what rule 3 deferred,
+ * in stream order: (1) QH_H3_SAW_DATA with EXPECT_FINAL_RESPONSE is -601
+ * (stream.c:1166); (2) content_length != -1 and recv > content_length is -107
+ * (on_data_chunk); (3) QH_H3_SAW_END with EXPECT_FINAL_RESPONSE or a
+ * content_length that differs from recv is -107 (on_remote_end_stream); (4)
+ * else the three flags are cleared, status QH_H3_END and hstate *_END when
+ * the end was seen, else 0.  An error is latched and leaves the rest of the
+ * record as it was (a later settle of that record answers the same error).  The device form is asynchronous on the context stream,
+ * with no host wait, and reads no stream bytes.
+ *
+ * A round is read -> partial push -> sections -> emit -> HTTP check ->
+ * settle.  A stream with headers, body and fin in one chunk is finished in
+ * that round; headers and trailers in one chunk, a 1xx and the final response
+ * in one chunk, or a blocked section are fed their rest in the next.
+ *
+ * Departures: the body spans of a call are valid only once the settle answers
+ * non-negative (the reference would have refused the overflowing chunk before
+ * recv_data); -107 for a body is reported at settle, not at the byte where it
+ * occurs; begin_headers / end_headers with fin have no output; the caller's
+ * QUIC stream buffer holds the tail after QH_H3_WAIT (consumed says where it
+ * begins).  Not built: frame writing, the control stream and SETTINGS,
+ * `priority`, QH_WHERE_HOST staging, a tail log as qh_ustream_* keeps. */
+#define QH_ERR_MALFORMED_HTTP_MESSAGING (-107)   /* nghttp3.h:210 */
+#define QH_ERR_H3_FRAME_UNEXPECTED (-601)        /* nghttp3.h:273 */
+#define QH_ERR_H3_FRAME_ERROR (-602)             /* nghttp3.h:280 */
+#define QH_ERR_H3_GENERAL_PROTOCOL_ERROR (-606)  /* nghttp3.h:307 */
+
+#define QH_H3_OPEN 0 /* status: the stream goes on                         */
+#define QH_H3_END 1  /* status: the message ended (MSG_END)                */
+#define QH_H3_WAIT 2 /* status: settle first, then feed from consumed on   */
+
+#define QH_H3_ST_FRAME_TYPE 0
+#define QH_H3_ST_FRAME_LENGTH 1
+#define QH_H3_ST_DATA 2
+#define QH_H3_ST_HEADERS 3
+#define QH_H3_ST_IGN_FRAME 4
+#define QH_H3_ST_IGN_REST 5
+
+#define QH_H3_F_NONE 0
+#define QH_H3_F_DATA 1    /* NGHTTP3_FRAME_DATA 0x00, lib/nghttp3_frame.h:37 */
+#define QH_H3_F_HEADERS 2 /* NGHTTP3_FRAME_HEADERS 0x01                      */
+#define QH_H3_F_REFUSED 3 /* the eleven types of conn.c:1643-1653            */
+#define QH_H3_F_UNKNOWN 4
+
+#define QH_H3_RESPONSE 0x1u
+#define QH_H3_PENDING 0x2u  /* a HEADERS section is on its way through the check */
+#define QH_H3_SAW_DATA 0x4u /* ... and a DATA frame began behind it              */
+#define QH_H3_SAW_END 0x8u  /* ... and the stream ended behind it                */
+
+typedef struct qh_h3_stream { /* 32 B */
+  uint64_t left;
+  uint64_t acc;
+  int64_t recv;
+  uint8_t state, vleft, fclass, hstate;
+  uint16_t flags;
+  int16_t err;
+} qh_h3_stream;
+/* FRAME_TYPE, REQ_INITIAL (response != 0: RESP_INITIAL and QH_H3_RESPONSE). */
+QH_EXPORT void qh_h3_stream_init(qh_h3_stream *rs, size_t n, int response);
+
+QH_EXPORT int qh_qpack_h3_read(
+    const uint8_t *src, const qh_span_in *chunks, const uint8_t *chunk_fin,
+    const uint64_t *chunk_sid, const uint32_t *chunk_view, size_t nchunks, qh_h3_stream *rs,
+    const qh_http_state *hs, int32_t *status, uint32_t *consumed, uint32_t *nunknown,
+    qh_span_in *pieces, uint64_t *piece_sid, uint32_t *piece_view, uint8_t *piece_fin,
+    uint8_t *piece_kind, uint64_t *npieces, uint64_t *dspan_start, qh_span_in *dspans,
+    uint64_t dspan_cap, uint64_t *ndspans);
+QH_EXPORT int qh_h3_read_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *chunks, const uint8_t *chunk_fin,
+    const uint64_t *chunk_sid, const uint32_t *chunk_view, size_t nchunks, qh_h3_stream *rs,
+    const qh_http_state *hs, int32_t *status, uint32_t *consumed, uint32_t *nunknown,
+    qh_span_in *pieces, uint64_t *piece_sid, uint32_t *piece_view, uint8_t *piece_fin,
+    uint8_t *piece_kind, uint64_t *npieces, uint64_t *dspan_start, qh_span_in *dspans,
+    uint64_t dspan_cap, uint64_t *ndspans, int where);
+
+QH_EXPORT int qh_qpack_h3_settle(qh_h3_stream *rs, const qh_http_state *hs,
+                                 const int32_t *sec_status, size_t n, int32_t *status);
+QH_EXPORT int qh_h3_settle_batch(qh_ctx *ctx, qh_h3_stream *rs, const qh_http_state *hs,
+                                 const int32_t *sec_status, size_t n, int32_t *status, int where);
+
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);
 

@@ -18,7 +18,11 @@ LIB_PATH = os.environ.get("QHUFF_LIB", LIB_PATH)
 QH_OK = 0
 QH_ERR_INVALID_ARGUMENT = -101
 QH_ERR_MALFORMED_HTTP_HEADER = -105
+QH_ERR_MALFORMED_HTTP_MESSAGING = -107
 QH_ERR_QPACK_FATAL = -108
+QH_ERR_H3_FRAME_UNEXPECTED = -601
+QH_ERR_H3_FRAME_ERROR = -602
+QH_ERR_H3_GENERAL_PROTOCOL_ERROR = -606
 QH_ERR_FATAL = -900
 QH_ERR_NOMEM = -901
 
@@ -248,6 +252,12 @@ EXPORTED_FUNCTIONS = (
     "qh_http_state_init",
     "qh_qpack_http_check",
     "qh_http_check_batch",
+    # request streams as they arrive: HTTP/3 frames cut per batch (csrc/qh_h3.c, csrc/qh_h3.inc)
+    "qh_h3_stream_init",
+    "qh_qpack_h3_read",
+    "qh_h3_read_batch",
+    "qh_qpack_h3_settle",
+    "qh_h3_settle_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

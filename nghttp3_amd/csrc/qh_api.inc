@@ -48,6 +48,7 @@ enum BufId {
   kBufUstream,      // the calls for streams as they arrive (qh_ustream.inc): owner words, lengths, copy items, scan headers
   kBufDynIndex,     // qh_dyn_index_batch: per-view needs, the wave kernel's list, owner words, the scan header
   kBufHttp,         // qh_http_check_batch: per-section KEEP counts, the scan header
+  kBufH3,           // qh_h3_read_batch: per-chunk piece and span counts, the scan header
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap

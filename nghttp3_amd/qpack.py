@@ -99,6 +99,17 @@ HTTP_REQUEST, HTTP_TRAILERS, HTTP_CONNECT_PROTOCOL = 1, 2, 4
 HTTP_KEEP, HTTP_REMOVE, HTTP_MALFORMED, HTTP_UNSEEN = range(4)
 HTTP_NO_FIELD = 0xFFFFFFFF
 QH_ERR_MALFORMED_HTTP_HEADER = -105
+# include/qhuff.h qh_h3_stream, QH_H3_*
+H3_STREAM_DTYPE = np.dtype([("left", "<u8"), ("acc", "<u8"), ("recv", "<i8"), ("state", "u1"), ("vleft", "u1"),
+                            ("fclass", "u1"), ("hstate", "u1"), ("flags", "<u2"), ("err", "<i2")])
+assert H3_STREAM_DTYPE.itemsize == 32
+H3_OPEN, H3_END, H3_WAIT = 0, 1, 2
+H3_ST_FRAME_TYPE, H3_ST_FRAME_LENGTH, H3_ST_DATA, H3_ST_HEADERS, H3_ST_IGN_FRAME, H3_ST_IGN_REST = range(6)
+H3_RESPONSE, H3_PENDING, H3_SAW_DATA, H3_SAW_END = 0x1, 0x2, 0x4, 0x8
+QH_ERR_MALFORMED_HTTP_MESSAGING = -107
+QH_ERR_H3_FRAME_UNEXPECTED = -601
+QH_ERR_H3_FRAME_ERROR = -602
+QH_ERR_H3_GENERAL_PROTOCOL_ERROR = -606
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
 
@@ -271,6 +282,11 @@ def _load():
         lib.qh_http_state_init.argtypes = [vp, sz]
         lib.qh_http_state_init.restype = None
         _pair(lib, "http_check", [vp, sz, vp, sz, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, vp])
+        lib.qh_h3_stream_init.argtypes = [vp, sz, i32]
+        lib.qh_h3_stream_init.restype = None
+        _pair(lib, "h3_read", [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pu64, vp, vp,
+                               u64, pu64])
+        _pair(lib, "h3_settle", [vp, vp, vp, sz, vp])
         _L = lib
     return _L
 
@@ -934,6 +950,142 @@ def http_states(n: int):
     if n:
         _load().qh_http_state_init(_vp(st), n)
     return st
+
+
+# ---- request streams as they arrive (qh_qpack_h3_read / qh_h3_read_batch, _settle) ----
+
+def h3_streams(n: int, response: bool = False):
+    """n fresh H3_STREAM_DTYPE records (qh_h3_stream_init): the type state and
+    REQ_INITIAL, or RESP_INITIAL with H3_RESPONSE for a client reading
+    responses."""
+    rs = np.zeros(n, dtype=H3_STREAM_DTYPE)
+    if n:
+        _load().qh_h3_stream_init(_vp(rs), n, 1 if response else 0)
+    return rs
+
+
+# The outputs of a read: name -> bytes per chunk (dspan_start has one entry more).
+_H3_OUT = (("status", 4), ("consumed", 4), ("nunknown", 4), ("pieces", 16), ("piece_sid", 8),
+           ("piece_view", 4), ("piece_fin", 1), ("piece_kind", 1))
+
+
+def h3_read_raw(be, src, chunks, chunk_fin, chunk_sid, chunk_view, nchunks, rs, hs, o, dspan_cap,
+                codec=None):
+    """The call over byte arrays of backend `be` -> (rv, npieces, ndspans).
+    `o`: the outputs of _H3_OUT plus dspan_start and dspans (nunknown and
+    dspans may be None); dspan_cap the room of dspans in spans."""
+    np_, nd = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rv = be.call(_load(), "h3_read", be.ptr(src), be.ptr(chunks), be.ptr(chunk_fin), be.ptr(chunk_sid),
+                 be.ptr(chunk_view), nchunks, be.ptr(rs), be.ptr(hs), be.ptr(o["status"]),
+                 be.ptr(o["consumed"]), be.ptr(o.get("nunknown")), be.ptr(o["pieces"]),
+                 be.ptr(o["piece_sid"]), be.ptr(o["piece_view"]), be.ptr(o["piece_fin"]),
+                 be.ptr(o["piece_kind"]), ctypes.byref(np_), be.ptr(o["dspan_start"]),
+                 be.ptr(o.get("dspans")), dspan_cap, ctypes.byref(nd), codec=codec)
+    return rv, int(np_.value), int(nd.value)
+
+
+def _h3_read(be, src, chunks, chunk_fin, chunk_sid, chunk_view, n, rs, hs, bufs, codec=None):
+    b = bufs or {}
+    if b.get("n", -1) < n:
+        b = {"n": n, "dspan_cap": b.get("dspan_cap", 0), "dspans": b.get("dspans")}
+        for name, unit in _H3_OUT:
+            b[name] = be.empty(max(n, 1) * unit)
+        b["dspan_start"] = be.empty((n + 1) * 8)
+    if b["dspans"] is None:
+        b["dspan_cap"] = cap_for(n, 64)
+        b["dspans"] = be.empty(b["dspan_cap"] * 16)
+
+    def attempt():
+        rv, npieces, nd = h3_read_raw(be, src, chunks, chunk_fin, chunk_sid, chunk_view, n, rs, hs, b,
+                                      b["dspan_cap"], codec=codec)
+        return rv, (npieces, nd)
+
+    def more(needs):
+        b["dspan_cap"] = cap_for(needs[1], 64)
+        b["dspans"] = be.empty(b["dspan_cap"] * 16)
+
+    _, (b["npieces"], b["ndspans"]) = be.retry("h3_read", attempt, more)
+    return b
+
+
+def h3_read(src, chunks, chunk_fin, chunk_sid, chunk_view, rs, hs):
+    """Host arrays: the new bytes of many request streams cut into HTTP/3
+    frames as nghttp3_conn_read_bidi cuts them.  chunks: SPAN_IN_DTYPE spans
+    into src, one per stream, with chunk_fin (uint8), chunk_sid (uint64) and
+    chunk_view (uint32); rs: H3_STREAM_DTYPE records (``h3_streams``), updated
+    in place; hs: HTTP_STATE_DTYPE records (``http_states``), read only.  ->
+    dict: status (H3_OPEN, H3_END, H3_WAIT or the error), consumed, nunknown per
+    chunk; pieces (SPAN_IN_DTYPE), piece_sid, piece_view, piece_fin, piece_kind
+    of the npieces HEADERS pieces, as qh_dec_partial_push takes them; dspans
+    (SPAN_IN_DTYPE) and dspan_start (uint64, one entry more than chunks): the
+    body spans.  Runs on the host (qh_qpack_h3_read)."""
+    src = _u8(src)
+    chunks = np.ascontiguousarray(chunks, SPAN_IN_DTYPE)
+    n = chunks.size
+    fin, sid = np.ascontiguousarray(chunk_fin, np.uint8), np.ascontiguousarray(chunk_sid, np.uint64)
+    view = np.ascontiguousarray(chunk_view, np.uint32)
+    if fin.size != n or sid.size != n or view.size != n or rs.dtype != H3_STREAM_DTYPE or rs.size != n or \
+            hs.dtype != HTTP_STATE_DTYPE or hs.size != n or not rs.flags.c_contiguous:
+        raise ValueError("h3_read: one fin, sid, view, stream record and HTTP state per chunk")
+    hs = np.ascontiguousarray(hs)
+    be = Backend()
+    b = _h3_read(be, src, chunks.view(np.uint8), fin, sid.view(np.uint8), view.view(np.uint8), n,
+                 rs.view(np.uint8), hs.view(np.uint8), None)
+    npieces, nd = b["npieces"], b["ndspans"]
+    return {"status": b["status"].view(np.int32)[:n], "consumed": b["consumed"].view(np.uint32)[:n],
+            "nunknown": b["nunknown"].view(np.uint32)[:n], "npieces": npieces, "ndspans": nd,
+            "pieces": b["pieces"].view(SPAN_IN_DTYPE)[:npieces],
+            "piece_sid": b["piece_sid"].view(np.uint64)[:npieces],
+            "piece_view": b["piece_view"].view(np.uint32)[:npieces],
+            "piece_fin": b["piece_fin"][:npieces], "piece_kind": b["piece_kind"][:npieces],
+            "dspan_start": b["dspan_start"].view(np.uint64), "dspans": b["dspans"].view(SPAN_IN_DTYPE)[:nd],
+            "rs": rs}
+
+
+def h3_read_dev(codec: HuffmanBatchCodec, src, chunks, chunk_fin, chunk_sid, chunk_view, rs, hs, bufs=None):
+    """Device-resident form (qh_h3_read_batch): uint8 tensors holding the same
+    records (chunks [n * 16], chunk_fin [n], chunk_sid [n * 8], chunk_view
+    [n * 4], rs [n * 32] updated in place, hs [n * 16]).  -> dict of uint8
+    tensors named as h3_read's arrays, with room for n chunks (the first
+    npieces / ndspans entries are written), plus the host integers npieces and
+    ndspans; `bufs` (a previous result) reuses its allocations.  One host wait,
+    for the two totals."""
+    n = int(chunk_fin.shape[0])
+    return _h3_read(Backend(chunk_fin.device), src, chunks, chunk_fin, chunk_sid, chunk_view, n, rs, hs,
+                    bufs, codec=codec)
+
+
+def h3_settle(rs, hs, sec_status=None):
+    """Host arrays: the records of the streams whose section the HTTP check
+    has judged, settled in place (hs now includes the section; sec_status the
+    check's status per stream, None: all 0).  -> status (int32: 0, H3_END or
+    the error).  Runs on the host (qh_qpack_h3_settle)."""
+    n = rs.size
+    if rs.dtype != H3_STREAM_DTYPE or hs.dtype != HTTP_STATE_DTYPE or hs.size != n or \
+            not rs.flags.c_contiguous:
+        raise ValueError("h3_settle: one HTTP state per stream record")
+    st = None if sec_status is None else np.ascontiguousarray(sec_status, np.int32)
+    if st is not None and st.size != n:
+        raise ValueError("h3_settle: one section status per stream record")
+    status = np.zeros(n, np.int32)
+    be = Backend()
+    hs = np.ascontiguousarray(hs)
+    rv = be.call(_load(), "h3_settle", be.ptr(rs.view(np.uint8)), be.ptr(hs.view(np.uint8)),
+                 None if st is None else be.ptr(st.view(np.uint8)), n, be.ptr(status.view(np.uint8)))
+    be.check(rv, "h3_settle")
+    return status
+
+
+def h3_settle_dev(codec: HuffmanBatchCodec, rs, hs, sec_status, status):
+    """Device-resident form (qh_h3_settle_batch): rs a uint8 tensor [n * 32]
+    updated in place, hs uint8 [n * 16], sec_status int32 [n] or None, status
+    int32 [n] filled.  Asynchronous on the context's stream: no host wait."""
+    n = int(status.shape[0])
+    be = Backend(status.device)
+    rv = be.call(_load(), "h3_settle", be.ptr(rs), be.ptr(hs), be.ptr(sec_status), n, be.ptr(status),
+                 codec=codec)
+    be.check(rv, "h3_settle")
+    return status
 
 
 class DynamicTable:
