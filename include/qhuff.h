@@ -227,11 +227,18 @@ QH_EXPORT int qh_ctx_set_encoder(qh_ctx *ctx, int kind);
  * QH_OPT_EMIT_LONG_MIN: qh_emit_fields_batch copies a name or value of at
  *   least `value` bytes with a wave instead of a lane; 0 (default) lets the
  *   library choose (else 16 .. 2^30).
+ * QH_OPT_H3W_LONG_MIN: qh_h3_write_batch copies a payload of at least `value`
+ *   bytes with waves, cut into pieces, instead of a 16-lane group; 0 (default)
+ *   lets the library choose (else 16 .. 2^30).
+ * QH_OPT_H3W_PIECE: the most bytes of such a payload that one wave copies; 0
+ *   (default) lets the library choose (else 1024 .. 2^30).
  * No reference counterpart (the reference codec has no batch kernels). */
 #define QH_OPT_LONG_MIN 1
 #define QH_OPT_LENS_LANE_PASS 2
 #define QH_OPT_SECTIONS_SLICE_BLOCKS 3
 #define QH_OPT_EMIT_LONG_MIN 4
+#define QH_OPT_H3W_LONG_MIN 5
+#define QH_OPT_H3W_PIECE 6
 QH_EXPORT int qh_ctx_set_option(qh_ctx *ctx, int option, int64_t value);
 QH_EXPORT void *qh_ctx_stream(qh_ctx *ctx);
 /* Wait for all work queued on the context's stream. */
@@ -2197,8 +2204,9 @@ QH_EXPORT int qh_http_check_batch(
  * recv_data); -107 for a body is reported at settle, not at the byte where it
  * occurs; begin_headers / end_headers with fin have no output; the caller's
  * QUIC stream buffer holds the tail after QH_H3_WAIT (consumed says where it
- * begins).  Not built: frame writing, the control stream and SETTINGS,
- * `priority`, QH_WHERE_HOST staging, a tail log as qh_ustream_* keeps. */
+ * begins).  Not built: the control stream and SETTINGS, `priority`,
+ * QH_WHERE_HOST staging, a tail log as qh_ustream_* keeps.  (Frame writing is
+ * the next section.) */
 #define QH_ERR_MALFORMED_HTTP_MESSAGING (-107)   /* nghttp3.h:210 */
 #define QH_ERR_H3_FRAME_UNEXPECTED (-601)        /* nghttp3.h:273 */
 #define QH_ERR_H3_FRAME_ERROR (-602)             /* nghttp3.h:280 */
@@ -2256,6 +2264,130 @@ QH_EXPORT int qh_qpack_h3_settle(qh_h3_stream *rs, const qh_http_state *hs,
                                  const int32_t *sec_status, size_t n, int32_t *status);
 QH_EXPORT int qh_h3_settle_batch(qh_ctx *ctx, qh_h3_stream *rs, const qh_http_state *hs,
                                  const int32_t *sec_status, size_t n, int32_t *status, int where);
+
+/* ---- Response and request streams as they leave: HTTP/3 frames written ------
+ *
+ * What nghttp3_stream_write_header_block and nghttp3_stream_write_data put in
+ * front of a field section and of body bytes (lib/nghttp3_stream.c:492-703:
+ * nghttp3_frame_write_hd, lib/nghttp3_frame.c:34-43, two shortest-form varints
+ * as nghttp3_put_uvarint writes them), for many streams in one call.  The
+ * sections lie where qh_encode_fields_batch, qh_encode_fields_dyn_batch or
+ * qh_encode_conns_batch left them (dst and sections[]), the bodies in a second
+ * buffer; the call writes the bytes of each stream's frames, contiguous and in
+ * stream order, into one buffer.  A host form over host pointers and a device
+ * form over pointers in HBM (where must be QH_WHERE_DEVICE; counts are host
+ * scalars); both compile the same rules (csrc/qh_h3w_core.h) and agree byte
+ * for byte on every output and every record.
+ *
+ * qh_h3_item is one frame to write (32 B):
+ *   span   the payload, bytes [off, off + len) of one of the two sources
+ *          (span.flags is ignored);
+ *   type   the frame type: 0 DATA, 1 HEADERS (lib/nghttp3_frame.h:37-38); any
+ *          other value up to 2^62 - 1 is written as given, so a caller can send
+ *          a frame whose payload it built itself, or a reserved type;
+ *   src    0: hsrc (the section writer's dst, so that sections[k] goes in as it
+ *          is), 1: dsrc (bodies);
+ *   flags  QH_H3W_END: the stream ends after this item.  This is the
+ *          reference's NGHTTP3_STREAM_FLAG_WRITE_END_STREAM: a request or
+ *          response submitted without a data reader (conn.c:2553-2555, :2591-2593), a data
+ *          reader's EOF without NGHTTP3_DATA_FLAG_NO_END_STREAM
+ *          (stream.c:641-644), or trailers (conn.c:2614).
+ * qh_h3_tx is the per-stream record, caller-owned, beside the stream's other
+ * records (16 B): off, the stream offset of the next byte, which is the sum of
+ * everything written so far; flags, QH_H3W_ENDED; rsv, zero.
+ *
+ * write.  Stream s owns items[item_start[s], item_start[s + 1]) (item_start has
+ * nstreams + 1 entries) and tx[s].  Per stream:
+ *   out[s]     a span into dst: the bytes of stream s of this call, contiguous,
+ *              the streams in order (out[s].off is the sum of the lengths
+ *              before it);
+ *   fin[s]     1 when this call ended the stream;
+ *   status[s]  0 or QH_ERR_INVALID_STATE.
+ * out, fin, a stream-id array and a view array are exactly the chunks,
+ * chunk_fin, chunk_sid and chunk_view of qh_h3_read_batch on the peer, with
+ * dst as its src.  Rules per stream, items in order:
+ *   1. (the project's own rule) tx[s].flags has QH_H3W_ENDED and the stream has
+ *      at least one item, or an item follows one that carries QH_H3W_END in
+ *      the same call: status QH_ERR_INVALID_STATE, nothing is written for the
+ *      stream, out[s].len and fin[s] are 0, the record is unchanged, and the
+ *      other streams proceed.  The reference answers this only for trailers
+ *      (conn.c:2610-2612) and leaves the other submits as a TODO
+ *      (conn.c:2564, :2582, :2602);
+ *   2. a DATA item of length 0 writes no frame (stream.c:645-663); its
+ *      QH_H3W_END still ends the stream;
+ *   3. every other item writes qh_h3_write_hd(type, len) followed by the len
+ *      payload bytes (stream.c:666-700; HEADERS :521-535).  A HEADERS item of
+ *      length 0 is written as it is.  Payloads and the order of frames are not
+ *      judged; the reference does not judge them either;
+ *   4. fin[s] is 1 and the record gains QH_H3W_ENDED iff an item carried
+ *      QH_H3W_END; tx[s].off advances by out[s].len.  A stream without items
+ *      has length 0, fin 0, status 0.
+ * Returns 0; QH_ERR_INVALID_ARGUMENT with nothing written for a NULL argument
+ * that is needed (dst_need; with streams item_start, tx, out, fin, status;
+ * items when a stream has one; the source of an item that has bytes; dst when
+ * bytes are to be written and dst_cap has room), nstreams of 2^27 or more,
+ * an item_start that decreases, a type of 2^62 or more, src above 1, an item
+ * flag or a record flag that is not defined (or rsv not 0), or a stream whose
+ * bytes of this call pass 2^32 - 1; QH_ERR_NOMEM when dst_cap is short, with
+ * the exact need in *dst_need and nothing else written (no dst, out, fin,
+ * status or record; a NULL dst with dst_cap 0 is the sizing call).  *dst_need
+ * is the sum of the out lengths after every other return of 0.  No byte
+ * outside an item's span is read and no byte outside [dst, dst + need) is
+ * written: the sources and dst need neither padding nor alignment.
+ *
+ * Device: a lane per stream checks and counts (qh_k_h3w_count), one scan over
+ * two segments, one host wait (the byte total, the long payloads' pieces, the
+ * list's errors), then a 16-lane group per stream places its frames, writes
+ * the headers and copies the payloads below QH_OPT_H3W_LONG_MIN bytes
+ * (qh_k_h3w_write); longer payloads are listed in pieces of at most
+ * QH_OPT_H3W_PIECE bytes and copied a wave per piece (qh_k_emit_copy_long).
+ *
+ * qh_h3_write_hd / qh_h3_write_hd_len are host drop-ins for
+ * nghttp3_frame_write_hd / nghttp3_frame_write_hd_len (frame.c:34-43): type
+ * and len below 2^62, p with room for qh_h3_write_hd_len bytes (at most 16);
+ * the return is the byte behind the header.
+ *
+ * Departures: the output is one contiguous run per stream, copied (the
+ * reference hands writev_stream a vector list and never copies a body); one
+ * DATA item is one frame (the reference joins up to eight vectors of one
+ * read_data call, stream.c:613-634); flow control, add_write_offset and the
+ * retention of unacknowledged bytes stay with the caller's QUIC stream
+ * buffer, of which dst is the input, as the reader leaves the unread tail
+ * there.  Not built: the control stream and the SETTINGS / GOAWAY /
+ * PRIORITY_UPDATE payloads (a caller sends them as an item with its own
+ * payload), the unidirectional streams' type byte, a vector-list output
+ * without the copy, QH_WHERE_HOST staging. */
+#define QH_ERR_INVALID_STATE (-102) /* nghttp3.h:175 */
+
+#define QH_H3W_END 0x1u   /* qh_h3_item.flags: the stream ends after this item */
+#define QH_H3W_ENDED 0x1u /* qh_h3_tx.flags: the stream has ended              */
+
+typedef struct qh_h3_item { /* 32 B */
+  qh_span_in span;
+  uint64_t type;
+  uint32_t src;
+  uint32_t flags;
+} qh_h3_item;
+
+typedef struct qh_h3_tx { /* 16 B */
+  uint64_t off;
+  uint32_t flags;
+  uint32_t rsv;
+} qh_h3_tx;
+/* off 0, no flags. */
+QH_EXPORT void qh_h3_tx_init(qh_h3_tx *tx, size_t n);
+
+QH_EXPORT uint8_t *qh_h3_write_hd(uint8_t *p, uint64_t type, uint64_t len);
+QH_EXPORT size_t qh_h3_write_hd_len(uint64_t type, uint64_t len);
+
+QH_EXPORT int qh_qpack_h3_write(
+    const uint8_t *hsrc, const uint8_t *dsrc, const qh_h3_item *items, const uint32_t *item_start,
+    size_t nstreams, qh_h3_tx *tx, uint8_t *dst, uint64_t dst_cap, uint64_t *dst_need,
+    qh_span_in *out, uint8_t *fin, int32_t *status);
+QH_EXPORT int qh_h3_write_batch(
+    qh_ctx *ctx, const uint8_t *hsrc, const uint8_t *dsrc, const qh_h3_item *items,
+    const uint32_t *item_start, size_t nstreams, qh_h3_tx *tx, uint8_t *dst, uint64_t dst_cap,
+    uint64_t *dst_need, qh_span_in *out, uint8_t *fin, int32_t *status, int where);
 
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("QHUFF_LIB", LIB_PATH)
 
 QH_OK = 0
 QH_ERR_INVALID_ARGUMENT = -101
+QH_ERR_INVALID_STATE = -102
 QH_ERR_MALFORMED_HTTP_HEADER = -105
 QH_ERR_MALFORMED_HTTP_MESSAGING = -107
 QH_ERR_QPACK_FATAL = -108
@@ -41,6 +42,8 @@ QH_OPT_LONG_MIN = 1
 QH_OPT_LENS_LANE_PASS = 2
 QH_OPT_SECTIONS_SLICE_BLOCKS = 3
 QH_OPT_EMIT_LONG_MIN = 4
+QH_OPT_H3W_LONG_MIN = 5
+QH_OPT_H3W_PIECE = 6
 QH_SECTIONS_DTABLE0 = 0x1
 QH_SECTIONS_PACKED = 0x2
 QH_IN_SRC, QH_IN_DST, QH_IN_STATIC, QH_IN_DYN, QH_IN_OUT = range(5)
@@ -258,6 +261,12 @@ EXPORTED_FUNCTIONS = (
     "qh_h3_read_batch",
     "qh_qpack_h3_settle",
     "qh_h3_settle_batch",
+    # response and request streams as they leave: HTTP/3 frames written per batch (csrc/qh_h3w.c, csrc/qh_h3w.inc)
+    "qh_h3_tx_init",
+    "qh_h3_write_hd",
+    "qh_h3_write_hd_len",
+    "qh_qpack_h3_write",
+    "qh_h3_write_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -49,6 +49,8 @@ enum BufId {
   kBufDynIndex,     // qh_dyn_index_batch: per-view needs, the wave kernel's list, owner words, the scan header
   kBufHttp,         // qh_http_check_batch: per-section KEEP counts, the scan header
   kBufH3,           // qh_h3_read_batch: per-chunk piece and span counts, the scan header
+  kBufH3W,          // qh_h3_write_batch: per-stream byte and piece counts, the scan header
+  kBufH3WWork,      // ... the long payloads' pieces
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap
@@ -132,6 +134,8 @@ struct qh_ctx {
   uint64_t es_nl_hint = 0;  // the most lines a call has seen (kBufEncSecLoff's capacity)
   hipEvent_t es_ev = nullptr;  // recorded after the copy into kBufEncSecHost
   uint32_t emit_long_min = 0;  // QH_OPT_EMIT_LONG_MIN (0: kEmitLongMin, qh_emit.inc)
+  uint32_t h3w_long_min = 0;   // QH_OPT_H3W_LONG_MIN (0: kH3wLongMin, qh_h3w.inc)
+  uint32_t h3w_piece = 0;      // QH_OPT_H3W_PIECE (0: kH3wPiece)
   // the instructions, spans, Huffman spans and decode-slot bytes the last
   // qh_dtables_apply_batch call parsed, and its stream count (the next call's
   // work buffer is laid out from them before its own totals are known)
@@ -1587,6 +1591,14 @@ QH_EXPORT int qh_ctx_set_option(qh_ctx *c, int option, int64_t value) {
     case QH_OPT_EMIT_LONG_MIN:
       if (value != 0 && (value < 16 || value > (1ll << 30))) return QH_ERR_INVALID_ARGUMENT;
       c->emit_long_min = (uint32_t)value;
+      return 0;
+    case QH_OPT_H3W_LONG_MIN:
+      if (value != 0 && (value < 16 || value > (1ll << 30))) return QH_ERR_INVALID_ARGUMENT;
+      c->h3w_long_min = (uint32_t)value;
+      return 0;
+    case QH_OPT_H3W_PIECE:
+      if (value != 0 && (value < 1024 || value > (1ll << 30))) return QH_ERR_INVALID_ARGUMENT;
+      c->h3w_piece = (uint32_t)value;
       return 0;
     default:
       return QH_ERR_INVALID_ARGUMENT;

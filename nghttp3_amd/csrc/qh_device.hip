@@ -25,6 +25,7 @@
 //   qh_k_us_*          encoder and decoder streams as they arrive: cut instructions held
 //   qh_k_http_*        decoded sections as HTTP messages: field verdicts, the kept records
 //   qh_k_h3_*          request streams as they arrive: HTTP/3 frames cut, body accounting, settle
+//   qh_k_h3w_*         streams as they leave: HTTP/3 frame headers written, payloads copied
 //   qh_k_idx_*         the hashed index over the views' keys: count, build
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
 // The kernels from qh_k_encsec_* to qh_k_http_* work a 16-lane group per table,
@@ -96,4 +97,5 @@
 #include "qh_ustream.inc"       // encoder and decoder streams as they arrive: cut instructions held; join, keep, sections, compact
 #include "qh_httpmsg.inc"       // decoded sections as HTTP messages: fields kept, removed or malformed, the state per stream
 #include "qh_h3.inc"            // request streams as they arrive: frames cut into HEADERS pieces and body spans; settle
+#include "qh_h3w.inc"           // response and request streams as they leave: frames placed, headers written, payloads copied
 

@@ -235,9 +235,10 @@ __global__ void __launch_bounds__(256) qh_k_emit_write(
 // A wave per listed string: lane l of round r copies the 16 bytes at
 // min(1024 r + 16 l, n - 16) (n >= 16: the last piece overlaps the one
 // before it), four rounds' loads ahead of their stores.
+// *count: the number of listed strings (a word the listing pass left on the device).
 __global__ void __launch_bounds__(256) qh_k_emit_copy_long(const EmLong *__restrict__ list,
-                                                           const uint64_t *__restrict__ hdr) {
-  const uint64_t n = hdr[kEmLong];
+                                                           const uint64_t *__restrict__ count) {
+  const uint64_t n = *count;
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t w = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
@@ -389,6 +390,6 @@ QH_EXPORT int qh_emit_fields_batch(qh_ctx *c, const uint8_t *src, const qh_span_
                       reinterpret_cast<qhk::SpanIn *>(e->out_blocks), long_min, list, hdr)))
     return rv;
   if (e->out && h[5])  // (some string is long; the list's length is read on the device)
-    return QH_LAUNCH_GRID(c, qh_k_emit_copy_long, std::min(c->num_cus, 256), 256, list, hdr);
+    return QH_LAUNCH_GRID(c, qh_k_emit_copy_long, std::min(c->num_cus, 256), 256, list, hdr + qhk::kEmLong);
   return 0;
 }

@@ -108,6 +108,15 @@ H3_ST_FRAME_TYPE, H3_ST_FRAME_LENGTH, H3_ST_DATA, H3_ST_HEADERS, H3_ST_IGN_FRAME
 H3_RESPONSE, H3_PENDING, H3_SAW_DATA, H3_SAW_END = 0x1, 0x2, 0x4, 0x8
 QH_ERR_MALFORMED_HTTP_MESSAGING = -107
 QH_ERR_H3_FRAME_UNEXPECTED = -601
+# include/qhuff.h qh_h3_item, qh_h3_tx, QH_H3W_*
+H3_ITEM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("span_flags", "<u4"), ("type", "<u8"), ("src", "<u4"),
+                          ("flags", "<u4")])
+H3_TX_DTYPE = np.dtype([("off", "<u8"), ("flags", "<u4"), ("rsv", "<u4")])
+assert H3_ITEM_DTYPE.itemsize == 32 and H3_TX_DTYPE.itemsize == 16
+H3_FRAME_DATA, H3_FRAME_HEADERS = 0, 1
+H3W_END = 0x1    # an item's flag: the stream ends after it
+H3W_ENDED = 0x1  # a record's flag
+QH_ERR_INVALID_STATE = -102
 QH_ERR_H3_FRAME_ERROR = -602
 QH_ERR_H3_GENERAL_PROTOCOL_ERROR = -606
 EMIT_BLOCKED = 1
@@ -287,6 +296,13 @@ def _load():
         _pair(lib, "h3_read", [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, pu64, vp, vp,
                                u64, pu64])
         _pair(lib, "h3_settle", [vp, vp, vp, sz, vp])
+        lib.qh_h3_tx_init.argtypes = [vp, sz]
+        lib.qh_h3_tx_init.restype = None
+        lib.qh_h3_write_hd.argtypes = [vp, u64, u64]
+        lib.qh_h3_write_hd.restype = vp
+        lib.qh_h3_write_hd_len.argtypes = [u64, u64]
+        lib.qh_h3_write_hd_len.restype = sz
+        _pair(lib, "h3_write", [vp, vp, vp, vp, sz, vp, vp, u64, pu64, vp, vp, vp])
         _L = lib
     return _L
 
@@ -1086,6 +1102,99 @@ def h3_settle_dev(codec: HuffmanBatchCodec, rs, hs, sec_status, status):
                  codec=codec)
     be.check(rv, "h3_settle")
     return status
+
+
+# ---- response and request streams as they leave (qh_qpack_h3_write / qh_h3_write_batch) ----
+
+def h3_tx(n: int):
+    """n fresh H3_TX_DTYPE records (qh_h3_tx_init): offset 0, not ended."""
+    tx = np.zeros(n, dtype=H3_TX_DTYPE)
+    if n:
+        _load().qh_h3_tx_init(_vp(tx), n)
+    return tx
+
+
+def h3_write_hd(type_: int, length: int) -> bytes:
+    """The frame header nghttp3_frame_write_hd writes (qh_h3_write_hd; its
+    length is qh_h3_write_hd_len)."""
+    lib = _load()
+    buf = np.zeros(16, np.uint8)
+    n = lib.qh_h3_write_hd_len(type_, length)
+    end = lib.qh_h3_write_hd(_vp(buf), type_, length)
+    assert end - buf.ctypes.data == n
+    return buf[:n].tobytes()
+
+
+# The per-stream outputs of a write: name -> bytes per stream.
+_H3W_OUT = (("out", 16), ("fin", 1), ("status", 4))
+
+
+def h3_write_raw(be, hsrc, dsrc, items, item_start, nstreams, tx, dst, dst_cap, o, codec=None):
+    """The call over byte arrays of backend `be` -> (rv, dst_need).  `o`: the
+    outputs of _H3W_OUT; dst may be None (with dst_cap 0: the sizing call)."""
+    need = ctypes.c_uint64(0)
+    rv = be.call(_load(), "h3_write", be.ptr(hsrc), be.ptr(dsrc), be.ptr(items), be.ptr(item_start), nstreams,
+                 be.ptr(tx), be.ptr(dst), dst_cap, ctypes.byref(need), be.ptr(o["out"]), be.ptr(o["fin"]),
+                 be.ptr(o["status"]), codec=codec)
+    return rv, int(need.value)
+
+
+def _h3_write(be, hsrc, dsrc, items, item_start, n, tx, bufs, codec=None):
+    b = bufs or {}
+    if b.get("n", -1) < n:
+        b = {"n": n, "dst_cap": b.get("dst_cap", 0), "dst": b.get("dst")}
+        for name, unit in _H3W_OUT:
+            b[name] = be.empty(max(n, 1) * unit)
+    if b["dst"] is None:
+        b["dst_cap"] = cap_for(be.size(hsrc) + be.size(dsrc) + 4 * n, 4096)
+        b["dst"] = be.empty(b["dst_cap"])
+
+    def attempt():
+        rv, need = h3_write_raw(be, hsrc, dsrc, items, item_start, n, tx, b["dst"], b["dst_cap"], b, codec=codec)
+        return rv, need
+
+    def more(need):
+        b["dst_cap"] = cap_for(need, 4096)
+        b["dst"] = be.empty(b["dst_cap"])
+
+    _, b["dst_need"] = be.retry("h3_write", attempt, more)
+    return b
+
+
+def h3_write(hsrc, dsrc, items, item_start, tx):
+    """Host arrays: the HTTP/3 frames of many streams written as
+    nghttp3_stream_write_header_block and nghttp3_stream_write_data write them.
+    items: H3_ITEM_DTYPE records (off, len into hsrc when src is 0, the section
+    writer's dst, or into dsrc when src is 1; type; flags H3W_END); item_start
+    (uint32, one entry more than streams); tx: H3_TX_DTYPE records
+    (``h3_tx``), updated in place.  -> dict: dst (the bytes written), out
+    (SPAN_IN_DTYPE, a stream's bytes of this call), fin (uint8), status (int32: 0
+    or QH_ERR_INVALID_STATE): out, fin, stream ids and views are the chunks of
+    ``h3_read`` on the peer.  Runs on the host (qh_qpack_h3_write)."""
+    hsrc, dsrc = _u8(hsrc), _u8(dsrc)
+    items = np.ascontiguousarray(items, H3_ITEM_DTYPE)
+    start = np.ascontiguousarray(item_start, np.uint32)
+    n = start.size - 1
+    if n < 0 or tx.dtype != H3_TX_DTYPE or tx.size != n or not tx.flags.c_contiguous or \
+            (n and int(start.max()) > items.size):
+        raise ValueError("h3_write: item_start has one entry more than streams, inside items; one record per stream")
+    be = Backend()
+    b = _h3_write(be, hsrc, dsrc, items.view(np.uint8), start.view(np.uint8), n, tx.view(np.uint8), None)
+    return {"dst": b["dst"][:b["dst_need"]], "out": b["out"].view(SPAN_IN_DTYPE)[:n], "fin": b["fin"][:n],
+            "status": b["status"].view(np.int32)[:n], "tx": tx}
+
+
+def h3_write_dev(codec: HuffmanBatchCodec, hsrc, dsrc, items, item_start, tx, bufs=None):
+    """Device-resident form (qh_h3_write_batch): uint8 tensors holding the same
+    records (hsrc, dsrc; items [nitems * 32]; item_start [(n + 1) * 4]; tx
+    [n * 16] updated in place).  -> dict of uint8 tensors dst (dst_need bytes
+    written), out [n * 16], fin [n], status [n * 4], plus the host integer
+    dst_need; `bufs` (a previous result) reuses its allocations.  out and fin
+    go as they are into ``h3_read_dev`` with dst as its src.  One host wait,
+    for the byte total."""
+    n = int(item_start.shape[0]) // 4 - 1
+    return _h3_write(Backend(tx.device if n else item_start.device), hsrc, dsrc, items, item_start, n, tx, bufs,
+                     codec=codec)
 
 
 class DynamicTable:

@@ -192,10 +192,13 @@ class HuffmanBatchCodec:
         (header blocks per slice of the pipelined host-memory field-section
         decode; 0 = chosen by the library) and 'emit_long_min' (field
         emission copies a string of at least that many bytes with a wave; 0 =
-        chosen by the library)."""
+        chosen by the library) and 'h3w_long_min' / 'h3w_piece' (frame writing
+        copies a payload of at least long_min bytes with waves, piece bytes
+        each; 0 = chosen by the library)."""
         k = {"long_min": _lib.QH_OPT_LONG_MIN, "lens_lane_pass": _lib.QH_OPT_LENS_LANE_PASS,
              "sections_slice_blocks": _lib.QH_OPT_SECTIONS_SLICE_BLOCKS,
-             "emit_long_min": _lib.QH_OPT_EMIT_LONG_MIN}[option]
+             "emit_long_min": _lib.QH_OPT_EMIT_LONG_MIN, "h3w_long_min": _lib.QH_OPT_H3W_LONG_MIN,
+             "h3w_piece": _lib.QH_OPT_H3W_PIECE}[option]
         _lib.check(self._lib.qh_ctx_set_option(self._ctx, k, int(value)), "qh_ctx_set_option")
 
     def sync(self):
