@@ -2204,8 +2204,7 @@ QH_EXPORT int qh_http_check_batch(
  * recv_data); -107 for a body is reported at settle, not at the byte where it
  * occurs; begin_headers / end_headers with fin have no output; the caller's
  * QUIC stream buffer holds the tail after QH_H3_WAIT (consumed says where it
- * begins).  Not built: the control stream and SETTINGS, `priority`,
- * QH_WHERE_HOST staging, a tail log as qh_ustream_* keeps.  (Frame writing is
+ * begins).  Not built: `priority`, QH_WHERE_HOST staging, a tail log as qh_ustream_* keeps.  (Frame writing is
  * the next section.) */
 #define QH_ERR_MALFORMED_HTTP_MESSAGING (-107)   /* nghttp3.h:210 */
 #define QH_ERR_H3_FRAME_UNEXPECTED (-601)        /* nghttp3.h:273 */
@@ -2353,10 +2352,10 @@ QH_EXPORT int qh_h3_settle_batch(qh_ctx *ctx, qh_h3_stream *rs, const qh_http_st
  * read_data call, stream.c:613-634); flow control, add_write_offset and the
  * retention of unacknowledged bytes stay with the caller's QUIC stream
  * buffer, of which dst is the input, as the reader leaves the unread tail
- * there.  Not built: the control stream and the SETTINGS / GOAWAY /
- * PRIORITY_UPDATE payloads (a caller sends them as an item with its own
- * payload), the unidirectional streams' type byte, a vector-list output
- * without the copy, QH_WHERE_HOST staging. */
+ * there.  Not built: the GOAWAY / PRIORITY_UPDATE payloads (a caller sends
+ * them as an item with its own payload; the control stream's opening bytes
+ * are qh_h3_write_settings), a vector-list output without the copy,
+ * QH_WHERE_HOST staging. */
 #define QH_ERR_INVALID_STATE (-102) /* nghttp3.h:175 */
 
 #define QH_H3W_END 0x1u   /* qh_h3_item.flags: the stream ends after this item */
@@ -2388,6 +2387,272 @@ QH_EXPORT int qh_h3_write_batch(
     qh_ctx *ctx, const uint8_t *hsrc, const uint8_t *dsrc, const qh_h3_item *items,
     const uint32_t *item_start, size_t nstreams, qh_h3_tx *tx, uint8_t *dst, uint64_t dst_cap,
     uint64_t *dst_need, qh_span_in *out, uint8_t *fin, int32_t *status, int where);
+
+/* ---- Unidirectional streams as they arrive: types, control frames, SETTINGS --
+ *
+ * What nghttp3_conn_read_uni does with the bytes of the peer's unidirectional
+ * streams (lib/nghttp3_conn.c:631-721): the stream type varint
+ * (conn_read_type, :570-625), which stream may open and which may not open
+ * twice, the control stream's frames (nghttp3_conn_read_control, :732-1340:
+ * SETTINGS first and once, GOAWAY, MAX_PUSH_ID, PRIORITY_UPDATE, the refused
+ * and the ignored types) and the peer's SETTINGS put to this side's QPACK
+ * encoder (nghttp3_conn_on_settings_entry_received, :1960-2052), for the
+ * chunks of many connections in one call.  The bytes behind the type of the
+ * QPACK encoder and decoder streams come out as spans that go as they are
+ * into qh_ustream_join_batch.  Each call has a host form over host pointers
+ * and a device form over pointers in HBM (where must be QH_WHERE_DEVICE;
+ * counts are host scalars); both compile the same rules (csrc/qh_h3u_core.h)
+ * and agree byte for byte on every output and every record.
+ *
+ * qh_h3_uni is the per-stream record, caller-owned (32 B):
+ *   left    rstate->left: payload bytes of the frame in progress still to come;
+ *   acc     rvint->acc: the value of the bytes of a cut varint read so far;
+ *   aux     the SETTINGS identifier whose value is still to come, or the
+ *           PRIORITY_UPDATE element id;
+ *   state   QH_H3U_ST_* (NGHTTP3_CTRL_STREAM_STATE_*, lib/nghttp3_stream.h:62-75);
+ *   vleft   rvint->left: the bytes of the cut varint still missing (0 to 7);
+ *   type    QH_H3U_T_NONE (not identified yet), _CONTROL, _QENC, _QDEC, _UNKNOWN;
+ *   ftype   QH_H3U_F_*: the class of the frame in progress;
+ *   flags   zero;
+ *   err     the first error, latched (0: none).
+ * qh_h3_conn is the per-connection record, caller-owned (64 B): the remote
+ * settings (max_field_section_size, 2^62 - 1 until the peer says otherwise,
+ * conn.c:357; qpack_max_dtable_capacity; qpack_blocked_streams;
+ * QH_H3C_CONNECT_PROTOCOL and QH_H3C_H3_DATAGRAM in flags), goaway_id (2^62
+ * until a GOAWAY arrives, conn.c:361), max_pushes, max_client_streams (the
+ * caller's: the bound of the PRIORITY_UPDATE id check, conn.c:2061-2064),
+ * pri_buf / pri_len (rx.pri_fieldbuf, lib/nghttp3_conn.h:137: a Priority Field
+ * Value that arrives in parts), flags (the reference's NGHTTP3_CONN_FLAG_*
+ * values for SETTINGS_RECVED, CONTROL_OPENED, QPACK_ENCODER_OPENED,
+ * QPACK_DECODER_OPENED and GOAWAY_RECVED; QH_H3C_SERVER; the two setting
+ * booleans; QH_H3C_CAP_NEW and QH_H3C_BLOCKED_NEW, see apply) and err, the
+ * connection's first error, latched: every error here is a connection error
+ * in the reference.
+ * qh_h3_event is what the callbacks would have delivered (32 B): kind
+ * (QH_H3_EV_SETTINGS: recv_settings, the values are in the connection record;
+ * QH_H3_EV_GOAWAY: shutdown, id the GOAWAY id; QH_H3_EV_PRIORITY_UPDATE: id
+ * the element id, value[0, len) the Priority Field Value, len 0 the empty
+ * update of conn.c:1116-1127; QH_H3_EV_STOP_SENDING: an unknown stream type
+ * identified without fin, conn.c:676-682, id the stream id), chunk (the chunk
+ * that produced it), id, value[8] (zero behind len), len.
+ *
+ * read.  Chunk c is src[chunks[c].off, + len), the new bytes of stream
+ * chunk_sid[c], chunk_fin[c] != 0 when they end it, with its record us[c] (the
+ * caller gathers and scatters).  Connection k owns cs[k] and the chunks
+ * [conn_start[k], conn_start[k + 1]) in arrival order (conn_start has nconns +
+ * 1 entries, begins at 0, does not decrease and ends at nchunks: the
+ * convention of qh_encode_conns_batch).  A stream appears at most once per
+ * call.  Per chunk: status[c] (QH_H3U_OPEN, QH_H3U_GONE: the stream was closed
+ * before any byte of its type and the reference deletes it, conn.c:641-657; or
+ * the error) and consumed[c].  Per connection: nglitch[k] (optional), the
+ * times the reference would have drained its rate limiter (a zero-length
+ * closed stream, an unknown stream type, PRIORITY_UPDATE, ORIGIN, an unknown
+ * frame, a GOAWAY or MAX_PUSH_ID that repeats the current value); the limiter
+ * is timed, so its verdict (-610) is the caller's.  Compacted in chunk order:
+ * enc_pieces[j] / enc_conn[j], *nenc: the bytes behind the type of QPACK
+ * encoder streams as spans into src with their connection index (pieces / tsel
+ * / nsel of qh_ustream_join_batch on the table side); dec_pieces / dec_conn,
+ * *ndec: the same for the decoder stream (qh_enc_read_decoder_batch's side).
+ * Room for nchunks entries in each always suffices and is required.  events,
+ * *nevents: when event_cap is short the call returns QH_ERR_NOMEM with the
+ * exact need in *nevents and nothing else written.  Rules per connection, its
+ * chunks in order, in the reference's order:
+ *   1. an error is latched in the connection (or the stream) record: status
+ *      is that error, consumed 0, nothing changes;
+ *   2. while the record's type is QH_H3U_T_NONE the stream id must be a
+ *      unidirectional stream of the peer (low two bits 2 for a server reading,
+ *      3 for a client), else -609 (conn.c:513-545); an empty chunk without fin
+ *      changes nothing;
+ *   3. the type (conn.c:640-688).  An empty chunk with fin is -606 when a
+ *      varint is cut, else QH_H3U_GONE and one glitch.  The varint is
+ *      continued from the record; one cut by fin is -606.  0 is the control
+ *      stream, 2 the QPACK encoder stream, 3 the QPACK decoder stream: each
+ *      sets its flag or is -609 when the flag is set already; 1 (push) is
+ *      -609; any other type is unknown: one glitch, a STOP_SENDING event
+ *      unless fin, and this and every later chunk of the stream is consumed
+ *      whole.  With nothing left behind the type the chunk ends here, before
+ *      the fin test (conn.c:685-687);
+ *   4. an identified stream with bytes or fin: fin on a control, encoder or
+ *      decoder stream is -605; encoder and decoder streams yield their piece
+ *      (none of their bytes is read); the control stream is walked as
+ *      read_control walks it: cut varints continued from the record; a first
+ *      frame other than SETTINGS is -603, a second SETTINGS -601; inside
+ *      SETTINGS a varint that crosses the frame's end and an identifier with
+ *      no value are -602, and every entry is judged as it completes (a second
+ *      nonzero table capacity or blocked-streams value -608, the four HTTP/2
+ *      identifiers -608, ENABLE_CONNECT_PROTOCOL ignored by a server and 0 or
+ *      1 on a client, never back to 0, H3_DATAGRAM 0 or 1, unknown identifiers
+ *      ignored); an empty SETTINGS frame is delivered too; GOAWAY of length 0
+ *      is -602, on a client an id that is no client bidirectional stream -607,
+ *      an increase -607, a repeat one glitch; MAX_PUSH_ID on a client -601,
+ *      length 0 -602, a decrease -602, a repeat one glitch (after the varint
+ *      of either the stream is back in the type state whatever the length
+ *      said, conn.c:1064, :1095); PRIORITY_UPDATE (0xF0700) on a client -601,
+ *      length 0 -602, one glitch, the element id checked when the frame ends
+ *      (-607), a value of more than 8 bytes turns the rest of the frame into
+ *      an ignored one; 0xF0701 is -607; ORIGIN (taken as the reference takes
+ *      it with no origin callbacks set) and every unknown type are one glitch
+ *      and skipped; the eight types of conn.c:875-883 are -601;
+ *   5. a chunk that ends in an error leaves no trace but the error: no piece,
+ *      no events and no glitches of that chunk, both records as on entry to
+ *      the chunk with the error latched in each, consumed 0.
+ * Returns 0; QH_ERR_INVALID_ARGUMENT with nothing written for a NULL argument
+ * that is needed, a bad conn_start, nchunks of 2^27 or more, or a stream or
+ * connection record that no call here leaves; QH_ERR_NOMEM as above.  No byte
+ * outside a chunk is read: src needs no padding.  Device: a lane per
+ * connection walks its chunks on copies of the records and counts
+ * (qh_k_h3u_count), one scan over three segments, one host wait (the three
+ * totals and the list's errors), then a lane per connection replays the walk
+ * and writes (qh_k_h3u_write).  The lane is per connection because which
+ * stream may open and whether SETTINGS has been seen is connection state that
+ * the chunks of one call change in order.
+ *
+ * apply.  For each listed connection (csel[j] < nconns; NULL: all nconns,
+ * whatever nsel says) whose record has QH_H3C_CAP_NEW: what
+ * qh_enc_state_set_capacity(&enc[k], &acct[k], qpack_max_dtable_capacity)
+ * does; with QH_H3C_BLOCKED_NEW: enc[k].max_blocked = min(100,
+ * qpack_blocked_streams) (conn.c:2007-2008).  Both bits are cleared.  The read
+ * sets them when the nonzero entry is received, which is when the reference
+ * calls its encoder.  A csel entry of nconns or more, or a connection named
+ * twice: host QH_ERR_INVALID_ARGUMENT with nothing written, device passed over
+ * (as qh_ustream_sections_batch does).  The device form is a lane per listed
+ * connection, asynchronous on the context stream, with no host wait.
+ *
+ * qh_h3_write_settings writes the opening bytes of this side's control stream
+ * as nghttp3_stream_write_stream_type and nghttp3_stream_write_settings do
+ * (lib/nghttp3_stream.c:309-390): the type 0x00, then a SETTINGS frame with
+ * the identifiers 0x06, 0x01, 0x07 in that order, always, then 0x33 = 1 and
+ * 0x08 = 1 when set, every varint in its shortest form.  Values below 2^62;
+ * dst NULL: only the length (at most 64) is returned.  Host only.  GOAWAY and
+ * PRIORITY_UPDATE need no call: qh_h3_write_batch writes any frame type around
+ * a payload the caller built.
+ *
+ * Departures: the Priority Field Value is handed out, not parsed (the
+ * reference's parser for it is not part of this library, and `priority` is
+ * left unparsed for the same reason), so the -606 of conn.c:1182-1186 is the
+ * caller's; finding or creating the prioritised stream (conn.c:2066-2106)
+ * needs the caller's stream map and stays there; ORIGIN is not delivered; the
+ * rate limiter's verdict is the caller's; a stream closed before any byte is
+ * counted as a glitch whether or not an empty chunk came before (the record
+ * does not tell).  Not built: QH_WHERE_HOST staging. */
+#define QH_ERR_H3_MISSING_SETTINGS (-603)        /* nghttp3.h:287 */
+#define QH_ERR_H3_CLOSED_CRITICAL_STREAM (-605)  /* nghttp3.h:300 */
+#define QH_ERR_H3_ID_ERROR (-607)                /* nghttp3.h:314 */
+#define QH_ERR_H3_SETTINGS_ERROR (-608)          /* nghttp3.h:321 */
+#define QH_ERR_H3_STREAM_CREATION_ERROR (-609)   /* nghttp3.h:329 */
+
+#define QH_H3U_OPEN 0 /* status: the stream goes on              */
+#define QH_H3U_GONE 1 /* status: closed before a byte of its type */
+
+#define QH_H3U_ST_FRAME_TYPE 0
+#define QH_H3U_ST_FRAME_LENGTH 1
+#define QH_H3U_ST_SETTINGS 2
+#define QH_H3U_ST_GOAWAY 3
+#define QH_H3U_ST_MAX_PUSH_ID 4
+#define QH_H3U_ST_IGN_FRAME 5
+#define QH_H3U_ST_SETTINGS_ID 6
+#define QH_H3U_ST_SETTINGS_VALUE 7
+#define QH_H3U_ST_PRIORITY_UPDATE_PRI_ELEM_ID 8
+#define QH_H3U_ST_PRIORITY_UPDATE 9
+
+#define QH_H3U_T_NONE 0
+#define QH_H3U_T_CONTROL 1
+#define QH_H3U_T_QENC 2
+#define QH_H3U_T_QDEC 3
+#define QH_H3U_T_UNKNOWN 4
+
+#define QH_H3U_F_NONE 0
+#define QH_H3U_F_SETTINGS 1             /* 0x04 */
+#define QH_H3U_F_GOAWAY 2               /* 0x07 */
+#define QH_H3U_F_MAX_PUSH_ID 3          /* 0x0d */
+#define QH_H3U_F_PRIORITY_UPDATE 4      /* 0xf0700 */
+#define QH_H3U_F_PRIORITY_UPDATE_PUSH 5 /* 0xf0701 */
+#define QH_H3U_F_ORIGIN 6               /* 0x0c */
+#define QH_H3U_F_REFUSED 7              /* the eight types of conn.c:875-883 */
+#define QH_H3U_F_UNKNOWN 8
+
+#define QH_H3C_SETTINGS_RECVED 0x0001u /* NGHTTP3_CONN_FLAG_*, lib/nghttp3_conn.h:54-69 */
+#define QH_H3C_CONTROL_OPENED 0x0002u
+#define QH_H3C_QENC_OPENED 0x0004u
+#define QH_H3C_QDEC_OPENED 0x0008u
+#define QH_H3C_GOAWAY_RECVED 0x0020u
+#define QH_H3C_SERVER 0x0100u
+#define QH_H3C_CONNECT_PROTOCOL 0x0200u /* remote enable_connect_protocol */
+#define QH_H3C_H3_DATAGRAM 0x0400u      /* remote h3_datagram             */
+#define QH_H3C_CAP_NEW 0x0800u          /* a table capacity to apply      */
+#define QH_H3C_BLOCKED_NEW 0x1000u      /* a blocked-streams value to apply */
+
+#define QH_H3_EV_SETTINGS 1
+#define QH_H3_EV_GOAWAY 2
+#define QH_H3_EV_PRIORITY_UPDATE 3
+#define QH_H3_EV_STOP_SENDING 4
+
+typedef struct qh_h3_uni { /* 32 B */
+  uint64_t left;
+  uint64_t acc;
+  uint64_t aux;
+  uint8_t state, vleft, type, ftype;
+  uint16_t flags;
+  int16_t err;
+} qh_h3_uni;
+
+typedef struct qh_h3_conn { /* 64 B */
+  uint64_t max_field_section_size;
+  uint64_t qpack_max_dtable_capacity;
+  uint64_t qpack_blocked_streams;
+  uint64_t goaway_id;
+  uint64_t max_pushes;
+  uint64_t max_client_streams;
+  uint8_t pri_buf[8];
+  uint8_t pri_len, rsv;
+  uint16_t flags;
+  int16_t err;
+  uint16_t rsv2;
+} qh_h3_conn;
+
+typedef struct qh_h3_event { /* 32 B */
+  uint32_t kind;
+  uint32_t chunk;
+  uint64_t id;
+  uint8_t value[8];
+  uint32_t len;
+  uint32_t rsv;
+} qh_h3_event;
+
+/* Not identified, the type state, no error. */
+QH_EXPORT void qh_h3_uni_init(qh_h3_uni *us, size_t n);
+/* The reference's conn_new values; server != 0: QH_H3C_SERVER. */
+QH_EXPORT void qh_h3_conn_init(qh_h3_conn *cs, size_t n, int server, uint64_t max_client_streams);
+
+QH_EXPORT int qh_qpack_h3_uni_read(
+    const uint8_t *src, const qh_span_in *chunks, const uint8_t *chunk_fin,
+    const uint64_t *chunk_sid, size_t nchunks, const uint32_t *conn_start, size_t nconns,
+    qh_h3_uni *us, qh_h3_conn *cs, int32_t *status, uint32_t *consumed, uint32_t *nglitch,
+    qh_span_in *enc_pieces, uint32_t *enc_conn, uint64_t *nenc, qh_span_in *dec_pieces,
+    uint32_t *dec_conn, uint64_t *ndec, qh_h3_event *events, uint64_t event_cap,
+    uint64_t *nevents);
+QH_EXPORT int qh_h3_uni_read_batch(
+    qh_ctx *ctx, const uint8_t *src, const qh_span_in *chunks, const uint8_t *chunk_fin,
+    const uint64_t *chunk_sid, size_t nchunks, const uint32_t *conn_start, size_t nconns,
+    qh_h3_uni *us, qh_h3_conn *cs, int32_t *status, uint32_t *consumed, uint32_t *nglitch,
+    qh_span_in *enc_pieces, uint32_t *enc_conn, uint64_t *nenc, qh_span_in *dec_pieces,
+    uint32_t *dec_conn, uint64_t *ndec, qh_h3_event *events, uint64_t event_cap,
+    uint64_t *nevents, int where);
+
+QH_EXPORT int qh_qpack_h3_settings_apply(qh_h3_conn *cs, const uint32_t *csel, size_t nsel,
+                                         size_t nconns, qh_dtable_acct *acct, qh_enc_state *enc);
+QH_EXPORT int qh_h3_settings_apply_batch(qh_ctx *ctx, qh_h3_conn *cs, const uint32_t *csel,
+                                         size_t nsel, size_t nconns, qh_dtable_acct *acct,
+                                         qh_enc_state *enc, int where);
+
+typedef struct qh_h3_settings { /* what qh_h3_write_settings announces */
+  uint64_t max_field_section_size;
+  uint64_t qpack_max_dtable_capacity;
+  uint64_t qpack_blocked_streams;
+  uint8_t enable_connect_protocol, h3_datagram;
+  uint8_t rsv[6];
+} qh_h3_settings;
+QH_EXPORT size_t qh_h3_write_settings(uint8_t *dst, const qh_h3_settings *s);
 
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);

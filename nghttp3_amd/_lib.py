@@ -267,6 +267,14 @@ EXPORTED_FUNCTIONS = (
     "qh_h3_write_hd_len",
     "qh_qpack_h3_write",
     "qh_h3_write_batch",
+    # unidirectional streams as they arrive: types, control frames, SETTINGS (csrc/qh_h3u.c, csrc/qh_h3u.inc)
+    "qh_h3_uni_init",
+    "qh_h3_conn_init",
+    "qh_qpack_h3_uni_read",
+    "qh_h3_uni_read_batch",
+    "qh_qpack_h3_settings_apply",
+    "qh_h3_settings_apply_batch",
+    "qh_h3_write_settings",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

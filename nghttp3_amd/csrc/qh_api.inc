@@ -51,6 +51,7 @@ enum BufId {
   kBufH3,           // qh_h3_read_batch: per-chunk piece and span counts, the scan header
   kBufH3W,          // qh_h3_write_batch: per-stream byte and piece counts, the scan header
   kBufH3WWork,      // ... the long payloads' pieces
+  kBufH3U,          // qh_h3_uni_read_batch: per-connection piece and event counts, the scan header; the apply call's owner words
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap

@@ -98,4 +98,5 @@
 #include "qh_httpmsg.inc"       // decoded sections as HTTP messages: fields kept, removed or malformed, the state per stream
 #include "qh_h3.inc"            // request streams as they arrive: frames cut into HEADERS pieces and body spans; settle
 #include "qh_h3w.inc"           // response and request streams as they leave: frames placed, headers written, payloads copied
+#include "qh_h3u.inc"           // unidirectional streams as they arrive: types, control frames, SETTINGS; the peer's settings put to the encoders
 

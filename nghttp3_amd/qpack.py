@@ -119,6 +119,33 @@ H3W_ENDED = 0x1  # a record's flag
 QH_ERR_INVALID_STATE = -102
 QH_ERR_H3_FRAME_ERROR = -602
 QH_ERR_H3_GENERAL_PROTOCOL_ERROR = -606
+# include/qhuff.h qh_h3_uni, qh_h3_conn, qh_h3_event, QH_H3U_*, QH_H3C_*, QH_H3_EV_*
+H3_UNI_DTYPE = np.dtype([("left", "<u8"), ("acc", "<u8"), ("aux", "<u8"), ("state", "u1"), ("vleft", "u1"),
+                         ("type", "u1"), ("ftype", "u1"), ("flags", "<u2"), ("err", "<i2")])
+H3_CONN_DTYPE = np.dtype([("max_field_section_size", "<u8"), ("qpack_max_dtable_capacity", "<u8"),
+                          ("qpack_blocked_streams", "<u8"), ("goaway_id", "<u8"), ("max_pushes", "<u8"),
+                          ("max_client_streams", "<u8"), ("pri_buf", "u1", (8,)), ("pri_len", "u1"),
+                          ("rsv", "u1"), ("flags", "<u2"), ("err", "<i2"), ("rsv2", "<u2")])
+H3_EVENT_DTYPE = np.dtype([("kind", "<u4"), ("chunk", "<u4"), ("id", "<u8"), ("value", "u1", (8,)),
+                           ("len", "<u4"), ("rsv", "<u4")])
+H3_SETTINGS_DTYPE = np.dtype([("max_field_section_size", "<u8"), ("qpack_max_dtable_capacity", "<u8"),
+                              ("qpack_blocked_streams", "<u8"), ("enable_connect_protocol", "u1"),
+                              ("h3_datagram", "u1"), ("rsv", "u1", (6,))])
+assert H3_UNI_DTYPE.itemsize == 32 and H3_CONN_DTYPE.itemsize == 64 and H3_EVENT_DTYPE.itemsize == 32
+assert H3_SETTINGS_DTYPE.itemsize == 32
+H3U_OPEN, H3U_GONE = 0, 1
+(H3U_ST_FRAME_TYPE, H3U_ST_FRAME_LENGTH, H3U_ST_SETTINGS, H3U_ST_GOAWAY, H3U_ST_MAX_PUSH_ID, H3U_ST_IGN_FRAME,
+ H3U_ST_SETTINGS_ID, H3U_ST_SETTINGS_VALUE, H3U_ST_PRIORITY_UPDATE_PRI_ELEM_ID, H3U_ST_PRIORITY_UPDATE) = range(10)
+H3U_T_NONE, H3U_T_CONTROL, H3U_T_QENC, H3U_T_QDEC, H3U_T_UNKNOWN = range(5)
+H3C_SETTINGS_RECVED, H3C_CONTROL_OPENED, H3C_QENC_OPENED, H3C_QDEC_OPENED = 0x1, 0x2, 0x4, 0x8
+H3C_GOAWAY_RECVED, H3C_SERVER, H3C_CONNECT_PROTOCOL, H3C_H3_DATAGRAM = 0x20, 0x100, 0x200, 0x400
+H3C_CAP_NEW, H3C_BLOCKED_NEW = 0x800, 0x1000
+H3_EV_SETTINGS, H3_EV_GOAWAY, H3_EV_PRIORITY_UPDATE, H3_EV_STOP_SENDING = 1, 2, 3, 4
+QH_ERR_H3_MISSING_SETTINGS = -603
+QH_ERR_H3_CLOSED_CRITICAL_STREAM = -605
+QH_ERR_H3_ID_ERROR = -607
+QH_ERR_H3_SETTINGS_ERROR = -608
+QH_ERR_H3_STREAM_CREATION_ERROR = -609
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
 
@@ -303,6 +330,15 @@ def _load():
         lib.qh_h3_write_hd_len.argtypes = [u64, u64]
         lib.qh_h3_write_hd_len.restype = sz
         _pair(lib, "h3_write", [vp, vp, vp, vp, sz, vp, vp, u64, pu64, vp, vp, vp])
+        lib.qh_h3_uni_init.argtypes = [vp, sz]
+        lib.qh_h3_uni_init.restype = None
+        lib.qh_h3_conn_init.argtypes = [vp, sz, i32, u64]
+        lib.qh_h3_conn_init.restype = None
+        _pair(lib, "h3_uni_read", [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, pu64, vp, vp, pu64,
+                                   vp, u64, pu64])
+        _pair(lib, "h3_settings_apply", [vp, vp, sz, sz, vp, vp])
+        lib.qh_h3_write_settings.argtypes = [vp, vp]
+        lib.qh_h3_write_settings.restype = sz
         _L = lib
     return _L
 
@@ -1195,6 +1231,161 @@ def h3_write_dev(codec: HuffmanBatchCodec, hsrc, dsrc, items, item_start, tx, bu
     n = int(item_start.shape[0]) // 4 - 1
     return _h3_write(Backend(tx.device if n else item_start.device), hsrc, dsrc, items, item_start, n, tx, bufs,
                      codec=codec)
+
+
+# ---- unidirectional streams as they arrive (qh_qpack_h3_uni_read / qh_h3_uni_read_batch, _settings_apply) ----
+
+def h3_unis(n: int):
+    """n fresh H3_UNI_DTYPE records (qh_h3_uni_init): not identified yet."""
+    us = np.zeros(n, dtype=H3_UNI_DTYPE)
+    if n:
+        _load().qh_h3_uni_init(_vp(us), n)
+    return us
+
+
+def h3_conns(n: int, server: bool = True, max_client_streams: int = 0):
+    """n fresh H3_CONN_DTYPE records (qh_h3_conn_init): the remote settings,
+    goaway_id and flags as nghttp3_conn_new leaves them; `max_client_streams`
+    bounds the element id of a PRIORITY_UPDATE."""
+    cs = np.zeros(n, dtype=H3_CONN_DTYPE)
+    if n:
+        _load().qh_h3_conn_init(_vp(cs), n, 1 if server else 0, int(max_client_streams))
+    return cs
+
+
+# The outputs of a read: name -> bytes per chunk; nglitch is per connection.
+_H3U_OUT = (("status", 4), ("consumed", 4), ("enc_pieces", 16), ("enc_conn", 4), ("dec_pieces", 16),
+            ("dec_conn", 4))
+
+
+def h3_uni_read_raw(be, src, chunks, chunk_fin, chunk_sid, nchunks, conn_start, nconns, us, cs, o, event_cap,
+                    codec=None):
+    """The call over byte arrays of backend `be` -> (rv, nenc, ndec, nevents).
+    `o`: the outputs of _H3U_OUT plus nglitch and events (either may be None);
+    event_cap the room of events in records."""
+    ne, nd, nv = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rv = be.call(_load(), "h3_uni_read", be.ptr(src), be.ptr(chunks), be.ptr(chunk_fin), be.ptr(chunk_sid),
+                 nchunks, be.ptr(conn_start), nconns, be.ptr(us), be.ptr(cs), be.ptr(o["status"]),
+                 be.ptr(o["consumed"]), be.ptr(o.get("nglitch")), be.ptr(o["enc_pieces"]), be.ptr(o["enc_conn"]),
+                 ctypes.byref(ne), be.ptr(o["dec_pieces"]), be.ptr(o["dec_conn"]), ctypes.byref(nd),
+                 be.ptr(o.get("events")), event_cap, ctypes.byref(nv), codec=codec)
+    return rv, int(ne.value), int(nd.value), int(nv.value)
+
+
+def _h3_uni_read(be, src, chunks, chunk_fin, chunk_sid, n, conn_start, nconns, us, cs, bufs, codec=None):
+    b = bufs or {}
+    if b.get("n", -1) < n or b.get("nconns", -1) < nconns:
+        b = {"n": n, "nconns": nconns, "event_cap": b.get("event_cap", 0), "events": b.get("events")}
+        for name, unit in _H3U_OUT:
+            b[name] = be.empty(max(n, 1) * unit)
+        b["nglitch"] = be.empty(max(nconns, 1) * 4)
+    if b["events"] is None:
+        b["event_cap"] = cap_for(nconns, 64)
+        b["events"] = be.empty(b["event_cap"] * 32)
+
+    def attempt():
+        rv, ne, nd, nv = h3_uni_read_raw(be, src, chunks, chunk_fin, chunk_sid, n, conn_start, nconns, us, cs, b,
+                                         b["event_cap"], codec=codec)
+        return rv, (ne, nd, nv)
+
+    def more(needs):
+        b["event_cap"] = cap_for(needs[2], 64)
+        b["events"] = be.empty(b["event_cap"] * 32)
+
+    _, (b["nenc"], b["ndec"], b["nevents"]) = be.retry("h3_uni_read", attempt, more)
+    return b
+
+
+def h3_uni_read(src, chunks, chunk_fin, chunk_sid, conn_start, us, cs):
+    """Host arrays: the new bytes of the peers' unidirectional streams of many
+    connections, read as nghttp3_conn_read_uni reads them.  chunks:
+    SPAN_IN_DTYPE spans into src with chunk_fin (uint8) and chunk_sid (uint64);
+    conn_start (uint32, one entry more than connections): connection k owns
+    chunks [conn_start[k], conn_start[k + 1]) in arrival order; us:
+    H3_UNI_DTYPE records (``h3_unis``), one per chunk; cs: H3_CONN_DTYPE
+    records (``h3_conns``); both updated in place.  -> dict: status (H3U_OPEN,
+    H3U_GONE or the error) and consumed per chunk, nglitch per connection;
+    enc_pieces / enc_conn (the QPACK encoder streams' bytes behind the type,
+    for ``DynamicTableSet.feed_encoder(src, pieces, tsel)``), dec_pieces /
+    dec_conn (the same for ``EncoderSet.feed_decoder``), events
+    (H3_EVENT_DTYPE).  Runs on the host (qh_qpack_h3_uni_read)."""
+    src = _u8(src)
+    chunks = np.ascontiguousarray(chunks, SPAN_IN_DTYPE)
+    n = chunks.size
+    fin, sid = np.ascontiguousarray(chunk_fin, np.uint8), np.ascontiguousarray(chunk_sid, np.uint64)
+    start = np.ascontiguousarray(conn_start, np.uint32)
+    nconns = start.size - 1
+    if fin.size != n or sid.size != n or us.dtype != H3_UNI_DTYPE or us.size != n or nconns < 0 or \
+            cs.dtype != H3_CONN_DTYPE or cs.size != nconns or not us.flags.c_contiguous or \
+            not cs.flags.c_contiguous:
+        raise ValueError("h3_uni_read: one fin, sid and stream record per chunk, one record per connection")
+    be = Backend()
+    b = _h3_uni_read(be, src, chunks.view(np.uint8), fin, sid.view(np.uint8), n, start.view(np.uint8), nconns,
+                     us.view(np.uint8), cs.view(np.uint8), None)
+    ne, nd, nv = b["nenc"], b["ndec"], b["nevents"]
+    return {"status": b["status"].view(np.int32)[:n], "consumed": b["consumed"].view(np.uint32)[:n],
+            "nglitch": b["nglitch"].view(np.uint32)[:nconns], "nenc": ne, "ndec": nd, "nevents": nv,
+            "enc_pieces": b["enc_pieces"].view(SPAN_IN_DTYPE)[:ne], "enc_conn": b["enc_conn"].view(np.uint32)[:ne],
+            "dec_pieces": b["dec_pieces"].view(SPAN_IN_DTYPE)[:nd], "dec_conn": b["dec_conn"].view(np.uint32)[:nd],
+            "events": b["events"].view(H3_EVENT_DTYPE)[:nv], "us": us, "cs": cs}
+
+
+def h3_uni_read_dev(codec: HuffmanBatchCodec, src, chunks, chunk_fin, chunk_sid, conn_start, us, cs, bufs=None):
+    """Device-resident form (qh_h3_uni_read_batch): uint8 tensors holding the
+    same records (chunks [n * 16], chunk_fin [n], chunk_sid [n * 8], conn_start
+    [(nconns + 1) * 4], us [n * 32] and cs [nconns * 64] updated in place).  ->
+    dict of uint8 tensors named as h3_uni_read's arrays, with room for n chunks
+    (the first nenc / ndec / nevents entries are written), plus those three
+    host integers; `bufs` (a previous result) reuses its allocations.  One host
+    wait, for the three totals."""
+    n = int(chunk_fin.shape[0])
+    nconns = int(conn_start.shape[0]) // 4 - 1
+    return _h3_uni_read(Backend(conn_start.device), src, chunks, chunk_fin, chunk_sid, n, conn_start, nconns, us,
+                        cs, bufs, codec=codec)
+
+
+def h3_settings_apply(cs, acct, enc, csel=None):
+    """Host arrays: the peer's SETTINGS of the listed connections (csel uint32;
+    None: all) put to their encoders, in place (qh_qpack_h3_settings_apply):
+    cs H3_CONN_DTYPE, acct ACCT_DTYPE, enc ENC_STATE_DTYPE, one per
+    connection."""
+    n = cs.size
+    if cs.dtype != H3_CONN_DTYPE or acct.dtype != ACCT_DTYPE or enc.dtype != ENC_STATE_DTYPE or \
+            acct.size != n or enc.size != n:
+        raise ValueError("h3_settings_apply: one acct and enc record per connection record")
+    sel = _as(csel, np.uint32)
+    be = Backend()
+    rv = be.call(_load(), "h3_settings_apply", be.ptr(cs.view(np.uint8)), be.list_ptr(sel),
+                 0 if sel is None else sel.size, n, be.ptr(acct.view(np.uint8)), be.ptr(enc.view(np.uint8)))
+    be.check(rv, "h3_settings_apply")
+
+
+def h3_settings_apply_dev(codec: HuffmanBatchCodec, cs, acct, enc, csel=None):
+    """Device-resident form (qh_h3_settings_apply_batch): uint8 tensors cs
+    [n * 64], acct [n * 32], enc [n * 64] updated in place, csel int32 / uint32
+    indices or None.  Asynchronous on the context's stream: no host wait."""
+    n = int(cs.shape[0]) // H3_CONN_DTYPE.itemsize
+    be = Backend(cs.device)
+    rv = be.call(_load(), "h3_settings_apply", be.ptr(cs), be.list_ptr(csel),
+                 0 if csel is None else int(csel.shape[0]), n, be.ptr(acct), be.ptr(enc), codec=codec)
+    be.check(rv, "h3_settings_apply")
+
+
+def h3_write_settings(max_field_section_size: int = (1 << 62) - 1, qpack_max_dtable_capacity: int = 0,
+                      qpack_blocked_streams: int = 0, enable_connect_protocol: bool = False,
+                      h3_datagram: bool = False) -> bytes:
+    """The opening bytes of this side's control stream (qh_h3_write_settings):
+    the stream type and the SETTINGS frame as nghttp3_stream_write_stream_type
+    and nghttp3_stream_write_settings write them."""
+    s = np.zeros(1, H3_SETTINGS_DTYPE)
+    s["max_field_section_size"], s["qpack_max_dtable_capacity"] = max_field_section_size, qpack_max_dtable_capacity
+    s["qpack_blocked_streams"] = qpack_blocked_streams
+    s["enable_connect_protocol"], s["h3_datagram"] = bool(enable_connect_protocol), bool(h3_datagram)
+    lib = _load()
+    n = lib.qh_h3_write_settings(None, _vp(s))
+    buf = np.zeros(n, np.uint8)
+    assert lib.qh_h3_write_settings(_vp(buf), _vp(s)) == n
+    return buf.tobytes()
 
 
 class DynamicTable:
@@ -2366,6 +2557,21 @@ class EncoderSet:
         if self.ustreams is None:
             raise ValueError("the set was made without streams=True")
         return self.ustreams
+
+    def apply_settings(self, cs, csel=None, codec: HuffmanBatchCodec | None = None):
+        """The peer's SETTINGS as ``h3_uni_read`` left them in the connection
+        records `cs` (H3_CONN_DTYPE as bytes, of this set's backend) put to
+        the encoders of connections `csel` (None: all): the table capacity as
+        ``set_capacity`` would, max_blocked = min(100, the peer's value)
+        (qh_qpack_h3_settings_apply; with the device form's codec
+        qh_h3_settings_apply_batch, no host wait)."""
+        be = self._be
+        if isinstance(cs, np.ndarray) and cs.dtype == H3_CONN_DTYPE:
+            cs = cs.view(np.uint8)
+        rv = be.call(self._lib, "h3_settings_apply", be.ptr(cs), be.list_ptr(csel),
+                     0 if csel is None else be.size(csel), self.n, be.ptr(self.acct), be.ptr(self.enc),
+                     codec=codec)
+        be.check(rv, "h3_settings_apply")
 
     def feed_decoder(self, src, pieces, tsel=None):
         """Decoder-stream bytes as they arrive (host form): piece p is the new
