@@ -16,7 +16,7 @@ CFLAGS   := -std=c11 -O2 -fPIC -fvisibility=hidden -Wall -Wextra
 DRIVER  := $(LIBDIR)/qpack
 
 # The host C objects every build of the library links next to its device object.
-HOSTOBJS := $(LIBDIR)/qh_scalar.o $(LIBDIR)/qh_qpack.o $(LIBDIR)/qh_http.o $(LIBDIR)/qh_static.o $(LIBDIR)/qh_emit.o $(LIBDIR)/qh_dtset.o $(LIBDIR)/qh_encconn.o $(LIBDIR)/qh_ack.o $(LIBDIR)/qh_blocked.o $(LIBDIR)/qh_partial.o $(LIBDIR)/qh_ustream.o $(LIBDIR)/qh_httpmsg.o $(LIBDIR)/qh_h3.o $(LIBDIR)/qh_h3w.o $(LIBDIR)/qh_h3u.o
+HOSTOBJS := $(LIBDIR)/qh_scalar.o $(LIBDIR)/qh_qpack.o $(LIBDIR)/qh_http.o $(LIBDIR)/qh_static.o $(LIBDIR)/qh_emit.o $(LIBDIR)/qh_dtset.o $(LIBDIR)/qh_encconn.o $(LIBDIR)/qh_ack.o $(LIBDIR)/qh_blocked.o $(LIBDIR)/qh_partial.o $(LIBDIR)/qh_ustream.o $(LIBDIR)/qh_httpmsg.o $(LIBDIR)/qh_h3.o $(LIBDIR)/qh_h3w.o $(LIBDIR)/qh_h3u.o $(LIBDIR)/qh_h3d.o
 
 all: $(LIB) $(ARCHIVE) $(DRIVER) $(ORACLE)
 
@@ -27,7 +27,7 @@ $(LIBDIR)/qh_scalar.o: $(CSRC)/qh_scalar.c $(CSRC)/qh_tables.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_scratch.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_index_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_enc_core.h $(CSRC)/qh_enc_index_core.h $(CSRC)/qh_ack_core.h $(CSRC)/qh_blocked_core.h $(CSRC)/qh_partial_core.h $(CSRC)/qh_ustream_core.h $(CSRC)/qh_http_core.h $(CSRC)/qh_h3_core.h $(CSRC)/qh_h3w_core.h $(CSRC)/qh_h3u_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
+$(LIBDIR)/qh_device.o: $(CSRC)/qh_device.hip $(CSRC)/*.inc $(CSRC)/qh_common.h $(CSRC)/qh_scratch.h $(CSRC)/qh_tables.h $(CSRC)/qh_tokens.h $(CSRC)/qh_qpack_core.h $(CSRC)/qh_emit_core.h $(CSRC)/qh_plan_core.h $(CSRC)/qh_index_core.h $(CSRC)/qh_dtable_core.h $(CSRC)/qh_enc_core.h $(CSRC)/qh_enc_index_core.h $(CSRC)/qh_ack_core.h $(CSRC)/qh_blocked_core.h $(CSRC)/qh_partial_core.h $(CSRC)/qh_ustream_core.h $(CSRC)/qh_http_core.h $(CSRC)/qh_h3_core.h $(CSRC)/qh_h3w_core.h $(CSRC)/qh_h3u_core.h $(CSRC)/qh_h3d_core.h $(CSRC)/qh_frame_fast.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -80,6 +80,10 @@ $(LIBDIR)/qh_h3w.o: $(CSRC)/qh_h3w.c $(CSRC)/qh_h3w_core.h $(CSRC)/qh_qpack_core
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(LIBDIR)/qh_h3u.o: $(CSRC)/qh_h3u.c $(CSRC)/qh_h3u_core.h $(CSRC)/qh_qpack_core.h include/qhuff.h
+	@mkdir -p $(LIBDIR)
+	$(CC) $(CFLAGS) -c $< -o $@
+
+$(LIBDIR)/qh_h3d.o: $(CSRC)/qh_h3d.c $(CSRC)/qh_h3d_core.h $(CSRC)/qh_h3_core.h $(CSRC)/qh_qpack_core.h include/qhuff.h
 	@mkdir -p $(LIBDIR)
 	$(CC) $(CFLAGS) -c $< -o $@
 

@@ -2159,7 +2159,7 @@ QH_EXPORT int qh_http_check_batch(
  *      and end with no piece.  The eleven types of conn.c:1643-1653 are -601
  *      once their length is read; every other type is skipped and counted.
  *      fin at a frame boundary is MSG_END (on_remote_end_stream, status
- *      QH_H3_END), anywhere else -602; in QH_H3_ST_IGN_REST (set by the caller,
+ *      QH_H3_END), anywhere else -602; in QH_H3_ST_IGN_REST (set by qh_h3_dispatch_batch or the caller,
  *      conn.c:506) everything is consumed and fin ends nothing.
  *      The one departure: when a HEADERS frame that is not trailers ends, the
  *      record gains QH_H3_PENDING, because hs[c] does not know that section
@@ -2530,8 +2530,8 @@ QH_EXPORT int qh_h3_write_batch(
  * Departures: the Priority Field Value is handed out, not parsed (the
  * reference's parser for it is not part of this library, and `priority` is
  * left unparsed for the same reason), so the -606 of conn.c:1182-1186 is the
- * caller's; finding or creating the prioritised stream (conn.c:2066-2106)
- * needs the caller's stream map and stays there; ORIGIN is not delivered; the
+ * caller's; finding the prioritised stream (conn.c:2066) is qh_h3_find_batch's,
+ * creating it (:2074-2097) stays with the caller; ORIGIN is not delivered; the
  * rate limiter's verdict is the caller's; a stream closed before any byte is
  * counted as a glitch whether or not an empty chunk came before (the record
  * does not tell).  Not built: QH_WHERE_HOST staging. */
@@ -2653,6 +2653,274 @@ typedef struct qh_h3_settings { /* what qh_h3_write_settings announces */
   uint8_t rsv[6];
 } qh_h3_settings;
 QH_EXPORT size_t qh_h3_write_settings(uint8_t *dst, const qh_h3_settings *s);
+
+/* ---- Streams by id: a per-connection stream table, arrivals routed ----------
+ *
+ * The top of the reference's receive path, which the calls above leave to
+ * their caller: finding a stream by its id, creating it when the id is new,
+ * refusing ids that may not open (nghttp3_conn_read_stream2,
+ * lib/nghttp3_conn.c:468-568; nghttp3_conn_create_stream / _find_stream,
+ * :2135-2171; conn_bidi_idtr_open, :446-459, lib/nghttp3_idtr.c,
+ * lib/nghttp3_gaptr.c), closing it (nghttp3_conn_close_stream2 :2772-2790,
+ * conn_delete_stream :1342-1403), the GOAWAY id (nghttp3_conn_shutdown,
+ * _submit_shutdown_notice, :2619-2669) and the create half of
+ * nghttp3_conn_submit_request (:2538-2549), for many connections in one call.
+ * Each call has a host form over host pointers and a device form over pointers
+ * in HBM (where must be QH_WHERE_DEVICE; counts are host scalars); both
+ * compile the same rules (csrc/qh_h3d_core.h) and agree byte for byte on every
+ * output, every record and every slot, entry and gap.
+ *
+ * State, caller-owned, named by one qh_h3d_tab (a host structure of pointers):
+ *   sm[nconns]     qh_h3_smap, one per connection (64 B): its regions
+ *                  (slot_off, nslots, rec_off, rec_cap, gap_off, in units of
+ *                  slots, records and gaps), nlive, the free-list head
+ *                  (free_head: local record index + 1, 0: none) and high-water
+ *                  mark (hiwater) of its records, num_streams
+ *                  (remote.bidi.num_streams: a server's live client bidi
+ *                  streams), max_stream_id_bidi (-4 at first, conn.c:363),
+ *                  tx_goaway_id (2^62 at first, conn.c:362), ngaps, call (the
+ *                  number of the last dispatch call, which a routed entry
+ *                  remembers), flags (QH_H3M_*) and err, the first error of a
+ *                  dispatch, latched;
+ *   slots[nslots]  uint32_t: 0, or local record index + 1.  The home slot of
+ *                  stream id x in a region of n slots (n a power of two, at
+ *                  least 2 and at least 2 rec_cap) is
+ *                    ((uint32_t)((x * 0x9E3779B97F4A7C15) >> 32)) & (n - 1)
+ *                  (the product modulo 2^64); a stream lies at the first free
+ *                  slot from there on, cyclically, and a removal shifts the
+ *                  run behind it back (no tombstones), so the slot bytes
+ *                  depend only on the order of inserts and removals;
+ *   ents[nrecs]    qh_h3_sent, one per record (32 B): stream_id, the raw
+ *                  Priority Field Value (pri_buf, pri_len, as qh_h3_event
+ *                  carries it), next (the free-list link), call, flags
+ *                  (QH_H3S_LIVE and the reference's NGHTTP3_STREAM_FLAG_*
+ *                  values READ_EOF, SHUT_RD, SERVER_PRIORITY_SET,
+ *                  PRIORITY_UPDATE_RECVED).  A record's index, rec_off + local
+ *                  index, is stable for the stream's life, reused after a
+ *                  close (last freed, first reused; else the high-water mark)
+ *                  and indexes rs_pool, hs_pool, us_pool and any pool the
+ *                  caller keeps beside them (qh_h3_tx);
+ *   gaps[ngaps]    qh_h3_gap (begin, end), 33 per connection: the
+ *                  nghttp3_gaptr of remote.bidi.idtr as a sorted array over
+ *                  stream_id >> 2; none: nothing pushed yet.  A list longer
+ *                  than 32 after an open drops its first gap (conn.c:454-456);
+ *   rs_pool, hs_pool, us_pool  nrecs records each.
+ * qh_h3_smap_init lays the regions of n connections out back to back in
+ * connection order (nslots the least power of two >= max(2, 2 rec_cap[k])),
+ * sets the reference's initial values and returns the three totals (slots,
+ * records, gaps); slots, ents and gaps start zeroed.  rec_cap[k] is the
+ * caller's bound on live streams (the QUIC stream limits plus the peer's
+ * unidirectional streams).
+ *
+ * dispatch.  Connection k owns arrivals [conn_start[k], conn_start[k + 1]) in
+ * arrival order (the convention of qh_h3_uni_read_batch); arrival a is
+ * stream_id[a], chunks[a] (a span the call only hands on) and fin[a].  Per
+ * arrival route[a] and rec[a] (the record index, UINT32_MAX: none), in the
+ * reference's order:
+ *   1. an error latched in the connection: route is that error;
+ *   2. the stream is found and was routed earlier in this call: QH_H3D_AGAIN,
+ *      nothing changes (the calls below take a stream once per call; the
+ *      caller feeds the arrival in its next call);
+ *   3. not found.  Server: a client bidi id (low bits 0) opens its id in the
+ *      gap list (an in-use answer is ignored, conn.c:490-494), raises
+ *      max_stream_id_bidi and num_streams and is created; behind a queued
+ *      GOAWAY with tx_goaway_id <= id its record starts in QH_H3_ST_IGN_REST
+ *      and the route of this arrival is QH_H3D_BIDI_REJECTED (the caller
+ *      sends STOP_SENDING and RESET_STREAM with 0x010B: conn_reject_stream);
+ *      a client uni id (2) with no bytes and fin creates nothing
+ *      (QH_H3D_NONE), else is created; ids 1 and 3 are -609.  Client: a
+ *      server uni id (3) likewise; ids 0, 1, 2 are -609.  A table with
+ *      rec_cap live streams is -901 (nghttp3_map_insert's failure; the limit
+ *      is this library's, tested before anything changes).  A created stream's
+ *      pool records are as qh_h3_stream_init (REQ_INITIAL on a server,
+ *      RESP_INITIAL and QH_H3_RESPONSE on a client), qh_http_state_init and
+ *      qh_h3_uni_init leave them;
+ *   4. no bytes and no fin: QH_H3D_NONE (the stream stays created; a rejected
+ *      creation is QH_H3D_BIDI_REJECTED all the same), and it joins no list;
+ *   5. fin sets QH_H3S_READ_EOF; the route is QH_H3D_UNI for ids 2 and 3, else
+ *      QH_H3D_BIDI (or _REJECTED, rule 3), and the arrival joins its list.
+ * A negative route is latched in sm[k].err.  The lists, compacted in arrival
+ * order, with room for narrivals entries each (required, so there is no NOMEM
+ * case): b_chunks, b_fin, b_sid, b_view (= k), b_rec and the gathered rs_call,
+ * hs_call go as they are into qh_h3_read_batch; u_chunks, u_fin, u_sid, u_rec,
+ * u_conn_start (nconns + 1 entries) and us_call into qh_h3_uni_read_batch.
+ * Returns 0; QH_ERR_INVALID_ARGUMENT with nothing written for a needed NULL, a
+ * bad conn_start, or a connection record, region or slot that no call here
+ * leaves (nslots no power of two, a region outside its array, a slot naming a
+ * record that is not live, nlive not the number of used slots).  Regions of
+ * two connections must not overlap (qh_h3_smap_init's layout; not checked).
+ *
+ * commit scatters rs_call / hs_call by b_rec and us_call by u_rec back into
+ * the pools after the round's last call.  An index out of range or named twice
+ * is passed over and counted in *nskipped (host: the first in list order is
+ * kept; device: a word in HBM, one of the two is kept).
+ *
+ * open: the create half of submit_request for items [conn_start[k],
+ * conn_start[k + 1]) of a client connection k, in order: the connection's
+ * latched error; -101 on a server or for an id that is no client bidi id; -111
+ * after QH_H3C_GOAWAY_RECVED in cs[k]; -104 when found; -901 when full; else
+ * created with RESP_INITIAL records, rec[j] its index.
+ *
+ * find writes rec[j] for (conn[j], stream_id[j]), or UINT32_MAX.
+ * recs_move gathers (dir 0: call[j] = pool[idx[j]]) or scatters (dir 1) records
+ * of 16, 32 or 64 bytes; an idx of npool or more is passed over.  Both arrays
+ * 16-byte aligned on the device.
+ *
+ * close: close_stream2 for items grouped by conn_start, in order: -110 when
+ * not found; -605 for a uni stream whose us_pool type is QH_H3U_T_CONTROL,
+ * _QENC or _QDEC (QH_H3U_T_NONE and QH_H3U_T_UNKNOWN are the reference's
+ * NGHTTP3_STREAM_TYPE_UNKNOWN, which may close); else the entry leaves the
+ * table, its record goes to the free list, num_streams falls for a server's
+ * client bidi stream.  cancel_sid / cancel_view, *ncancel: every closed bidi
+ * stream, compacted in list order, for qh_dec_blocked_cancel_batch and
+ * qh_dec_partial_cancel_batch (the reference cancels a blocked stream only;
+ * both calls answer removed = 0 for a stream they do not hold).  drained[k]:
+ * QH_H3M_SHUTDOWN_COMMENCED and num_streams == 0 (conn.c:3023-3024; the
+ * control stream's queue is the caller's).
+ *
+ * shutdown, per listed connection (csel as in apply above): kind
+ * QH_H3D_NOTICE sets tx_goaway_id to 2^62 - 4 (client: 2^62 - 1) and
+ * QH_H3M_GOAWAY_QUEUED; QH_H3D_SHUTDOWN to min(2^62 - 4, max_stream_id_bidi +
+ * 4) (client: 0) and QH_H3M_SHUTDOWN_COMMENCED too.  goaway_id[j] is the id to
+ * frame with qh_h3_write_batch.  An id above the current one (the reference's
+ * assert) is status -101 with nothing changed.
+ *
+ * Departures: the reference's robin-hood nghttp3_map is not observable and is
+ * not copied; a stream twice in one call is answered QH_H3D_AGAIN; -901 comes
+ * from rec_cap.  Not built: priority_resolve (conn_on_priority_update_stream,
+ * conn.c:2054-2107, for the events of a uni read), QH_WHERE_HOST staging. */
+#define QH_ERR_STREAM_IN_USE (-104)    /* nghttp3.h:189 */
+#define QH_ERR_STREAM_NOT_FOUND (-110) /* nghttp3.h:231 */
+#define QH_ERR_CONN_CLOSING (-111)     /* nghttp3.h:238 */
+
+#define QH_H3D_NONE 0
+#define QH_H3D_BIDI 1
+#define QH_H3D_BIDI_REJECTED 2
+#define QH_H3D_UNI 3
+#define QH_H3D_AGAIN 4
+
+#define QH_H3D_NOTICE 0
+#define QH_H3D_SHUTDOWN 1
+
+#define QH_H3D_GAPS 33 /* gaps per connection */
+
+#define QH_H3M_SERVER 0x01u
+#define QH_H3M_GOAWAY_QUEUED 0x40u      /* NGHTTP3_CONN_FLAG_GOAWAY_QUEUED      */
+#define QH_H3M_SHUTDOWN_COMMENCED 0x80u /* NGHTTP3_CONN_FLAG_SHUTDOWN_COMMENCED */
+
+#define QH_H3S_LIVE 0x0001u
+#define QH_H3S_READ_EOF 0x0020u /* NGHTTP3_STREAM_FLAG_*, lib/nghttp3_stream.h:116-131 */
+#define QH_H3S_SHUT_RD 0x0200u
+#define QH_H3S_SERVER_PRIORITY_SET 0x0400u
+#define QH_H3S_PRIORITY_UPDATE_RECVED 0x0800u
+
+typedef struct qh_h3_smap { /* 64 B */
+  uint32_t slot_off, nslots;
+  uint32_t rec_off, rec_cap;
+  uint32_t gap_off, nlive;
+  uint32_t free_head, hiwater;
+  uint64_t num_streams;
+  int64_t max_stream_id_bidi;
+  uint64_t tx_goaway_id;
+  uint32_t call;
+  uint8_t ngaps, flags;
+  int16_t err;
+} qh_h3_smap;
+
+typedef struct qh_h3_sent { /* 32 B */
+  uint64_t stream_id;
+  uint8_t pri_buf[8];
+  uint32_t next;
+  uint32_t call;
+  uint16_t flags;
+  uint8_t pri_len, rsv;
+  uint32_t rsv2;
+} qh_h3_sent;
+
+typedef struct qh_h3_gap { /* 16 B */
+  uint64_t begin, end;
+} qh_h3_gap;
+
+typedef struct qh_h3d_tab {
+  qh_h3_smap *sm;
+  size_t nconns;
+  uint32_t *slots;
+  uint64_t nslots;
+  qh_h3_sent *ents;
+  uint64_t nrecs;
+  qh_h3_gap *gaps;
+  uint64_t ngaps;
+  qh_h3_stream *rs_pool;
+  qh_http_state *hs_pool;
+  qh_h3_uni *us_pool;
+} qh_h3d_tab;
+
+typedef struct qh_h3d_lists { /* dispatch's outputs, room for narrivals each */
+  qh_span_in *b_chunks;
+  uint8_t *b_fin;
+  uint64_t *b_sid;
+  uint32_t *b_view;
+  uint32_t *b_rec;
+  qh_h3_stream *rs_call;
+  qh_http_state *hs_call;
+  qh_span_in *u_chunks;
+  uint8_t *u_fin;
+  uint64_t *u_sid;
+  uint32_t *u_rec;
+  uint32_t *u_conn_start; /* nconns + 1 */
+  qh_h3_uni *us_call;
+} qh_h3d_lists;
+
+/* 0, or QH_ERR_INVALID_ARGUMENT when a total passes 2^32 - 1. */
+QH_EXPORT int qh_h3_smap_init(qh_h3_smap *sm, size_t n, int server, const uint32_t *rec_cap,
+                              uint64_t totals[3]);
+
+QH_EXPORT int qh_qpack_h3_dispatch(const qh_h3d_tab *t, const uint64_t *stream_id,
+                                   const qh_span_in *chunks, const uint8_t *fin, size_t narrivals,
+                                   const uint32_t *conn_start, int32_t *route, uint32_t *rec,
+                                   const qh_h3d_lists *out, uint64_t *nbidi, uint64_t *nuni);
+QH_EXPORT int qh_h3_dispatch_batch(qh_ctx *ctx, const qh_h3d_tab *t, const uint64_t *stream_id,
+                                   const qh_span_in *chunks, const uint8_t *fin, size_t narrivals,
+                                   const uint32_t *conn_start, int32_t *route, uint32_t *rec,
+                                   const qh_h3d_lists *out, uint64_t *nbidi, uint64_t *nuni, int where);
+
+QH_EXPORT int qh_qpack_h3_commit(const qh_h3d_tab *t, const uint32_t *b_rec,
+                                 const qh_h3_stream *rs_call, const qh_http_state *hs_call,
+                                 size_t nbidi, const uint32_t *u_rec, const qh_h3_uni *us_call,
+                                 size_t nuni, uint32_t *nskipped);
+QH_EXPORT int qh_h3_commit_batch(qh_ctx *ctx, const qh_h3d_tab *t, const uint32_t *b_rec,
+                                 const qh_h3_stream *rs_call, const qh_http_state *hs_call,
+                                 size_t nbidi, const uint32_t *u_rec, const qh_h3_uni *us_call,
+                                 size_t nuni, uint32_t *nskipped, int where);
+
+QH_EXPORT int qh_qpack_h3_open(const qh_h3d_tab *t, const qh_h3_conn *cs, const uint64_t *stream_id,
+                               size_t n, const uint32_t *conn_start, int32_t *status, uint32_t *rec);
+QH_EXPORT int qh_h3_open_batch(qh_ctx *ctx, const qh_h3d_tab *t, const qh_h3_conn *cs,
+                               const uint64_t *stream_id, size_t n, const uint32_t *conn_start,
+                               int32_t *status, uint32_t *rec, int where);
+
+QH_EXPORT int qh_qpack_h3_find(const qh_h3d_tab *t, const uint32_t *conn, const uint64_t *stream_id,
+                               size_t n, uint32_t *rec);
+QH_EXPORT int qh_h3_find_batch(qh_ctx *ctx, const qh_h3d_tab *t, const uint32_t *conn,
+                               const uint64_t *stream_id, size_t n, uint32_t *rec, int where);
+
+QH_EXPORT int qh_qpack_h3_recs_move(void *pool, uint64_t npool, void *call, const uint32_t *idx,
+                                    size_t n, uint32_t rec_bytes, int dir);
+QH_EXPORT int qh_h3_recs_move_batch(qh_ctx *ctx, void *pool, uint64_t npool, void *call,
+                                    const uint32_t *idx, size_t n, uint32_t rec_bytes, int dir,
+                                    int where);
+
+QH_EXPORT int qh_qpack_h3_close(const qh_h3d_tab *t, const uint64_t *stream_id, size_t n,
+                                const uint32_t *conn_start, int32_t *status, uint64_t *cancel_sid,
+                                uint32_t *cancel_view, uint64_t *ncancel, uint8_t *drained);
+QH_EXPORT int qh_h3_close_batch(qh_ctx *ctx, const qh_h3d_tab *t, const uint64_t *stream_id, size_t n,
+                                const uint32_t *conn_start, int32_t *status, uint64_t *cancel_sid,
+                                uint32_t *cancel_view, uint64_t *ncancel, uint8_t *drained, int where);
+
+QH_EXPORT int qh_qpack_h3_shutdown(const qh_h3d_tab *t, const uint32_t *csel, size_t nsel, int kind,
+                                   uint64_t *goaway_id, int32_t *status);
+QH_EXPORT int qh_h3_shutdown_batch(qh_ctx *ctx, const qh_h3d_tab *t, const uint32_t *csel, size_t nsel,
+                                   int kind, uint64_t *goaway_id, int32_t *status, int where);
 
 /* Library version string. */
 QH_EXPORT const char *qh_version(void);

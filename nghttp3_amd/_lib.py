@@ -275,6 +275,22 @@ EXPORTED_FUNCTIONS = (
     "qh_qpack_h3_settings_apply",
     "qh_h3_settings_apply_batch",
     "qh_h3_write_settings",
+    # streams by id: a stream table per connection, arrivals routed (csrc/qh_h3d.c, csrc/qh_h3d.inc)
+    "qh_h3_smap_init",
+    "qh_qpack_h3_dispatch",
+    "qh_h3_dispatch_batch",
+    "qh_qpack_h3_commit",
+    "qh_h3_commit_batch",
+    "qh_qpack_h3_open",
+    "qh_h3_open_batch",
+    "qh_qpack_h3_find",
+    "qh_h3_find_batch",
+    "qh_qpack_h3_recs_move",
+    "qh_h3_recs_move_batch",
+    "qh_qpack_h3_close",
+    "qh_h3_close_batch",
+    "qh_qpack_h3_shutdown",
+    "qh_h3_shutdown_batch",
     # field validation (csrc/qh_http.c, csrc/qh_validate.inc)
     "nghttp3_check_header_name",
     "nghttp3_check_header_value",

@@ -52,6 +52,7 @@ enum BufId {
   kBufH3W,          // qh_h3_write_batch: per-stream byte and piece counts, the scan header
   kBufH3WWork,      // ... the long payloads' pieces
   kBufH3U,          // qh_h3_uni_read_batch: per-connection piece and event counts, the scan header; the apply call's owner words
+  kBufH3D,          // the stream-table calls (qh_h3d.inc): per-connection counts, per-arrival ranks, owner words, the scan header
   kBufEw,         // fused encoder: window records and ticket counters, two halves
   kBufStage,      // host-mode staging: a call's pieces in and out (qhs::Staged)
   kBufStageDst,   // ... its dst, sized by dst_cap

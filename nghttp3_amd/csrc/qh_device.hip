@@ -26,6 +26,8 @@
 //   qh_k_http_*        decoded sections as HTTP messages: field verdicts, the kept records
 //   qh_k_h3_*          request streams as they arrive: HTTP/3 frames cut, body accounting, settle
 //   qh_k_h3w_*         streams as they leave: HTTP/3 frame headers written, payloads copied
+//   qh_k_h3u_*         unidirectional streams as they arrive: types, control frames, SETTINGS
+//   qh_k_h3d_*         streams by id: the per-connection stream table, arrivals routed, closes, GOAWAY ids
 //   qh_k_idx_*         the hashed index over the views' keys: count, build
 //   qh_k_scan, qh_k_synth_*   prefix sums, synthetic inputs (bench/tests)
 // The kernels from qh_k_encsec_* to qh_k_http_* work a 16-lane group per table,
@@ -99,4 +101,4 @@
 #include "qh_h3.inc"            // request streams as they arrive: frames cut into HEADERS pieces and body spans; settle
 #include "qh_h3w.inc"           // response and request streams as they leave: frames placed, headers written, payloads copied
 #include "qh_h3u.inc"           // unidirectional streams as they arrive: types, control frames, SETTINGS; the peer's settings put to the encoders
-
+#include "qh_h3d.inc"           // streams by id: a stream table per connection; arrivals routed to their records, opens, closes, GOAWAY ids

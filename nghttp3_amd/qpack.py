@@ -146,6 +146,25 @@ QH_ERR_H3_CLOSED_CRITICAL_STREAM = -605
 QH_ERR_H3_ID_ERROR = -607
 QH_ERR_H3_SETTINGS_ERROR = -608
 QH_ERR_H3_STREAM_CREATION_ERROR = -609
+# include/qhuff.h qh_h3_smap, qh_h3_sent, qh_h3_gap, QH_H3D_*, QH_H3M_*, QH_H3S_*
+H3_SMAP_DTYPE = np.dtype([("slot_off", "<u4"), ("nslots", "<u4"), ("rec_off", "<u4"), ("rec_cap", "<u4"),
+                          ("gap_off", "<u4"), ("nlive", "<u4"), ("free_head", "<u4"), ("hiwater", "<u4"),
+                          ("num_streams", "<u8"), ("max_stream_id_bidi", "<i8"), ("tx_goaway_id", "<u8"),
+                          ("call", "<u4"), ("ngaps", "u1"), ("flags", "u1"), ("err", "<i2")])
+H3_SENT_DTYPE = np.dtype([("stream_id", "<u8"), ("pri_buf", "u1", (8,)), ("next", "<u4"), ("call", "<u4"),
+                          ("flags", "<u2"), ("pri_len", "u1"), ("rsv", "u1"), ("rsv2", "<u4")])
+H3_GAP_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])
+assert H3_SMAP_DTYPE.itemsize == 64 and H3_SENT_DTYPE.itemsize == 32 and H3_GAP_DTYPE.itemsize == 16
+H3D_NONE, H3D_BIDI, H3D_BIDI_REJECTED, H3D_UNI, H3D_AGAIN = range(5)
+H3D_NOTICE, H3D_SHUTDOWN = 0, 1
+H3D_GAPS = 33
+H3D_NOREC = 0xFFFFFFFF
+H3D_HASH = 0x9E3779B97F4A7C15
+H3M_SERVER, H3M_GOAWAY_QUEUED, H3M_SHUTDOWN_COMMENCED = 0x01, 0x40, 0x80
+H3S_LIVE, H3S_READ_EOF, H3S_SHUT_RD, H3S_SERVER_PRIORITY_SET, H3S_PRIORITY_UPDATE_RECVED = 0x1, 0x20, 0x200, 0x400, 0x800
+QH_ERR_STREAM_IN_USE = -104
+QH_ERR_STREAM_NOT_FOUND = -110
+QH_ERR_CONN_CLOSING = -111
 EMIT_BLOCKED = 1
 EMIT_QIF = 0x1
 
@@ -167,6 +186,25 @@ class qh_plan_dyn(ctypes.Structure):
 class qh_plan_dyn_index(ctypes.Structure):
     """include/qhuff.h qh_plan_dyn_index (the index of a planning call)."""
     _fields_ = [("recs", ctypes.c_void_p), ("slots", ctypes.c_void_p), ("nslots", ctypes.c_uint64)]
+
+
+class qh_h3d_tab(ctypes.Structure):
+    """include/qhuff.h qh_h3d_tab (the state arrays of the stream-table calls)."""
+    _fields_ = [("sm", ctypes.c_void_p), ("nconns", ctypes.c_size_t), ("slots", ctypes.c_void_p),
+                ("nslots", ctypes.c_uint64), ("ents", ctypes.c_void_p), ("nrecs", ctypes.c_uint64),
+                ("gaps", ctypes.c_void_p), ("ngaps", ctypes.c_uint64), ("rs_pool", ctypes.c_void_p),
+                ("hs_pool", ctypes.c_void_p), ("us_pool", ctypes.c_void_p)]
+
+
+# dispatch's lists: name -> bytes per arrival, in qh_h3d_lists' order (u_conn_start: per connection + 1)
+H3D_LISTS = (("b_chunks", 16), ("b_fin", 1), ("b_sid", 8), ("b_view", 4), ("b_rec", 4), ("rs_call", 32),
+             ("hs_call", 16), ("u_chunks", 16), ("u_fin", 1), ("u_sid", 8), ("u_rec", 4), ("u_conn_start", 4),
+             ("us_call", 32))
+
+
+class qh_h3d_lists(ctypes.Structure):
+    """include/qhuff.h qh_h3d_lists (the outputs of a dispatch)."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in H3D_LISTS]
 
 
 SECTIONS_DTABLE0 = 0x1
@@ -339,6 +377,16 @@ def _load():
         _pair(lib, "h3_settings_apply", [vp, vp, sz, sz, vp, vp])
         lib.qh_h3_write_settings.argtypes = [vp, vp]
         lib.qh_h3_write_settings.restype = sz
+        lib.qh_h3_smap_init.argtypes = [vp, sz, i32, vp, vp]
+        lib.qh_h3_smap_init.restype = i32
+        tabp = c.POINTER(qh_h3d_tab)
+        _pair(lib, "h3_dispatch", [tabp, vp, vp, vp, sz, vp, vp, vp, c.POINTER(qh_h3d_lists), pu64, pu64])
+        _pair(lib, "h3_commit", [tabp, vp, vp, vp, sz, vp, vp, sz, vp])
+        _pair(lib, "h3_open", [tabp, vp, vp, sz, vp, vp, vp])
+        _pair(lib, "h3_find", [tabp, vp, vp, sz, vp])
+        _pair(lib, "h3_recs_move", [vp, u64, vp, vp, sz, c.c_uint32, i32])
+        _pair(lib, "h3_close", [tabp, vp, sz, vp, vp, vp, vp, pu64, vp])
+        _pair(lib, "h3_shutdown", [tabp, vp, sz, i32, vp, vp])
         _L = lib
     return _L
 
@@ -1386,6 +1434,205 @@ def h3_write_settings(max_field_section_size: int = (1 << 62) - 1, qpack_max_dta
     buf = np.zeros(n, np.uint8)
     assert lib.qh_h3_write_settings(_vp(buf), _vp(s)) == n
     return buf.tobytes()
+
+
+# ---- streams by id (qh_qpack_h3_dispatch / qh_h3_dispatch_batch, _commit, _open, _find, _recs_move, _close, _shutdown) ----
+
+class H3Smaps:
+    """The stream tables of n connections (include/qhuff.h "Streams by id"):
+    the connection records ``sm`` (H3_SMAP_DTYPE), the slot, entry
+    (H3_SENT_DTYPE) and gap (H3_GAP_DTYPE) arrays and the per-stream pools
+    ``rs_pool`` (H3_STREAM_DTYPE), ``hs_pool`` (HTTP_STATE_DTYPE) and ``us_pool``
+    (H3_UNI_DTYPE), all as bytes on one backend: numpy arrays, or uint8 tensors
+    on `device`.  ``h3_smaps`` makes one; the h3_* functions below work on it."""
+
+    def __init__(self, n: int, rec_cap, server: bool = True, device=None, codec=None):
+        caps = np.ascontiguousarray(np.broadcast_to(np.asarray(rec_cap, np.uint32), (n,)))
+        sm = np.zeros(n, dtype=H3_SMAP_DTYPE)
+        tot = np.zeros(3, np.uint64)
+        _lib.check(_load().qh_h3_smap_init(_vp(sm), n, 1 if server else 0, _vp(caps), _vp(tot)), "qh_h3_smap_init")
+        be = self.be = Backend(device, codec)
+        self.n, self.server = n, bool(server)
+        self.nslots, self.nrecs, self.ngaps = (int(x) for x in tot)
+        self.sm = be.put(sm.view(np.uint8))
+        self.slots, self.gaps = be.zeros(self.nslots * 4), be.zeros(self.ngaps * 16)
+        self.ents, self.rs_pool = be.zeros(self.nrecs * 32), be.zeros(self.nrecs * 32)
+        self.hs_pool, self.us_pool = be.zeros(self.nrecs * 16), be.zeros(self.nrecs * 32)
+
+    ARRAYS = ("sm", "slots", "ents", "gaps", "rs_pool", "hs_pool", "us_pool")
+    _DTYPES = {"sm": H3_SMAP_DTYPE, "slots": np.uint32, "ents": H3_SENT_DTYPE, "gaps": H3_GAP_DTYPE,
+               "rs_pool": H3_STREAM_DTYPE, "hs_pool": HTTP_STATE_DTYPE, "us_pool": H3_UNI_DTYPE}
+
+    def tab(self):
+        p = self.be.ptr
+        return qh_h3d_tab(p(self.sm), self.n, p(self.slots), self.nslots, p(self.ents), self.nrecs, p(self.gaps),
+                          self.ngaps, p(self.rs_pool), p(self.hs_pool), p(self.us_pool))
+
+    def records(self, name: str):
+        """A typed numpy copy of one of ARRAYS."""
+        return self.be.host(getattr(self, name)).view(self._DTYPES[name])
+
+    def load(self, other: "H3Smaps"):
+        """The state of `other` (the same layout, any backend) copied into this one."""
+        for name in self.ARRAYS:
+            setattr(self, name, self.be.put(other.be.host(getattr(other, name))))
+        return self
+
+    def _b(self, a, dtype):
+        if isinstance(a, np.ndarray) or not self.be.dev:
+            a = np.ascontiguousarray(a, dtype).reshape(-1).view(np.uint8)
+            return self.be.put(a) if self.be.dev else a
+        return a
+
+
+def h3_smaps(n: int, rec_cap, server: bool = True, device=None, codec=None) -> H3Smaps:
+    """The stream tables of n connections with room for rec_cap (one number or
+    one per connection) live streams each; `device`: in HBM."""
+    return H3Smaps(n, rec_cap, server=server, device=device, codec=codec)
+
+
+def h3_dispatch(maps: H3Smaps, stream_id, chunks, fin, conn_start, out=None, codec=None):
+    """The arrivals of one call routed to their streams' records
+    (nghttp3_conn_read_stream2 up to its last two lines).  stream_id (uint64),
+    chunks (SPAN_IN_DTYPE) and fin (uint8) per arrival, conn_start (uint32, one
+    entry more than connections); numpy arrays, or uint8 tensors for tables in
+    HBM.  -> dict of byte arrays of the tables' backend: route (int32) and rec
+    (uint32) per arrival and the lists of H3D_LISTS with room for every
+    arrival, plus the host integers n, nbidi, nuni and rv.  `out` (arrays by
+    those names): written in place of fresh ones, and rv is handed back
+    unchecked.  One host wait on the device."""
+    be = maps.be
+    sid, ch, fn = maps._b(stream_id, np.uint64), maps._b(chunks, SPAN_IN_DTYPE), maps._b(fin, np.uint8)
+    start = maps._b(conn_start, np.uint32)
+    n = int(fn.shape[0])
+    o = dict(out) if out is not None else {}
+    for name, unit in (("route", 4), ("rec", 4)) + H3D_LISTS:
+        if name not in o:
+            o[name] = be.empty((maps.n + 1 if name == "u_conn_start" else max(n, 1)) * unit)
+    lists = qh_h3d_lists(*[be.ptr(o[name]) for name, _ in H3D_LISTS])
+    nb, nu = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rv = be.call(_load(), "h3_dispatch", ctypes.byref(maps.tab()), be.ptr(sid), be.ptr(ch), be.ptr(fn), n,
+                 be.ptr(start), be.ptr(o["route"]), be.ptr(o["rec"]), ctypes.byref(lists), ctypes.byref(nb),
+                 ctypes.byref(nu), codec=codec)
+    if out is None:
+        be.check(rv, "h3_dispatch")
+    o.update(n=n, nbidi=int(nb.value), nuni=int(nu.value), rv=rv)
+    return o
+
+
+def h3_dispatch_dev(codec: HuffmanBatchCodec, maps: H3Smaps, stream_id, chunks, fin, conn_start, out=None):
+    """Device-resident form (qh_h3_dispatch_batch) of ``h3_dispatch``."""
+    return h3_dispatch(maps, stream_id, chunks, fin, conn_start, out=out, codec=codec)
+
+
+def h3_commit(maps: H3Smaps, d, codec=None) -> int:
+    """The records of a dispatch `d` (its b_rec, rs_call, hs_call, u_rec,
+    us_call as the round's calls left them) scattered back into the pools;
+    -> the entries passed over (host), or a one-word tensor holding that count
+    (device: no host wait)."""
+    be = maps.be
+    skipped = be.zeros(4)
+    rv = be.call(_load(), "h3_commit", ctypes.byref(maps.tab()), be.ptr(d["b_rec"]), be.ptr(d["rs_call"]),
+                 be.ptr(d["hs_call"]), d["nbidi"], be.ptr(d["u_rec"]), be.ptr(d["us_call"]), d["nuni"],
+                 be.ptr(skipped), codec=codec)
+    be.check(rv, "h3_commit")
+    return skipped if be.dev else int(skipped.view(np.uint32)[0])
+
+
+def h3_commit_dev(codec: HuffmanBatchCodec, maps: H3Smaps, d):
+    return h3_commit(maps, d, codec=codec)
+
+
+def _h3_items(maps, stream_id, conn_start):
+    sid, start = maps._b(stream_id, np.uint64), maps._b(conn_start, np.uint32)
+    return sid, start, int(sid.shape[0]) // 8
+
+
+def h3_open(maps: H3Smaps, cs, stream_id, conn_start, codec=None, checked=True):
+    """A client's own request streams created (the create half of
+    nghttp3_conn_submit_request): ids grouped per connection by conn_start, cs
+    the H3_CONN_DTYPE records.  -> (status int32 bytes, rec uint32 bytes, rv)."""
+    be = maps.be
+    sid, start, n = _h3_items(maps, stream_id, conn_start)
+    status, rec = be.empty(max(n, 1) * 4), be.empty(max(n, 1) * 4)
+    conns = maps._b(cs, H3_CONN_DTYPE)
+    rv = be.call(_load(), "h3_open", ctypes.byref(maps.tab()), be.ptr(conns), be.ptr(sid), n,
+                 be.ptr(start), be.ptr(status), be.ptr(rec), codec=codec)
+    if checked:
+        be.check(rv, "h3_open")
+    return status[:n * 4], rec[:n * 4], rv
+
+
+def h3_open_dev(codec: HuffmanBatchCodec, maps: H3Smaps, cs, stream_id, conn_start, checked=True):
+    return h3_open(maps, cs, stream_id, conn_start, codec=codec, checked=checked)
+
+
+def h3_find(maps: H3Smaps, conn, stream_id, codec=None):
+    """rec (uint32 bytes) for each (conn, stream_id), H3D_NOREC when the stream
+    is not in the table.  No host wait on the device."""
+    be = maps.be
+    cn, sid = maps._b(conn, np.uint32), maps._b(stream_id, np.uint64)
+    n = int(cn.shape[0]) // 4
+    rec = be.empty(max(n, 1) * 4)
+    rv = be.call(_load(), "h3_find", ctypes.byref(maps.tab()), be.ptr(cn), be.ptr(sid), n, be.ptr(rec), codec=codec)
+    be.check(rv, "h3_find")
+    return rec[:n * 4]
+
+
+def h3_find_dev(codec: HuffmanBatchCodec, maps: H3Smaps, conn, stream_id):
+    return h3_find(maps, conn, stream_id, codec=codec)
+
+
+def h3_recs_move(be: Backend, pool, call, idx, rec_bytes: int, scatter: bool, codec=None):
+    """Records of 16, 32 or 64 bytes gathered from `pool` into `call` at
+    idx[j] (uint32 bytes), or scattered back (byte arrays of backend `be`):
+    how a pool the caller keeps beside the tables (H3_TX_DTYPE) is moved."""
+    n = int(idx.shape[0]) // 4
+    rv = be.call(_load(), "h3_recs_move", be.ptr(pool), int(pool.shape[0]) // rec_bytes, be.ptr(call), be.ptr(idx),
+                 n, rec_bytes, 1 if scatter else 0, codec=codec)
+    be.check(rv, "h3_recs_move")
+
+
+def h3_close(maps: H3Smaps, stream_id, conn_start, codec=None, checked=True):
+    """Streams closed (nghttp3_conn_close_stream2), ids grouped per connection
+    by conn_start.  -> dict: status (int32 bytes), cancel_sid / cancel_view
+    (the closed bidi streams, for ``cancel`` of the blocked and partial
+    queues), drained (uint8 per connection), the host integers ncancel, rv."""
+    be = maps.be
+    sid, start, n = _h3_items(maps, stream_id, conn_start)
+    o = {"status": be.empty(max(n, 1) * 4), "cancel_sid": be.empty(max(n, 1) * 8),
+         "cancel_view": be.empty(max(n, 1) * 4), "drained": be.empty(max(maps.n, 1))}
+    nc = ctypes.c_uint64(0)
+    rv = be.call(_load(), "h3_close", ctypes.byref(maps.tab()), be.ptr(sid), n, be.ptr(start), be.ptr(o["status"]),
+                 be.ptr(o["cancel_sid"]), be.ptr(o["cancel_view"]), ctypes.byref(nc), be.ptr(o["drained"]),
+                 codec=codec)
+    if checked:
+        be.check(rv, "h3_close")
+    o.update(n=n, ncancel=int(nc.value), rv=rv)
+    return o
+
+
+def h3_close_dev(codec: HuffmanBatchCodec, maps: H3Smaps, stream_id, conn_start, checked=True):
+    return h3_close(maps, stream_id, conn_start, codec=codec, checked=checked)
+
+
+def h3_shutdown(maps: H3Smaps, kind: int = H3D_SHUTDOWN, csel=None, codec=None, checked=True):
+    """nghttp3_conn_shutdown (H3D_SHUTDOWN) or _submit_shutdown_notice
+    (H3D_NOTICE) for the listed connections (uint32; None: all).  ->
+    (goaway_id uint64 bytes, status int32 bytes, rv): the ids to frame."""
+    be = maps.be
+    sel = None if csel is None else maps._b(csel, np.uint32)
+    n = maps.n if sel is None else int(sel.shape[0]) // 4
+    ids, status = be.empty(max(n, 1) * 8), be.empty(max(n, 1) * 4)
+    rv = be.call(_load(), "h3_shutdown", ctypes.byref(maps.tab()), be.list_ptr(sel), n, kind, be.ptr(ids),
+                 be.ptr(status), codec=codec)
+    if checked:
+        be.check(rv, "h3_shutdown")
+    return ids[:n * 8], status[:n * 4], rv
+
+
+def h3_shutdown_dev(codec: HuffmanBatchCodec, maps: H3Smaps, kind: int = H3D_SHUTDOWN, csel=None, checked=True):
+    return h3_shutdown(maps, kind, csel, codec=codec, checked=checked)
 
 
 class DynamicTable:
